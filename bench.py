@@ -9,10 +9,15 @@
 
 A "step" is one whole BFS traversal (label reset + every advance+filter level) from one seeded source, inputs resident
 in HBM.  value = sum over steps of m_t (CSR entries of reached vertices) / wall time of the K steps / 1e6,
-max over ranks.  The line is only printed with exit status 0 when the first timed source's labels equal the oracle's
-(or, at RMAT-26, pass the BFS-tree property check): a wrong traversal that ends early would report a HIGHER rate.
+max over ranks.  With --full the line is only printed with exit status 0 when the first timed source's labels equal the
+oracle's (or, at RMAT-26, pass the BFS-tree property check): a wrong traversal that ends early would report a HIGHER rate.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the line (--dump-outputs DIR: and writes the last timed step's
+outputs as DIR/<name>.npy).  Everything else -- the oracle check, the CPU baseline, the per-call, roofline and per-level
+passes, at N > 1 the config5 and replicas measurements -- runs only with --full (--validate turns the oracle check on by
+itself); without it those objects are null.
+
+Extra objects on the JSON line (--full):
   roofline     the product kernel k_bfs_push (one launch per slot: long rows + short rows, or a chain of small levels):
                algorithmic bytes (8 B/edge + 20 B/frontier vertex) per launch / average launch duration (HIP
                events around every launch, on the launch stream, in a second pass over the same sources), vs 8 TB/s.
@@ -71,8 +76,46 @@ def parse():
     ap.add_argument("--file", default=None, help="MatrixMarket file instead of the synthetic R-MAT")
     ap.add_argument("--undirected", action="store_true", help="--file: append the swapped copy of every entry")
     ap.add_argument("--src", type=int, default=None, help="source vertex (default: seeded sources; --file: 0)")
-    ap.add_argument("--validate", action="store_true", help="compare EVERY timed source with the oracle (default: the first)")
-    return ap.parse_args()
+    ap.add_argument("--validate", action="store_true", help="compare EVERY timed source with the oracle (default, with --full: the first)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the oracle check, the CPU baseline, the per-call / roofline / per-level passes and, at "
+                         "N > 1, config5 and replicas (a plain run only sets up, warms up and times the steps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (labels / distances / reduced values, one GPU) "
+                         "as DIR/<name>.npy in float32 or float64, at most 64 MB in all (a fixed seeded sample of a larger output)")
+    args = ap.parse_args()
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs: one GPU only")
+    if not args.full:
+        args.no_cpu_baseline = True
+        args.no_check = args.no_check or not args.validate
+    return args
+
+
+DUMP_BYTES = 60 * 1000 * 1000          # --dump-outputs: everything written, headers aside, stays under 64 MB
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: {name: array} of the last timed step -> d/<name>.npy.  float32 outputs, and integer ones whose values
+    float32 holds exactly, as float32; other integers as float64.  The arrays share DUMP_BYTES, the smallest served first;
+    one over its share is written as a fixed sample of its entries (seeded: the same positions for every run of the same
+    arguments), the sampled positions beside it as <name>_index.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.asarray(v).ravel() for k, v in arrays.items()}
+    left = DUMP_BYTES
+    for i, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].size)):
+        exact32 = a.dtype == np.float32 or (a.dtype.kind in "iu" and (a.size == 0 or int(np.abs(a.astype(np.int64)).max()) < (1 << 24)))
+        a = a.astype(np.float32 if exact32 else np.float64)
+        share = left // (len(arrays) - i)
+        if a.nbytes > share:
+            k = share // (a.itemsize + 8)
+            idx = np.sort(np.random.default_rng(12345).choice(a.size, size=k, replace=False))
+            np.save(os.path.join(d, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+            left -= 8 * k
+        left -= a.nbytes
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def source_sha():
@@ -192,6 +235,8 @@ def main():
     from mini_amd import rmat
 
     if world > 1 or force_dist:
+        if args.dump_outputs:
+            sys.exit("bench.py: --dump-outputs: one GPU only")
         import bench_dist
         return bench_dist.bench_main(args, rank, world, local_rank)
 
@@ -330,10 +375,14 @@ def bench_bfs(args, ctx, stream):
         L = bfs.STATS_LEN
         stats = [bfs.stats_dict(raw[i * L:(i + 1) * L]) for i in range(len(timed))]
     dev_ms = ev0.elapsed_time(ev1)
-    # Per-call pass (always): the same K sources, one call each, each timed on the host -> the per-call mean beside the
+    if args.dump_outputs:
+        # the labels the timed call leaves are its last source's (batch or per call); m_t / reached / levels of that traversal
+        last = stats[-1] if stats else {"levels": 0, "reached": 0, "m_t": 0}
+        dump_outputs(args.dump_outputs, {"labels": bfs.labels(), "counts": [last["levels"], last["reached"], last["m_t"]]})
+    # Per-call pass (--full): the same K sources, one call each, each timed on the host -> the per-call mean beside the
     # batched figure, and the per-source median SURVEY 8d asks for
     per_src_s = []
-    for s in timed:
+    for s in (timed if args.full else []):
         st1 = bfs.new_stats()
         torch.cuda.synchronize()
         tc = time.perf_counter()
@@ -345,10 +394,11 @@ def bench_bfs(args, ctx, stream):
     # and of the queue build behind it (on the launch stream).  A pass of its own because every event record between two
     # kernels leaves a ~6 us gap on the stream (rocprofv3 kernel trace, profiles/): inside the timed region they would cost
     # several % of `value`.
+    passes = timed if args.full else []
     bfs.set_kernel_timing(2)
     stats_timed, kernel_times = [], []
     build_launches, build_ns = 0, 0
-    for s in timed:
+    for s in passes:
         stats_timed.append(bfs.run(s, mode, args.alpha))
         slots_hist[stats_timed[-1]["slots"]] = slots_hist.get(stats_timed[-1]["slots"], 0) + 1
         kt = bfs.kernel_times()
@@ -358,7 +408,7 @@ def bench_bfs(args, ctx, stream):
     # ... and once more with the launch split into its parts (long rows / short rows), for the breakdown only
     bfs.set_kernel_timing(1)
     parts = {"stream": {"launches": 0, "ns": 0, "edges": 0, "vertices": 0}, "wave": {"launches": 0, "ns": 0, "edges": 0, "vertices": 0}}
-    for s in timed:
+    for s in passes:
         bfs.run(s, mode, args.alpha)
         k = bfs.kernel_times()
         for name in parts:
@@ -370,7 +420,7 @@ def bench_bfs(args, ctx, stream):
     # distance from the traversal's biggest one
     by_rel = {}
     if mode == mini_amd.MGX_BFS_PUSH:
-        for s in timed[:32]:
+        for s in passes[:32]:
             bfs.run(s, mode, args.alpha)
             tms, tr = bfs.level_times_ms(), bfs.level_trace()
             L = min(len(tms), len(tr))
@@ -496,15 +546,15 @@ def bench_bfs(args, ctx, stream):
                       "graph": args.graph if not args.file else "file",
                       "seed": seed, "parallelism": "1 GPU", "submission": "per_call" if args.per_call else "batch",
                       "layout": "hub-first (degree-sorted) copy + unit blocks for the fused kernel" if use_layout else "generator ids"},
-           "roofline": roofline, "cpu_baseline": cpu, "parity_vs_oracle": parity,
-           "per_call": {"ms_per_step": round(sum(per_src_s) * 1e3 / K, 4), "value": round(m_t / max(sum(per_src_s), 1e-12) / 1e6, 2),
+           "roofline": roofline if args.full else None, "cpu_baseline": cpu, "parity_vs_oracle": parity,
+           "per_call": None if not args.full else {"ms_per_step": round(sum(per_src_s) * 1e3 / K, 4), "value": round(m_t / max(sum(per_src_s), 1e-12) / 1e6, 2),
                         "ms_per_step_median": round(med, 4),
                         "value_median_source": round(per_src_rate[len(per_src_rate) // 2], 2) if per_src_rate else None,
                         "note": "the same %d sources, one mgx_bfs_run call each, each timed on the host (call to return); the median is "
                                 "over sources (SURVEY 8d)" % len(timed)},
            "graph500_MTEPS": round(m_t / 2.0 / elapsed / 1e6, 2),
            "graph500_note": "Graph500 convention: undirected input edges inside the reached component / time = m_t / 2 on the symmetrised CSR (SURVEY 8d)",
-           "batch_reruns": reruns, "slots_needed_hist": {str(k): v for k, v in sorted(slots_hist.items())},
+           "batch_reruns": reruns, "slots_needed_hist": {str(k): v for k, v in sorted(slots_hist.items())} if args.full else None,
            "device_ms_per_step": round(dev_ms / max(args.steps, 1), 4),
            "avg_levels": round(sum(st["levels"] for st in stats) / K, 2),
            "avg_slots": round(sum(st["slots"] for st in stats) / K, 2),
@@ -560,10 +610,13 @@ def bench_sssp(args, ctx, stream):
     relax = sum(st["relaxations"] for st in stats)
     ftot = sum(st["frontier_total"] for st in stats)
     iters = sum(st["iterations"] for st in stats)
-    # roofline pass: the same sources with HIP events around every k_sssp_relax launch (on the launch stream)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"distances": sssp.distances()})
+    passes = timed if args.full else []
+    # roofline pass (--full): the same sources with HIP events around every k_sssp_relax launch (on the launch stream)
     sssp.set_kernel_timing(True)
     k_launch, k_ns, relax2, ftot2 = 0, 0, 0, 0
-    for s in timed:
+    for s in passes:
         st = sssp.run(s)
         kt = sssp.kernel_times()
         k_launch += kt["launches"]; k_ns += kt["ns"]
@@ -572,7 +625,7 @@ def bench_sssp(args, ctx, stream):
     # ... and the iterations of the product's launches from the device-side stamps (no events on the stream), lined up by their distance from
     # the run's heaviest one: time from an iteration's opener to the next one's (relax + sweep + queue build)
     by_rel = {}
-    for s in timed[:32]:
+    for s in passes[:32]:
         sssp.run(s)
         tr = sssp.iteration_trace()
         if not tr:
@@ -644,7 +697,7 @@ def bench_sssp(args, ctx, stream):
                                   "copy with weights (layout_build_s)" % (args.scale, args.edgefactor, n, m, args.steps),
                       "scale": args.scale, "edgefactor": args.edgefactor, "seed": seed, "parallelism": "1 GPU",
                       "layout": "generator ids" if args.no_layout else "hub-first (degree-sorted) copy with weights"},
-           "roofline": roofline, "cpu_baseline": cpu, "parity_vs_oracle": parity,
+           "roofline": roofline if args.full else None, "cpu_baseline": cpu, "parity_vs_oracle": parity,
            "traversed_MTEPS": None,
            "relaxations_per_source": relax // K, "frontier_total_per_source": ftot // K, "iterations_per_source": round(iters / K, 2),
            "device_ms_per_step": round(dev_ms / max(args.steps, 1), 4), "graph_build_s": round(t_build, 2), "layout_build_s": round(t_layout, 2),
@@ -704,8 +757,10 @@ def bench_pr(args, ctx, stream):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     dev_ms = ev0.elapsed_time(ev1)
-    # roofline pass: events around each operator call (all its kernels run on this stream; the count read-back included)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"reduced": red.cpu().numpy()})
+    # roofline pass (--full): events around each operator call (all its kernels run on this stream; the count read-back included)
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps if args.full else 0)]
     for a, b in evs:
         a.record(stream)
         mini_amd.segreduce(graph, f, vals, 0.0, red, "f32_plus")
@@ -713,7 +768,7 @@ def bench_pr(args, ctx, stream):
     torch.cuda.synchronize()
     op_ms = sum(a.elapsed_time(b) for a, b in evs) / max(len(evs), 1)
     alg = 8.0 * nz + 16.0 * n
-    achieved = alg / (op_ms / 1e3) / 1e9
+    achieved = alg / (op_ms / 1e3) / 1e9 if op_ms > 0 else 0.0
     sha = source_sha()
     traffic, traffic_note = _pmc_traffic(args, "neighbour-reduce operator", sha)
     roofline = {"bound": "hbm", "kernel": "neighbour-reduce operator (every kernel of one mgx_segreduce_f32_plus call over the full frontier: "
@@ -758,7 +813,7 @@ def bench_pr(args, ctx, stream):
                       "layout": "generator ids" if args.no_layout else "the operator is called with generator ids; for a full frontier the library reads "
                                 "the graph's hub-first copy (the long rows regrouped by slice of their destinations -- nr_slices --, degree classes "
                                 "for the short rows; untimed one-time preprocessing: layout_build_s + nr_slices_build_s)"},
-           "roofline": roofline, "cpu_baseline": cpu, "parity_vs_oracle": parity, "parity_tolerance": "rtol 2e-5 against the serial float32 oracle (float sum order); where the oracle's own rounding exceeds that (rows of several 10^5 entries): rtol 2e-6 against the float64 sum of the same values, the oracle within 1e-3 of it",
+           "roofline": roofline if args.full else None, "cpu_baseline": cpu, "parity_vs_oracle": parity, "parity_tolerance": "rtol 2e-5 against the serial float32 oracle (float sum order); where the oracle's own rounding exceeds that (rows of several 10^5 entries): rtol 2e-6 against the float64 sum of the same values, the oracle within 1e-3 of it",
            "device_ms_per_step": round(dev_ms / max(args.steps, 1), 4), "graph_build_s": round(t_build, 2), "layout_build_s": round(t_layout, 2),
            "nr_slices_build_s": round(t_slices, 2), "nr_slices": None if args.no_layout else graph.nr_slices_info(),
            "source_sha": sha}

@@ -1,7 +1,7 @@
 """bench_dist.py -- bench.py's body for N > 1 (one process per GPU, launched by torch.distributed.run; RCCL over xGMI).
 
 Part of the benchmark, not of the product: it drives mini_amd.dist_bfs (the partitioned traversal) and -- as bench.py
-does at N = 1 -- checks the first timed source against the CPU oracle before it prints the line.
+does at N = 1 -- checks the first timed source against the CPU oracle before it prints the line (bench.py --full).
 """
 import os
 import sys
@@ -212,6 +212,14 @@ def bench_single_sharded(args, ctx, shards):
         levels += sts[0]["levels"]
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        # the last timed traversal's labels, hub-first ids, every shard's rows in place
+        from bench import dump_outputs
+        lab = np.empty(n, dtype=np.int32)
+        for r, e in enumerate(engs):
+            lab[r::shards] = e.labels()
+        dump_outputs(args.dump_outputs, {"labels": lab})
+        del lab
     parity = None
     if not args.no_check and steps > 0:
         src = sources[warmup]
@@ -305,9 +313,9 @@ def _measure_replicas(args, rank, world, ctx, device, stream):
 def bench_main(args, rank, world, local_rank):
     """bench.py body for N > 1 (one process per GPU, RCCL).  --scaling strong (default): the SAME RMAT-<scale> graph
     partitioned over the N GPUs (the metric's "RMAT-22 @1/2/4/8"; --scale 26 at N = 8 is BASELINE config 5);
-    --scaling weak: RMAT-(scale + log2 N), a fixed share per GPU.  The first timed source is verified before the line
+    --scaling weak: RMAT-(scale + log2 N), a fixed share per GPU.  With --full the first timed source is verified before the line
     is printed: against the oracle (rank 0 rebuilds the whole graph; scales <= 23) or, above that, by the BFS-tree
-    properties over every rank's own rows.  At N = 8 with the default workload (strong RMAT-22) the line also carries
+    properties over every rank's own rows.  With --full at N = 8 and the default workload (strong RMAT-22) the line also carries
     `config5`: the same measurement on RMAT-26 -- BASELINE config 5, the graph the north star's ">= 5x at 8 GPUs" is
     quoted on -- with fewer sources (MGX_BENCH_CONFIG5=0 switches it off)."""
     import json
@@ -320,11 +328,11 @@ def bench_main(args, rank, world, local_rank):
     r = _measure(args, rank, world, local_rank, ctx, device, gscale, args.steps, args.warmup, weak)
     c5 = None
     want5 = os.environ.get("MGX_BENCH_CONFIG5", "auto")
-    if (want5 == "1" or (want5 == "auto" and world == 8 and gscale == 22)) and not weak and r["parity"] is not False:
+    if args.full and (want5 == "1" or (want5 == "auto" and world == 8 and gscale == 22)) and not weak and r["parity"] is not False:
         c5_scale = int(os.environ.get("MGX_BENCH_CONFIG5_SCALE", "26"))
         c5 = _measure(args, rank, world, local_rank, ctx, device, c5_scale, min(args.steps, 16), 1, False)
     rep = None
-    if os.environ.get("MGX_BENCH_REPLICAS", "auto") != "0" and not weak and dist.get_backend() == "nccl" and gscale <= 24:
+    if args.full and os.environ.get("MGX_BENCH_REPLICAS", "auto") != "0" and not weak and dist.get_backend() == "nccl" and gscale <= 24:
         rep = _measure_replicas(args, rank, world, ctx, device, stream)
     m_t, elapsed, levels, parity, ranks_seen = r["m_t"], r["elapsed"], r["levels"], r["parity"], r["ranks_seen"]
     if c5 is not None and c5["parity"] is False:

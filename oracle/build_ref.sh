@@ -8,13 +8,13 @@
 # against THIS repo's data model + operator headers (include/gunrock/{graph,frontier,problem,
 # enactor,intrinsics,advance,filter,neighborhood,test_utils}.hxx, kernels in include/mgx/).
 # Nothing of the reference is copied: its files are read where they lie under /root/reference
-# through a symlink farm in a temp dir; only the binaries land in tests/dropin/_bin/
-# (git-ignored, shipped to the GPU box like any other built artefact).
-# Only runs where /root/reference exists (this container); the GPU box uses the prebuilt files.
+# through a symlink farm in a temp dir; only the binaries land in oracle/_ref/ (git-ignored; built by
+# __graft_entry__.build() where the reference tree is present, and carried to the GPU machine with the other build products).
+# Without a reference tree it does nothing: the tests use the binaries built beforehand.
 set -e
 REF=${REF:-/root/reference}
-ROOT=$(cd "$(dirname "$0")/../.." && pwd)
-OUT=$ROOT/tests/dropin/_bin
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+OUT=$ROOT/oracle/_ref
 [ -d "$REF/gunrock/src" ] || { echo "no reference tree at $REF: skipping"; exit 0; }
 FARM=$(mktemp -d)
 trap 'rm -rf "$FARM"' EXIT

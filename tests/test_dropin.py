@@ -1,18 +1,18 @@
 """Drop-in boundary: the reference's own BFS/SSSP/PR (and k-core) enactors, problems, functors and test
-drivers, unmodified, compiled against this repo's operator headers (tests/dropin/build_dropin.sh)."""
+drivers, unmodified, compiled against this repo's operator headers (oracle/build_ref.sh)."""
 import os
 import subprocess
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "dropin", "_bin")
+BIN = os.path.join(ROOT, "oracle", "_ref")
 GOLD = os.path.join(ROOT, "tests", "golden")
 
 
 @pytest.mark.skipif(not os.path.isdir("/root/reference/gunrock/src"), reason="reference tree not present")
 def test_reference_sources_compile_unchanged_against_our_operator_headers():
-    subprocess.check_call(["bash", os.path.join(ROOT, "tests", "dropin", "build_dropin.sh")])
+    subprocess.check_call(["bash", os.path.join(ROOT, "oracle", "build_ref.sh")])
     for t in ("bfs", "sssp", "pr", "kcore"):
         assert os.path.exists(os.path.join(BIN, "ref_test_" + t))
 
@@ -20,7 +20,7 @@ def test_reference_sources_compile_unchanged_against_our_operator_headers():
 def _run(name, *args):
     exe = os.path.join(BIN, name)
     if not os.path.exists(exe):
-        pytest.skip("%s not prebuilt (built only where /root/reference exists)" % name)
+        pytest.skip("%s not prebuilt (built only where the reference tree is present)" % name)
     return subprocess.run([exe] + list(args), capture_output=True, text=True, timeout=300)
 
 

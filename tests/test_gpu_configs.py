@@ -586,10 +586,41 @@ def test_rmat26_on_one_gpu_as_two_shards(gpu_ctx):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--scale", "26", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--scale", "26", "--steps", "3", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["config"]["scale"] == 26 and line["parity_vs_oracle"] is True
     assert line["config"]["parallelism"] == "1 GPU, 2 shards in turn"
     assert line["value"] > 0 and line["avg_levels"] >= 5
+
+
+def test_bench_plain_run_dumps_the_last_step(oracle, tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` (no --full): one line with the headline only -- no oracle check,
+    CPU baseline or roofline passes -- and DIR/labels.npy holding the labels of the last timed source, equal to the
+    oracle's BFS on the same seeded graph; a second run with the same arguments writes the same arrays"""
+    import json
+    import subprocess
+    import sys
+    from mini_amd import rmat
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    scale, steps, warmup = 12, 5, 2
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("out%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--scale", str(scale), "--steps", str(steps),
+                            "--warmup", str(warmup), "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == steps and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["roofline"] is None and line["cpu_baseline"] is None and line["parity_vs_oracle"] is None
+        dumps.append({f: np.load(d / f) for f in ("labels.npy", "counts.npy")})
+    assert all(a.dtype in (np.float32, np.float64) for a in dumps[0].values())
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+    n, ro, ci, _ = oracle.rmat_csr(scale, 16, scale)
+    src = rmat.pick_sources(ro, steps + warmup, scale)[-1]
+    want = oracle.bfs_cpu(ro, ci, src)
+    assert np.array_equal(dumps[0]["labels.npy"], want.astype(np.float64))
+    levels, reached, m_t = dumps[0]["counts.npy"]
+    assert reached == (want >= 0).sum() and m_t == np.diff(ro)[want >= 0].sum()

@@ -6,7 +6,7 @@ O=gpurun_out/ab_libs_n; rm -rf $O; mkdir -p $O
 for i in $(seq 1 $R); do
   for L in "$@"; do
     tag=$(basename $L .so)_$i
-    MGX_LIB=$L timeout 300 python bench.py --no-cpu-baseline $BENCH_ARGS > $O/$tag.json 2> $O/$tag.err || echo "$tag failed: $(tail -n 2 $O/$tag.err)"
+    MGX_LIB=$L timeout 300 python bench.py --full --no-cpu-baseline $BENCH_ARGS > $O/$tag.json 2> $O/$tag.err || echo "$tag failed: $(tail -n 2 $O/$tag.err)"
   done
 done
 python - "$O" <<'PY'

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What "drop-in" costs: one BFS traversal of the same R-MAT graph from the same sources
   (i)   the reference's UNCHANGED bfs_enactor_t + bfs_functor_t (a CAS per edge) on this repo's advance / filter operators
-        (tests/dropin/_bin/ref_bench_bfs: warm, best of 3 per source),
+        (oracle/_ref/ref_bench_bfs: warm, best of 3 per source),
   (ii)  the repo's restatement of the functor (reads the label before the CAS) on the same operators (mgx_bfs_enact_pushpull),
   (iii) the fused device-resident traversal behind the same data model (mgx_bfs_run),
 each with its algorithmic rate against the 8 TB/s roof (8 B per traversed edge + 20 B per reached vertex).
@@ -24,7 +24,7 @@ def frac(m_t, reached, ms):
     return (8.0 * m_t + 20.0 * reached) / (ms * 1e-3) / 1e9 / PEAK
 rows = []
 # (i) the reference's own enactor and functor
-exe = os.path.join(ROOT, "tests", "dropin", "_bin", "ref_bench_bfs")
+exe = os.path.join(ROOT, "oracle", "_ref", "ref_bench_bfs")
 ref_ms = {}
 if os.path.exists(exe):
     with tempfile.TemporaryDirectory() as td:

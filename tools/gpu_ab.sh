@@ -4,7 +4,7 @@ ulimit -c 0
 mkdir -p gpurun_out; rm -f gpurun_out/ab.log
 for v in $VALS; do
   export $VAR=$v
-  timeout 300 python3 bench.py --steps 16 --warmup 3 --no-cpu-baseline 2>&1 | tail -1 | python3 -c "
+  timeout 300 python3 bench.py --full --steps 16 --warmup 3 --no-cpu-baseline 2>&1 | tail -1 | python3 -c "
 import sys, json
 l = sys.stdin.read().strip()
 try:

@@ -6,13 +6,13 @@ cd $R
 ulimit -c 0
 timeout 900 python -m pytest tests/test_gpu_parity.py -x -q -k "neighbour_reduce or pr_matches" > $O/pytest_nr.log 2>&1; tail -3 $O/pytest_nr.log
 for v in 1 0 1 0; do
-  MGX_NR_SLICED=$v timeout 300 python3 bench.py --mode pr --steps 32 --warmup 2 --no-cpu-baseline > $O/pr_$v.log 2>&1
+  MGX_NR_SLICED=$v timeout 300 python3 bench.py --full --mode pr --steps 32 --warmup 2 --no-cpu-baseline > $O/pr_$v.log 2>&1
   grep '^{' $O/pr_$v.log | tail -1 | python3 -c "
 import sys, json
 j = json.loads(sys.stdin.read()); print('MGX_NR_SLICED=$v: %.4f ms  frac %.3f  parity %s  slices %s build %.2fs' % (j['ms_per_step'], j['roofline']['frac'], j.get('parity_vs_oracle'), j.get('nr_slices'), j.get('nr_slices_build_s', -1)))" >> $O/ab.log 2>&1 || tail -5 $O/pr_$v.log >> $O/ab.log
 done
 for i in 1 2; do
-  timeout 300 python3 bench.py --steps 64 --warmup 2 --cpu-seconds 3 > $O/push_$i.log 2>&1
+  timeout 300 python3 bench.py --full --steps 64 --warmup 2 --cpu-seconds 3 > $O/push_$i.log 2>&1
   grep '^{' $O/push_$i.log | tail -1 | python3 -c "
 import sys, json
 j = json.loads(sys.stdin.read()); print('push run $i: %.4f ms  %.1f GTEPS  parity %s  push frac %.3f slot %.3f whole %.3f' % (j['ms_per_step'], j['value']/1e3, j.get('parity_vs_oracle'), j['roofline']['frac'], j['roofline']['slot_frac'], j['roofline']['whole_bfs_frac']))" >> $O/ab.log 2>&1 || tail -5 $O/push_$i.log >> $O/ab.log
@@ -21,7 +21,7 @@ cat $O/ab.log
 timeout 600 python -m pytest tests/test_gpu_parity.py -x -q -k "kernel_variants" > $O/pytest_variants.log 2>&1; tail -3 $O/pytest_variants.log
 cd /tmp && export TMPDIR=/tmp
 for v in 1 0; do
-  MGX_NR_SLICED=$v timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_pr_$v -- python3 $R/bench.py --mode pr --steps 16 --warmup 2 --no-cpu-baseline --no-check > $O/trace_pr_$v.log 2>&1
+  MGX_NR_SLICED=$v timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_pr_$v -- python3 $R/bench.py --full --mode pr --steps 16 --warmup 2 --no-cpu-baseline --no-check > $O/trace_pr_$v.log 2>&1
 done
 cd $R
 python3 - <<'PY'

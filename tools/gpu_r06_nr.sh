@@ -5,4 +5,4 @@ timeout 1200 python -m pytest tests/test_gpu_parity.py -x -q -k "neighbour_reduc
 for sw in 1 0; do
   echo "=== MGX_NR_SUBSET=$sw"; MGX_NR_SUBSET=$sw timeout 600 python tools/pr_bench.py 2>&1 | grep -v amdgpu.ids | grep "library layout"
 done > $O/pr_s22.txt; cat $O/pr_s22.txt
-timeout 300 python bench.py --mode pr --no-cpu-baseline > $O/bench_pr.json 2> $O/bench_pr.err; cut -c1-400 $O/bench_pr.json
+timeout 300 python bench.py --full --mode pr --no-cpu-baseline > $O/bench_pr.json 2> $O/bench_pr.err; cut -c1-400 $O/bench_pr.json

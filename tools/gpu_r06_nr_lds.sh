@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06_nr_lds; rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for set in "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_ACTIVE_INST_LDS" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_VALU SQ_INSTS_SALU" "TCP_TCC_READ_REQ_sum TCP_PENDING_STALL_CYCLES_sum TA_BUSY_avr GRBM_GUI_ACTIVE"; do
   tag=$(echo $set | cut -d' ' -f1)
-  MGX_NR_PARTS=${PARTS:-2} timeout 600 rocprofv3 --pmc $set --output-format csv -d $O/p_$tag -- python3 $R/bench.py --mode pr --steps 4 --warmup 1 --no-cpu-baseline --no-check > $O/p_$tag.log 2>&1
+  MGX_NR_PARTS=${PARTS:-2} timeout 600 rocprofv3 --pmc $set --output-format csv -d $O/p_$tag -- python3 $R/bench.py --full --mode pr --steps 4 --warmup 1 --no-cpu-baseline --no-check > $O/p_$tag.log 2>&1
 done
 cd $R
 python3 - <<'PY'

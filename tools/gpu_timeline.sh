@@ -7,7 +7,7 @@ i=0
 for cfg in "$@"; do
   i=$((i+1))
   for kv in $cfg; do export "$kv"; done
-  timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/trace$i -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-check > $O/run$i.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/trace$i -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-check > $O/run$i.log 2>&1
   echo "=== [$cfg] trace rc=$?" | tee -a $O/windows.txt
   for kv in $cfg; do unset "${kv%%=*}"; done
   for occ in 4 7; do

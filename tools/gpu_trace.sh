@@ -2,7 +2,7 @@
 # kernel-trace stats of the bench command -> gpurun_out/trace_quick/kernel_stats.txt
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/trace_quick; rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --steps 16 --warmup 2 --no-cpu-baseline --no-check "$@" > $O/bench.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --full --steps 16 --warmup 2 --no-cpu-baseline --no-check "$@" > $O/bench.log 2>&1
 echo "trace rc=$?"; tail -1 $O/bench.log | cut -c1-300
 cd $R
 python3 - <<'PY'

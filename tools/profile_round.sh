@@ -16,31 +16,31 @@ echo "smoke rc=$?"; tail -1 $O/smoke.log
 # very run report as roofline.traffic
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 900 rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -- python3 $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-check > $O/pmc_$c.log 2>&1
+  timeout 900 rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -- python3 $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-check > $O/pmc_$c.log 2>&1
   echo "pmc $c rc=$?"
-  timeout 900 rocprofv3 --pmc $c --output-format csv -d $O/pmc_sssp_$c -- python3 $R/bench.py --mode sssp --steps 4 --warmup 1 --no-cpu-baseline --no-check > $O/pmc_sssp_$c.log 2>&1
+  timeout 900 rocprofv3 --pmc $c --output-format csv -d $O/pmc_sssp_$c -- python3 $R/bench.py --full --mode sssp --steps 4 --warmup 1 --no-cpu-baseline --no-check > $O/pmc_sssp_$c.log 2>&1
   echo "pmc sssp $c rc=$?"
-  timeout 900 rocprofv3 --pmc $c --output-format csv -d $O/pmc_pr_$c -- python3 $R/bench.py --mode pr --steps 4 --warmup 1 --no-cpu-baseline --no-check > $O/pmc_pr_$c.log 2>&1
+  timeout 900 rocprofv3 --pmc $c --output-format csv -d $O/pmc_pr_$c -- python3 $R/bench.py --full --mode pr --steps 4 --warmup 1 --no-cpu-baseline --no-check > $O/pmc_pr_$c.log 2>&1
   echo "pmc pr $c rc=$?"
 done
 cd $R
 python3 tools/summarize_profiles.py $O > /dev/null 2>&1
 [ -s $O/pmc_traffic.json ] && cp $O/pmc_traffic.json $R/profiles/pmc_traffic.json
-timeout 900 python bench.py > $O/bench.log 2>&1
+timeout 900 python bench.py --full > $O/bench.log 2>&1
 echo "bench rc=$?"; tail -1 $O/bench.log | cut -c1-300
-timeout 900 python bench.py --per-call --steps 64 > $O/bench_per_call.log 2>&1
-timeout 900 python bench.py --mode sssp > $O/bench_sssp.log 2>&1
+timeout 900 python bench.py --full --per-call --steps 64 > $O/bench_per_call.log 2>&1
+timeout 900 python bench.py --full --mode sssp > $O/bench_sssp.log 2>&1
 echo "bench sssp rc=$?"; tail -1 $O/bench_sssp.log | cut -c1-300
-timeout 900 python bench.py --mode pr > $O/bench_pr.log 2>&1
+timeout 900 python bench.py --full --mode pr > $O/bench_pr.log 2>&1
 echo "bench pr rc=$?"; tail -1 $O/bench_pr.log | cut -c1-300
 timeout 600 python tools/bfs_levels.py --scale 22 --runs 2 > $O/levels.log 2>&1
 timeout 600 python tools/sssp_iterations.py --runs 2 > $O/sssp_iterations.log 2>&1
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --steps 16 --warmup 2 --no-cpu-baseline --no-check > $O/trace_bench.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --full --steps 16 --warmup 2 --no-cpu-baseline --no-check > $O/trace_bench.log 2>&1
 echo "trace rc=$?"
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_sssp -- python3 $R/bench.py --mode sssp --steps 8 --warmup 2 --no-cpu-baseline --no-check > $O/trace_sssp.log 2>&1
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_pr -- python3 $R/bench.py --mode pr --steps 16 --warmup 2 --no-cpu-baseline --no-check > $O/trace_pr.log 2>&1
-timeout 900 rocprofv3 --pmc TCC_EA0_ATOMIC_sum TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum --output-format csv -d $O/pmc_TCC -- python3 $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-check > $O/pmc_TCC.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_sssp -- python3 $R/bench.py --full --mode sssp --steps 8 --warmup 2 --no-cpu-baseline --no-check > $O/trace_sssp.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_pr -- python3 $R/bench.py --full --mode pr --steps 16 --warmup 2 --no-cpu-baseline --no-check > $O/trace_pr.log 2>&1
+timeout 900 rocprofv3 --pmc TCC_EA0_ATOMIC_sum TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum --output-format csv -d $O/pmc_TCC -- python3 $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-check > $O/pmc_TCC.log 2>&1
 cd $R
 for m in sssp pr; do
   f=$(ls $O/trace_$m/*/*kernel_stats.csv 2>/dev/null | head -1)
@@ -71,14 +71,14 @@ bash tools/gpu_d2_native_stats.sh 22 8 "" > /dev/null 2>&1
 cp $R/gpurun_out/d2native/summary.txt $O/dist2_native_kernels_22_8.txt 2>/dev/null
 timeout 600 python tools/dist2_loopback.py 22 8 reduce 8 2>/dev/null | grep -v amdgpu.ids | tail -10 > $O/dist2_loopback_22_8.log
 # (round 5) RMAT-26 on one GPU, the graphs off RMAT-22, what the drop-in costs, the timed batch per kernel
-timeout 900 python bench.py --scale 26 --steps 8 --warmup 1 > $O/bench_rmat26_1gpu.log 2>&1
+timeout 900 python bench.py --full --scale 26 --steps 8 --warmup 1 > $O/bench_rmat26_1gpu.log 2>&1
 for g in "uniform 22 16" "grid2d 22 4" "rmat 23 32" "rmat 24 16" "rmat 25 16" "rmat 20 32"; do
   set -- $g
-  timeout 600 python bench.py --graph $1 --scale $2 --steps $3 --warmup 2 --cpu-seconds 5 > $O/bench_$1_$2.log 2>&1
+  timeout 600 python bench.py --full --graph $1 --scale $2 --steps $3 --warmup 2 --cpu-seconds 5 > $O/bench_$1_$2.log 2>&1
 done
 # (round 6) the neighbour-reduce above RMAT-22: hot slices by graph size
 for sc in 23 24 25; do
-  timeout 600 python bench.py --mode pr --scale $sc --steps 16 --warmup 2 --cpu-seconds 5 > $O/bench_pr_rmat_$sc.log 2>&1
+  timeout 600 python bench.py --full --mode pr --scale $sc --steps 16 --warmup 2 --cpu-seconds 5 > $O/bench_pr_rmat_$sc.log 2>&1
 done
 timeout 600 python tools/dropin_cost.py 20 4 2>&1 | grep -v amdgpu.ids > $O/dropin_cost.log
 timeout 600 python tools/dropin_cost.py 22 4 2>&1 | grep -v amdgpu.ids >> $O/dropin_cost.log
@@ -105,14 +105,14 @@ for r in rows:
         r = dict(r); r["Name"] = r["Name"][:120]; w.writerow(r)
 PY
 # the driver's own command line
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.log 2>&1
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.log 2>&1
 # auxiliary logs: operator path (reference loop, idempotent mode), direction-optimising sweep
 timeout 600 python tools/bfs_operator_bench.py 22 > $O/bfs_operator_s22.log 2>&1
 timeout 600 python tools/sssp_bench.py > $O/sssp_s22.log 2>&1
 timeout 600 python tools/pr_bench.py > $O/pr_s22.log 2>&1
 timeout 600 python tools/kcore_bench.py 20 > $O/kcore_s20.log 2>&1
 for a in 0.01 1 4 16 64 256 1000; do
-  timeout 300 python bench.py --mode do --alpha $a --steps 16 --warmup 2 --no-cpu-baseline 2>/dev/null | python3 -c "
+  timeout 300 python bench.py --full --mode do --alpha $a --steps 16 --warmup 2 --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 j = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('alpha=$a MTEPS %.2f ms_per_step %.4f (one call per source: %.4f) parity_vs_oracle %s' % (j['value'], j['ms_per_step'], j['per_call']['ms_per_step'], j.get('parity_vs_oracle')))" >> $O/dobfs_alpha_sweep.txt
 done

@@ -48,7 +48,7 @@ if "FETCH_SIZE" in pm and "WRITE_SIZE" in pm:
                "dispatches": pm["FETCH_SIZE"]["dispatches"],
                "fetch_bytes_corrected": 2.0 * fetch_raw, "write_bytes": write_raw, "hbm_bytes_per_launch": 2.0 * fetch_raw + write_raw,
                "correction": "2 x FETCH_SIZE + WRITE_SIZE (MI355X_MICROARCH.md, HBM: gfx950 FETCH_SIZE counts 128-B read requests as 64 B)",
-               "command": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-check; "
+               "command": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-check; "
                           "average over every dispatch of the kernel (all slots of all traversals, as bench.py's alg_bytes_per_launch)"}
     entries = [traffic]
     # the other modes' dominant kernels: the same two counters from passes over `bench.py --mode sssp` / `--mode pr`
@@ -75,7 +75,7 @@ if "FETCH_SIZE" in pm and "WRITE_SIZE" in pm:
             entries.append({"kernel": kname, "scale": scale, "mode": mode, "source_sha": bench.source_sha(), "dispatches": disp,
                             "fetch_bytes_corrected": 2.0 * fr, "write_bytes": wr, "hbm_bytes_per_launch": 2.0 * fr + wr,
                             "correction": traffic["correction"],
-                            "command": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --mode %s --steps 4 --warmup 1 --no-cpu-baseline --no-check; dispatches matching '%s'" % (mode, pat)})
+                            "command": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --full --mode %s --steps 4 --warmup 1 --no-cpu-baseline --no-check; dispatches matching '%s'" % (mode, pat)})
             print("pmc %s: HBM bytes per launch %.4g (read x2 %.4g, written %.4g)" % (mode, 2 * fr + wr, 2 * fr, wr))
     out_json = dict(traffic)
     out_json["entries"] = entries
