@@ -176,42 +176,7 @@ struct bfs_fused_enactor_t {
       layout.col_indices = g.d_layout_col_indices.data();
       layout.new_of_old = g.d_new_of_old.data();
       layout.old_of_new = g.d_old_of_new.data();
-      if (g.ub_units > 0) {
-        layout.ub_col = g.d_ub_col.size() ? g.d_ub_col.data() : nullptr;      // (round 6: gone when the 24-bit copy below exists)
-        layout.ub_col24 = g.d_ub_col24.size() ? g.d_ub_col24.data() : nullptr;
-        layout.ub_owner = g.d_ub_owner.data();
-        layout.ub_units = g.ub_units;
-        layout.ub_units_pad = g.ub_units_pad;
-        layout.ub_min_degree = g.ub_min_degree;
-      }
-      for (int i = 0; i < 4; ++i) layout.vs_v[i] = g.vs_v[i];
-      layout.vs_v9 = g.vs_v9;
-      layout.vs_edges = g.vs_edges; layout.vs_dummy = g.vs_dummy; layout.vs_long_min = g.vs_long_min;
-      if (g.cold_slices > 0) {
-        // (round 6: the 8-byte pairs are gone when every slice carries the packed words below -- cold_pairs8 says which)
-        layout.cold_pairs8 = g.d_cold_owner.size() != 0 && g.d_cold_dst.size() != 0;
-        layout.cold_owner = layout.cold_pairs8 ? g.d_cold_owner.data() : nullptr;
-        layout.cold_dst = layout.cold_pairs8 ? g.d_cold_dst.data() : nullptr;
-        layout.cold_slices = g.cold_slices;
-        if (g.d_cold_pk.size() && g.d_cold_cbase.size()) {
-          layout.cold_pk = g.d_cold_pk.data(); layout.cold_cbase = g.d_cold_cbase.data(); layout.cold_pk_mask = g.cold_pk_mask;
-          for (int i = 0; i <= mgx::BFS_COLD_MAX_SLICES; ++i) layout.cold_cb[i] = g.cold_cb[i];
-        }
-        static_assert(mgx::BFS_COLD_MAX_SLICES == 64, "graph_device_t::cold_* hold this many slices");
-        for (int i = 0; i < mgx::BFS_COLD_MAX_SLICES; ++i) layout.cold_lo[i] = g.cold_lo[i];
-        for (int i = 0; i <= mgx::BFS_COLD_MAX_SLICES; ++i) { layout.cold_off[i] = g.cold_off[i]; layout.colds_off[i] = g.colds_off[i]; layout.cold_wgs[i] = g.cold_wgs[i]; }
-        layout.colds_owner = g.colds_pairs > 0 ? g.d_colds_owner.data() : nullptr;
-        layout.colds_dst = g.colds_pairs > 0 ? g.d_colds_dst.data() : nullptr;
-        layout.cold_hot_n = g.cold_hot_n;
-        layout.cold_long_min = g.cold_long_min;
-        if (g.ubh_units > 0 && g.d_ubh_col24.size() && g.d_ubh_owner.size()) {
-          layout.ubh_col24 = g.d_ubh_col24.data(); layout.ubh_owner = g.d_ubh_owner.data();
-          layout.ubh_units = g.ubh_units; layout.ubh_units_pad = g.ubh_units_pad;
-        }
-      }
-      layout.cold_majority = g.cold_majority;
-      layout.cold_all = g.cold_all;
-      layout.cold_pairs_total = g.cold_all ? (unsigned long long)g.cold_pairs : 0ull;
+      layout.rows = &g.rows;
     }
     return layout;
   }

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../mgx/runtime.hpp"
+#include "../mgx/row_layout.hpp"
 #include "../mgx/src_shapes.hpp"
 
 // The reference's sources say `using namespace mgpu;` and `mgpu::fill<...>` for the memory
@@ -71,28 +72,15 @@ struct graph_device_t {
   mem_t<int> d_new_of_old;
   mem_t<int> d_old_of_new;
   bool has_layout = false;
-  // Unit blocks of the layout's long rows (mgx_layout.hip, mgx/bfs_fused_dense.hpp): rows of >= ub_min_degree edges
-  // padded to 64-entry units, owner[u] = the row of unit u.  Built with the layout; optional.
-  mem_t<int> d_ub_col;
-  // the unit blocks' entries once more, 24 bits each (3 bytes: 4 entries = 12 bytes, -1 = 0xFFFFFF), for graphs of at most
-  // 2^23 vertices: the fused BFS's unit-block body streams these -- a quarter less HBM traffic on the level that carries
-  // a traversal's edges (mgx/bfs_fused_dense.hpp).  Empty: not built (bigger graphs, MGX_BFS_PACK24=0).
-  mem_t<unsigned> d_ub_col24;
-  mem_t<int> d_ub_owner;
-  long long ub_units = 0, ub_units_pad = 0;
-  // The unit blocks of the fused BFS when the graph carries cold-edge lists: the same rows WITHOUT the entries that live in the
-  // lists (the unit-block body would read them only to skip them), 24 bits per entry whatever the graph's size -- what is left
-  // points into the LDS prefix.  Owners of their own (fewer units per row).  Empty: not built.
-  mem_t<unsigned> d_ubh_col24;
-  mem_t<int> d_ubh_owner;
-  long long ubh_units = 0, ubh_units_pad = 0;
-  int ub_min_degree = 0;
+  // What the fused BFS runs on, derived from the layout (mgx/row_layout.hpp): the unit blocks of its long rows (built with the layout;
+  // for graphs of at most 2^23 vertices their entries at 24 bits only -- MGX_BFS_PACK24=0 keeps the 32-bit ones), the degree classes
+  // of its short rows (only for a layout the library built itself: sorted by degree, eight ints of -1 behind its neighbour array), the
+  // cold-edge lists and the unit blocks without their entries (when the cold entries are a small share of the long rows').
+  mgx::row_layout_t rows;
   mem_t<unsigned long long> d_nr_pos;   // neighbour-reduce over a SUBSET frontier (mgx/nreduce.hpp): (epoch, frontier position) per layout vertex; allocated and zeroed at the first such call
   mem_t<float> d_ub_w;               // weights of the unit blocks' entries (fused SSSP's heavy iterations); built on first use
   mem_t<unsigned short> d_ub_w16;    // the same weights as IEEE halves, kept only when every one of them is exact that way (fused SSSP's sweep, 24-bit entries)
   bool ub_w_tried = false;
-  mem_t<unsigned char> d_ub_cnt;     // real entries of every unit (the rest is padding): what a reduction may count (mgx/nreduce.hpp)
-  mem_t<int> d_ub_first;             // n + 1: the units of layout row v are [ub_first[v], ub_first[v + 1])
   // What a traversal FROM vertex v starts with, by original id, on the host (mgx::bfs_src_shape_t, bfs_fused_run.hpp): the
   // source's own row and the level behind it -- its distinct neighbours other than itself that have entries: true edges,
   // rows below and from the long-row threshold.  The fused BFS sizes a traversal's launch sequence from it before the
@@ -113,29 +101,6 @@ struct graph_device_t {
   unsigned nrs_tier[3] = {0, 0, 0};  // k_nrs_fold: rows [0, t0) a workgroup each, [t0, t1) a wave, [t1, t2) eight lanes, the others a thread
   long long nrs_units = 0;
   bool nrs_tried = false;
-  // Degree classes of the layout's short rows (mgx/bfs_fused_vshort.hpp): only for a layout the library built itself
-  // (sorted by degree, eight ints of -1 behind its neighbour array).
-  unsigned vs_v[4] = {0, 0, 0, 0};
-  unsigned vs_v9 = 0;                // first layout vertex of degree < 9 (inside [vs_v[1], vs_v[2]]): the fused BFS walks degrees 5 .. 8 with two lanes per vertex
-  unsigned vs_edges = 0, vs_dummy = 0;
-  int vs_long_min = 0;
-  // Cold-edge lists of the long rows (mgx/bfs_fused_cold.hpp): the unit blocks' entries behind the LDS prefix as
-  // (owner, dst) pairs grouped by slice of the id range; built with the layout when they are a small share of the entries.
-  mem_t<int> d_cold_owner;
-  mem_t<int> d_cold_dst;
-  mem_t<unsigned> d_cold_pk;          // the long rows' pairs at four bytes each + the owners of their 64-chunks (mgx_layout.hip: mgx_cold_pack_device)
-  mem_t<unsigned> d_cold_cbase;
-  unsigned cold_cb[65] = {0};
-  unsigned long long cold_pk_mask = 0;
-  mem_t<int> d_colds_owner;           // the same for the SHORT rows' entries (the vertex-by-vertex body's cold entries)
-  mem_t<int> d_colds_dst;
-  long long cold_pairs = 0, colds_pairs = 0;
-  int cold_slices = 0;
-  unsigned cold_lo[64] = {0}, cold_off[65] = {0}, colds_off[65] = {0}, cold_wgs[65] = {0};     // (mgx::BFS_COLD_MAX_SLICES)
-  unsigned cold_hot_n = 0;
-  int cold_long_min = 0;
-  bool cold_majority = false;         // the long rows' entries behind the LDS prefix were too many for lists (more than a quarter of them): a FLAT graph
-  bool cold_all = false;             // (round 6) a FLAT graph: the lists hold EVERY entry of every row, slices from vertex 0 on (cold_hot_n == 0)
 
   graph_device_t() : num_nodes(0), num_edges(0) {}
 

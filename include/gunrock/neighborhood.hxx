@@ -57,9 +57,9 @@ int neighborhood_kernel(std::shared_ptr<Problem> problem, std::shared_ptr<fronti
   const bool subset = !full && frontier_size < (long long)graph.num_nodes && frontier_size * 8 >= (long long)graph.num_nodes && nr_subset_enabled();
   if constexpr (sizeof(Value) == 4)     // (the kernel keeps 40 000 4-byte values in the 160 KB of LDS: wider values take the general path)
   if (!has_output && is_pure_gather<Functor>::value && (full || subset) && frontier_size > 0 &&
-      graph.has_layout && (push || graph.csc_is_csr) && graph.ub_units > 0 && graph.ub_min_degree == graph.vs_long_min && graph.vs_long_min >= 17 && graph.vs_long_min <= 64 &&
-      graph.d_ub_cnt.size() && graph.d_ub_first.size() && graph.vs_dummy != 0 &&
-      context.scratch_bytes >= mgx::nr_scratch_bytes(graph.num_nodes, graph.ub_units_pad, sizeof(Value))) {
+      graph.has_layout && (push || graph.csc_is_csr) && graph.rows.ub.units > 0 && graph.rows.ub_min_degree == graph.rows.vs_long_min && graph.rows.vs_long_min >= 17 && graph.rows.vs_long_min <= 64 &&
+      graph.rows.ub.cnt.size() && graph.rows.ub.first.size() && graph.rows.vs_dummy != 0 &&
+      context.scratch_bytes >= mgx::nr_scratch_bytes(graph.num_nodes, graph.rows.ub.units_pad, sizeof(Value))) {
     // the check (inside the first kernel) and the work go out back to back: the kernels behind it look at its verdict themselves (a device
     // word that holds the epoch of the last call whose frontier was NOT the iota); one host wait, behind everything
     context.mailbox[8] = 1;
@@ -71,13 +71,13 @@ int neighborhood_kernel(std::shared_ptr<Problem> problem, std::shared_ptr<fronti
       L.row_offsets = (const mgx::u32*)graph.d_layout_row_offsets.data();
       L.col_indices = graph.d_layout_col_indices.data();
       L.old_of_new = graph.d_old_of_new.data();
-      L.ub_col = graph.d_ub_col.size() ? graph.d_ub_col.data() : nullptr;      // (round 6: gone when the layout carries the 24-bit copy)
-      L.ub_col24 = graph.d_ub_col24.size() ? graph.d_ub_col24.data() : nullptr;     // (the 24-bit copy whenever the layout has one: 0.492 -> 0.477 ms in round 4)
-      L.ub_cnt = graph.d_ub_cnt.data();
-      L.ub_first = graph.d_ub_first.data();
-      L.ub_units = (mgx::u32)graph.ub_units; L.ub_units_pad = (mgx::u32)graph.ub_units_pad;
-      for (int i = 0; i < 4; ++i) L.vs_v[i] = graph.vs_v[i];
-      L.vs_dummy = graph.vs_dummy;
+      L.ub_col = graph.rows.ub.col.size() ? graph.rows.ub.col.data() : nullptr;      // (round 6: gone when the layout carries the 24-bit copy)
+      L.ub_col24 = graph.rows.ub.col24.size() ? graph.rows.ub.col24.data() : nullptr;     // (the 24-bit copy whenever the layout has one: 0.492 -> 0.477 ms in round 4)
+      L.ub_cnt = graph.rows.ub.cnt.data();
+      L.ub_first = graph.rows.ub.first.data();
+      L.ub_units = (mgx::u32)graph.rows.ub.units; L.ub_units_pad = (mgx::u32)graph.rows.ub.units_pad;
+      for (int i = 0; i < 4; ++i) L.vs_v[i] = graph.rows.vs_v[i];
+      L.vs_dummy = graph.rows.vs_dummy;
       L.big_rows = graph.nr_big_rows;
       L.n = graph.num_nodes;
       {
@@ -88,7 +88,7 @@ int neighborhood_kernel(std::shared_ptr<Problem> problem, std::shared_ptr<fronti
         // the long rows by slice of their destinations (MGX_NR_SLICED=0: the unit blocks, as before round 5), when the graph carries
         // them and the scratch arena holds a partial per mini-unit
         static const bool sliced = [] { const char* e = mgx::env("MGX_NR_SLICED"); return !e || std::atoi(e) != 0; }();
-        if (sliced && graph.nrs_units > 0 && graph.nrs_slices > 0 && graph.nrs_rows == graph.vs_v[0] && graph.d_nrs_mu.size() && graph.d_nrs_off.size() &&
+        if (sliced && graph.nrs_units > 0 && graph.nrs_slices > 0 && graph.nrs_rows == graph.rows.vs_v[0] && graph.d_nrs_mu.size() && graph.d_nrs_off.size() &&
             context.scratch_bytes >= mgx::nr_scratch_bytes(graph.num_nodes, graph.nrs_units, sizeof(Value))) {
           L.nrs_mu = (const uint4*)graph.d_nrs_mu.data();
           L.nrs_off = graph.d_nrs_off.data();

@@ -419,15 +419,6 @@ __global__ void k_d2_unfreeze(bfs_ctrl_t* c) {
   if (blockIdx.x == 0 && threadIdx.x == 0) c->d2_frozen_level = -1;
 }
 
-// unit owners as the builder numbers them (local rows; n_local for padding units) -> global ids (n_global for padding)
-__global__ __launch_bounds__(BLOCK) void k_d2_owner_global(int* __restrict__ owner, long long units_pad, int ranks, int rank, int n_local,
-                                                           int n_global) {
-  const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= units_pad) return;
-  const int o = owner[i];
-  owner[i] = (o >= n_local) ? n_global : o * ranks + rank;
-}
-
 // rows of at least min_deg entries (a prefix of the rank's rows: they come by descending degree) and whether every row is
 // sorted by neighbour id (the cold-list builder finds a row's cold tail by bisection): *long_rows <- the count, *sorted <- 0 if not
 __global__ __launch_bounds__(BLOCK) void k_d2_row_facts(const int* __restrict__ ro, const int* __restrict__ ci, int n_local, int min_deg,
@@ -499,34 +490,18 @@ struct d2_state_t {
   int sparse_push = 1;                // levels of at most list_cap edges append to the list themselves (MGX_DIST_SPARSE_PUSH=0: every level sweeps)
   u64* host_flag = nullptr;           // pinned: what k_d2_lists_apply tells the host
   u64 flag_seq = 0;
-  // unit blocks of the rank's long rows (mgx_layout.hip; owners in GLOBAL ids, padding units owned by vertex n_global):
-  // built on request (mgx_dbfs2_build_units), owned here
-  int* ub_col = nullptr;
-  int* ub_owner = nullptr;
+  // The rank's row layout (mgx/row_layout.hpp; built on request by mgx_dbfs2_build_units, owners in GLOBAL ids, padding units owned
+  // by vertex n_global): the unit blocks of its long rows -- or, when it has cold-edge lists, the blocks of the rows' HOT entries alone,
+  // at 32 and 24 bits (the full blocks are gone then) --, the degree classes over its LOCAL rows, the cold-edge lists
+  row_layout_t rows;
+  const unit_blocks_t& blocks() const { return rows.ubh.units > 0 ? rows.ubh : rows.ub; }
   // the short rows vertex by vertex (bfs_fused_vshort.hpp; mgx_dbfs2_build_units sets it up when the rank's rows come by
-  // non-increasing degree): class boundaries over the LOCAL rows, the edges of those rows, a copy of col_indices with readable
-  // entries behind it, the frontier over the local rows (written by k_bfs_build2)
-  u32 vs_v[4] = {0, 0, 0, 0};
-  u32 vs_v9 = 0, vs_edges = 0, vs_div = 0;
+  // non-increasing degree): a copy of col_indices with readable entries behind it, the frontier over the local rows (written by k_bfs_build2)
+  u32 vs_div = 0;
   mem_t<int> col_pad;
   mem_t<u32> front_local;
-  mem_t<u32> ub_col24;                // the same, 24 bits per entry: only when the blocks hold the rows' HOT entries alone (the others are in the cold-edge lists)
-  long long ub_units = 0, ub_units_pad = 0;
   u32 dense_div = 4;
-  // cold-edge lists of those rows (mgx_layout.hip: mgx_cold_build_device; owners global): pairs by slice of the destination,
-  // the slices that hold any, the cold workgroups of a push launch per slice, their flush bitmaps
-  int* cold_owner = nullptr;
-  int* cold_dst = nullptr;
-  u32* cold_pk = nullptr;             // the same pairs at four bytes each (mgx_layout.hip: mgx_cold_pack_device), their 64-chunks' owners
-  u32* cold_cbase = nullptr;
-  u32 cold_cb[BFS_COLD_MAX_SLICES + 1] = {};
-  u64 cold_pk_mask = 0;
-  long long cold_pairs = 0;
-  int cold_slices = 0;
-  u32 cold_lo[BFS_COLD_MAX_SLICES] = {};
-  u32 cold_off[BFS_COLD_MAX_SLICES + 1] = {};
-  u32 cold_wgs[BFS_COLD_MAX_SLICES + 1] = {};
-  mem_t<u32> cold_flush;
+  mem_t<u32> cold_flush;              // the flush bitmaps of the cold workgroups of a push launch
   int cold_reduce = 1;                // k_d2_cold_reduce in front of the sweep (MGX_DIST_COLD_REDUCE)
   int fused_merge = 1;                // OR-merge inside the queue build (MGX_DIST_FUSED_MERGE)
   int build_list = 0;                 // the list-based queue build (MGX_DIST_BUILD_LIST)
@@ -541,21 +516,22 @@ struct d2_state_t {
   static constexpr long long D2_DEFER_MIN_ENTRIES = 48ll << 20;
   d2_cold_view_t cold_view() const {
     d2_cold_view_t v;
-    if (!cold_dst || cold_slices <= 0 || !cold_flush.size()) return v;
-    v.flush = cold_flush.data(); v.slices = cold_slices;
+    const row_layout_t& R = rows;
+    if (!R.cold_dst.data() || R.cold_slices <= 0 || !cold_flush.size()) return v;
+    v.flush = cold_flush.data(); v.slices = R.cold_slices;
     // (the table covers 128 slices behind the first one in use -- 83 M vertices; a bigger range keeps the search over lo[])
     v.slice_n = (u32)BFS_COLD_WORDS * 32u;
     bool table = true;
     for (int k = 0; k < 128; ++k) v.qof[k] = 255;
-    for (int q = 0; q < cold_slices; ++q) {
-      const u32 k = (cold_lo[q] - cold_lo[0]) / v.slice_n;
-      if (k >= 128u || (cold_lo[q] - cold_lo[0]) % v.slice_n) { table = false; break; }
+    for (int q = 0; q < R.cold_slices; ++q) {
+      const u32 k = (R.cold_lo[q] - R.cold_lo[0]) / v.slice_n;
+      if (k >= 128u || (R.cold_lo[q] - R.cold_lo[0]) % v.slice_n) { table = false; break; }
       v.qof[k] = (unsigned char)q;
     }
     if (!table) v.slice_n = 0;
     v.reduced = cold_reduce ? 1 : 0;
-    for (int i = 0; i < BFS_COLD_MAX_SLICES; ++i) v.lo[i] = cold_lo[i];
-    for (int i = 0; i <= BFS_COLD_MAX_SLICES; ++i) v.wgs[i] = cold_wgs[i];
+    for (int i = 0; i < BFS_COLD_MAX_SLICES; ++i) v.lo[i] = R.cold_lo[i];
+    for (int i = 0; i <= BFS_COLD_MAX_SLICES; ++i) v.wgs[i] = R.cold_wgs[i];
     return v;
   }
 
@@ -589,12 +565,6 @@ struct d2_state_t {
   }
   ~d2_state_t() {
     if (host_flag) (void)hipHostFree(host_flag);
-    if (ub_col) (void)hipFree(ub_col);
-    if (ub_owner) (void)hipFree(ub_owner);
-    if (cold_owner) (void)hipFree(cold_owner);
-    if (cold_dst) (void)hipFree(cold_dst);
-    if (cold_pk) (void)hipFree(cold_pk);
-    if (cold_cbase) (void)hipFree(cold_cbase);
   }
   d2_state_t() {}
   d2_state_t(const d2_state_t&) = delete;
@@ -616,7 +586,8 @@ struct d2_state_t {
     a.visited = fs->visited.data();
     a.mark = fs->mark.data();
     // (with unit blocks: the level's merged discoveries ARE the frontier bitmap their owners are looked up in)
-    a.frontier_bits = ub_col ? merged.data() : fs->frontier_bits.data();
+    const unit_blocks_t& ub = blocks();
+    a.frontier_bits = ub.col.data() ? merged.data() : fs->frontier_bits.data();
     a.in_offsets = nullptr; a.in_indices = nullptr;
     for (int i = 0; i < 2; ++i) {
       a.fr_row[i] = fs->fr_row[i].data(); a.fr_off[i] = fs->fr_off[i].data();
@@ -629,22 +600,23 @@ struct d2_state_t {
     a.n = n_global;
     a.mode = 0; a.alpha = 0.f;
     a.count_marks = 0;
-    a.ub_col = ub_col; a.ub_col24 = ub_col24.size() ? ub_col24.data() : nullptr; a.ub_owner = ub_owner; a.ub_units = (u32)ub_units; a.ub_units_pad = (u32)ub_units_pad; a.dense_div = ub_col ? dense_div : 0u;
+    a.ub_col = ub.col.data(); a.ub_col24 = ub.col24.data(); a.ub_owner = ub.owner.data(); a.ub_units = (u32)ub.units; a.ub_units_pad = (u32)ub.units_pad; a.dense_div = ub.col.data() ? dense_div : 0u;
     {
       const bool vs = vs_div != 0u && col_pad.size() && front_local.size() && !build_list;      // (the list-based build writes no local frontier)
-      for (int i = 0; i < 4; ++i) a.vs_v[i] = vs ? vs_v[i] : 0u;
-      a.vs_v9 = vs ? vs_v9 : 0u; a.vs_edges = vs ? vs_edges : 0u; a.vs_div = vs ? vs_div : 0u; a.vs_dummy = 0;     // (entry 0: readable, and a lane without entries looks at none of the four)
+      for (int i = 0; i < 4; ++i) a.vs_v[i] = vs ? rows.vs_v[i] : 0u;
+      a.vs_v9 = vs ? rows.vs_v9 : 0u; a.vs_edges = vs ? rows.vs_edges : 0u; a.vs_div = vs ? vs_div : 0u; a.vs_dummy = 0;     // (entry 0: readable, and a lane without entries looks at none of the four)
       a.vs_col = vs ? col_pad.data() : nullptr; a.d2_front = vs ? const_cast<u32*>(front_local.data()) : nullptr;
     }
     a.lazy_div = 0; a.slot_marks = const_cast<u32*>(slot_marks.data()); a.merged_pull = 0; a.lazy_pull = 0; a.chain_big_edges = 0; a.defer_reach_mul = 1; a.defer_reach_div = 1;
-    const bool cold = cold_dst != nullptr && ub_col != nullptr && cold_slices > 0 && cold_flush.size() > 0;
-    a.cold_owner = cold ? cold_owner : nullptr; a.cold_dst = cold ? cold_dst : nullptr; a.cold_slices = cold ? cold_slices : 0;
+    const row_layout_t& R = rows;
+    const bool cold = R.cold_dst.data() != nullptr && ub.col.data() != nullptr && R.cold_slices > 0 && cold_flush.size() > 0;
+    a.cold_owner = cold ? R.cold_owner.data() : nullptr; a.cold_dst = cold ? R.cold_dst.data() : nullptr; a.cold_slices = cold ? R.cold_slices : 0;
     a.cold_flush = cold ? const_cast<u32*>(cold_flush.data()) : nullptr;
-    const bool pk = cold && cold_pk && cold_cbase;
-    a.cold_pk = pk ? cold_pk : nullptr; a.cold_cbase = pk ? cold_cbase : nullptr; a.cold_pk_mask = pk ? cold_pk_mask : 0ull; a.cold_ranks = (u32)ranks;
-    for (int i = 0; i <= BFS_COLD_MAX_SLICES; ++i) a.cold_cb[i] = pk ? cold_cb[i] : 0u;
-    for (int i = 0; i < BFS_COLD_MAX_SLICES; ++i) a.cold_lo[i] = cold ? cold_lo[i] : 0u;
-    for (int i = 0; i <= BFS_COLD_MAX_SLICES; ++i) { a.cold_off[i] = cold ? cold_off[i] : 0u; a.cold_wgs[i] = cold ? cold_wgs[i] : 0u; }
+    const bool pk = cold && R.cold_pk.data() && R.cold_cbase.data();
+    a.cold_pk = pk ? R.cold_pk.data() : nullptr; a.cold_cbase = pk ? R.cold_cbase.data() : nullptr; a.cold_pk_mask = pk ? R.cold_pk_mask : 0ull; a.cold_ranks = (u32)ranks;
+    for (int i = 0; i <= BFS_COLD_MAX_SLICES; ++i) a.cold_cb[i] = pk ? R.cold_cb[i] : 0u;
+    for (int i = 0; i < BFS_COLD_MAX_SLICES; ++i) a.cold_lo[i] = cold ? R.cold_lo[i] : 0u;
+    for (int i = 0; i <= BFS_COLD_MAX_SLICES; ++i) { a.cold_off[i] = cold ? R.cold_off[i] : 0u; a.cold_wgs[i] = cold ? R.cold_wgs[i] : 0u; }
     // deferred hot marks: while the ranks together have reached fewer vertices than the deferred range holds (reached counts this
     // rank's: x ranks); k_d2_cold_reduce + k_d2_newbits read the bitmaps
     const bool defer = defer_buf.size() != 0 && cold_reduce && defer_pays;

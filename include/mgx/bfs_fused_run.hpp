@@ -21,55 +21,25 @@
 #include "bfs_fused_vshort.hpp"
 #include "bfs_fused_sparse.hpp"
 #include "bfs_fused_wave.hpp"
+#include "row_layout.hpp"
 
 namespace mgx {
 
 // layout (optional): a hub-first relabelled copy of the CSR plus the two id maps; labels stay in the
-// original id space either way.  Unit blocks (optional, of the same CSR): see bfs_fused_dense.hpp.
+// original id space either way.  What the fused BFS runs on, derived from that CSR (unit blocks, degree classes, cold-edge
+// lists): its row layout (mgx/row_layout.hpp), owned by the graph.
 struct bfs_layout_t {
   const int* row_offsets = nullptr;
   const int* col_indices = nullptr;
   const int* new_of_old = nullptr;
   const int* old_of_new = nullptr;
-  const int* ub_col = nullptr;
-  const unsigned* ub_col24 = nullptr;   // the same entries, 24 bits each (graphs of at most 2^23 vertices; NULL: none)
-  const int* ub_owner = nullptr;
-  long long ub_units = 0, ub_units_pad = 0;
-  int ub_min_degree = 0;            // the rows the unit blocks hold: degree >= this (must equal the long-row threshold)
-  // the same rows without the entries of the cold-edge lists, 24 bits per entry (any graph size), their own owners: read instead of the
-  // blocks above by a run that takes the cold-edge pass on every unit-block level (NULL: none)
-  const unsigned* ubh_col24 = nullptr;
-  const int* ubh_owner = nullptr;
-  long long ubh_units = 0, ubh_units_pad = 0;
-  // short rows vertex by vertex (bfs_fused_vshort.hpp): class boundaries of the degree-sorted CSR, edges of the range,
-  // the long-row threshold they were computed for, index of four -1 behind col_indices (0: not available)
-  unsigned vs_v[4] = {0, 0, 0, 0};
-  unsigned vs_v9 = 0;               // first vertex of degree < 9 (0: unknown -- degrees 5 .. 16 are one class)
-  unsigned vs_edges = 0, vs_dummy = 0;
-  int vs_long_min = 0;
-  // cold-edge lists of the long rows (bfs_fused_cold.hpp): pairs grouped by slice; hot_n / long_min they were cut for
-  const int* cold_owner = nullptr;
-  const int* cold_dst = nullptr;
-  bool cold_pairs8 = false;             // the two arrays above exist (round 6: a layout whose slices are ALL packed drops them)
-  const unsigned* cold_pk = nullptr;    // the same pairs, four bytes each (bfs_fused_args_t::cold_pk); NULL: none
-  const unsigned* cold_cbase = nullptr;
-  unsigned cold_cb[BFS_COLD_MAX_SLICES + 1] = {0};
-  unsigned long long cold_pk_mask = 0;
-  const int* colds_owner = nullptr;   // the short rows' cold entries (graphs of more than 2^23 vertices)
-  const int* colds_dst = nullptr;
-  int cold_slices = 0;
-  unsigned cold_lo[BFS_COLD_MAX_SLICES] = {0}, cold_off[BFS_COLD_MAX_SLICES + 1] = {0}, colds_off[BFS_COLD_MAX_SLICES + 1] = {0},
-           cold_wgs[BFS_COLD_MAX_SLICES + 1] = {0};
-  unsigned cold_hot_n = 0;
-  int cold_long_min = 0;
-  bool cold_majority = false;         // more than a quarter of the long rows' entries point behind the LDS prefix (no lists were built): a flat graph
-  bool cold_all = false;              // (round 6) a flat graph WITH lists: every entry of every row, slices from vertex 0 on (cold_hot_n == 0); cold_pairs_total of them
-  unsigned long long cold_pairs_total = 0;
+  const row_layout_t* rows = nullptr;   // (NULL: none)
   // HOST table, 4 words per SOURCE OF THE CALL (entry i belongs to the i-th source handed to bfs_fused_run / _run_many; round 6: resolved
   // on demand, mgx/src_shapes.hpp): what a traversal from it starts with
   const unsigned* src_shapes = nullptr;
   int src_shapes_long_min = 0;
 };
+static_assert(row_layout_t::MAX_SLICES == BFS_COLD_MAX_SLICES, "row_layout_t's slice tables hold this many slices");
 
 // A traversal's first levels, known before anything is enqueued (bfs_layout_t::src_shapes): level 0 is the source's row,
 // level 1 its distinct neighbours.  The launch sequence of a traversal is [init][chain][M] slots ... [M][chain]; whether
@@ -372,6 +342,8 @@ inline bfs_launch_plan_t bfs_fused_plan(bfs_fused_state_t& st, const int* row_of
   bfs_fused_args_t& a = plan.a;
   const bfs_run_opts_t& opt = st.opts;        // (environment switches: read once, when the handle's state was made)
   const bool relabelled = layout && layout->row_offsets;
+  static const row_layout_t no_rows;
+  const row_layout_t& R = layout && layout->rows ? *layout->rows : no_rows;
   a.row_offsets = (const u32*)(relabelled ? layout->row_offsets : row_offsets);
   a.col_indices = relabelled ? layout->col_indices : col_indices;
   a.old_of_new = relabelled ? layout->old_of_new : nullptr;
@@ -400,8 +372,8 @@ inline bfs_launch_plan_t bfs_fused_plan(bfs_fused_state_t& st, const int* row_of
   a.count_marks = (st.count_marks || st.time_kernels == 1) ? 1 : 0;
   // unit blocks: only for the CSR they were built from, with the long-row threshold they were built for
   // (the entries at 32 bits, or their 24-bit copy when the run may read it: a layout that carries the copy has dropped the former)
-  const bool units_avail = relabelled && (layout->ub_col || (layout->ub_col24 && st.opts.pack24)) && layout->ub_owner && layout->ub_units > 0 &&
-                           layout->ub_min_degree == st.long_min && st.long_min > 0 && !lab_flags;
+  const bool units_avail = relabelled && (R.ub.col.data() || (R.ub.col24.data() && st.opts.pack24)) && R.ub.owner.data() && R.ub.units > 0 &&
+                           R.ub_min_degree == st.long_min && st.long_min > 0 && !lab_flags;
   // Probing the bitmap word of cold neighbours (instead of marking them untested) pays on big graphs WITHOUT the unit
   // blocks -- the partitioned ranks, a caller-made layout.  With them the unit-block body, the cold-edge pass and the
   // lazy builds win at every size measured: RMAT-23 391 against 272 GTEPS, RMAT-24 386 / 253, RMAT-25 187 / 179.
@@ -411,51 +383,52 @@ inline bfs_launch_plan_t bfs_fused_plan(bfs_fused_state_t& st, const int* row_of
   // L2s) wins there: 1.35 against 2.02 ms per traversal.
   // (the layout says so: it counted the long rows' cold entries and found more than a quarter of them cold.  NOT "no lists": RMAT-20
   //  has none either -- a handful of cold entries -- and lost 19 % to this rule while it read "no lists": 0.1915 -> 0.2272 ms)
-  const bool flat = units_avail && layout->cold_majority;
+  const bool flat = units_avail && R.cold_majority;
   const bool coldt = opt.cold_test >= 0 ? opt.cold_test != 0 : ((bfs_cold_test(a.n, -1) && !units_avail) || flat);
   const bool units = units_avail && !coldt;
-  a.ub_col = units ? layout->ub_col : nullptr;
-  a.ub_col24 = (units && st.opts.pack24) ? layout->ub_col24 : nullptr;
-  a.ub_owner = units ? layout->ub_owner : nullptr;
-  a.ub_units = units ? (u32)layout->ub_units : 0u;
-  a.ub_units_pad = units ? (u32)layout->ub_units_pad : 0u;
+  a.ub_col = units ? R.ub.col.data() : nullptr;
+  a.ub_col24 = (units && st.opts.pack24) ? R.ub.col24.data() : nullptr;
+  a.ub_owner = units ? R.ub.owner.data() : nullptr;
+  a.ub_units = units ? (u32)R.ub.units : 0u;
+  a.ub_units_pad = units ? (u32)R.ub.units_pad : 0u;
   // (with the 24-bit copy a unit costs three quarters of the bytes: the unit-block body wins from an eighth of the units on
   //  -- RMAT-22, per call: 1/2 0.3282, 1/4 0.3262, 1/8 0.3215, 1/16 0.3250 ms; with 32-bit entries 1/2 was best)
   // k_bfs_build2 reads a thread's 17 row offsets and 16 layout ids with 16-byte loads: borrowed arrays must be aligned
   const bool build2_ok = ((uintptr_t)a.row_offsets % 16 == 0) && ((uintptr_t)a.old_of_new % 16 == 0);
   // cold-edge lists (bfs_fused_cold.hpp): with the unit blocks they were cut from, the prefix they were cut behind, and a
   // queue build that knows their bitmaps
-  // (the pairs at 8 bytes, or every slice packed at 4 and a run that may read those)
-  const bool cold_all_packed = layout && layout->cold_pk && layout->cold_cbase && layout->cold_slices > 0 &&
-                               (layout->cold_pk_mask & (layout->cold_slices >= 64 ? ~0ull : ((1ull << layout->cold_slices) - 1ull))) ==
-                                   (layout->cold_slices >= 64 ? ~0ull : ((1ull << layout->cold_slices) - 1ull));
-  const bool cold_pairs_ok = layout && ((layout->cold_pairs8 && layout->cold_dst) || (cold_all_packed && opt.cold_pack));
-  const bool flat_lists = layout && layout->cold_all && layout->cold_hot_n == 0u && cold_all_packed && opt.cold_pack && layout->cold_pairs_total > 0;
-  const bool cold_lists = units && cold_pairs_ok && layout->cold_slices > 0 &&
-                          (layout->cold_hot_n == (unsigned)(BFS_DENSE_HOTW * 32) || flat_lists) && (!layout->cold_all || flat_lists) &&
-                          layout->cold_long_min == st.long_min && build2_ok && !opt.build_list && opt.cold != 0 &&
+  // (the pairs at 8 bytes -- round 6: gone when every slice is packed -- or every slice packed at 4 and a run that may read those)
+  const bool cold_pairs8 = R.cold_owner.size() != 0 && R.cold_dst.size() != 0;
+  const bool cold_all_packed = R.cold_pk.data() && R.cold_cbase.data() && R.cold_slices > 0 &&
+                               (R.cold_pk_mask & (R.cold_slices >= 64 ? ~0ull : ((1ull << R.cold_slices) - 1ull))) ==
+                                   (R.cold_slices >= 64 ? ~0ull : ((1ull << R.cold_slices) - 1ull));
+  const bool cold_pairs_ok = cold_pairs8 || (cold_all_packed && opt.cold_pack);
+  const bool flat_lists = R.cold_all && R.cold_hot_n == 0u && cold_all_packed && opt.cold_pack && R.cold_pairs > 0;
+  const bool cold_lists = units && cold_pairs_ok && R.cold_slices > 0 &&
+                          (R.cold_hot_n == (unsigned)(BFS_DENSE_HOTW * 32) || flat_lists) && (!R.cold_all || flat_lists) &&
+                          R.cold_long_min == st.long_min && build2_ok && !opt.build_list && opt.cold != 0 &&
                           !MGX_LAB_GET(opt, dense_diag, 0);
   // ... and then the unit blocks WITHOUT the lists' entries (every level that reads unit blocks runs the cold-edge pass: the body
   // reads those entries only to skip them), at 24 bits whatever the graph's size.  Round 5, as the partitioned ranks have had
   // them since round 4 (mgx_capi.hip): see the note at the layout's builder for what they are worth.
-  const bool hot_units = cold_lists && st.opts.pack24 && st.opts.hot_units && layout->ubh_col24 && layout->ubh_owner && layout->ubh_units > 0 &&
+  const bool hot_units = cold_lists && st.opts.pack24 && st.opts.hot_units && R.ubh.col24.data() && R.ubh.owner.data() && R.ubh.units > 0 &&
                          (opt.dense < 0 || opt.dense > 0);
   if (hot_units) {
-    a.ub_col24 = layout->ubh_col24; a.ub_owner = layout->ubh_owner;     // (a.ub_col: the full blocks' -- not read by the 24-bit body)
-    a.ub_units = (u32)layout->ubh_units; a.ub_units_pad = (u32)layout->ubh_units_pad;
+    a.ub_col24 = R.ubh.col24.data(); a.ub_owner = R.ubh.owner.data();     // (a.ub_col: the full blocks' -- not read by the 24-bit body)
+    a.ub_units = (u32)R.ubh.units; a.ub_units_pad = (u32)R.ubh.units_pad;
   }
   a.ub_hot_only = hot_units ? 1u : 0u;
-  a.ubf_col24 = hot_units ? layout->ub_col24 : nullptr; a.ubf_owner = hot_units ? layout->ub_owner : nullptr;
-  a.ubf_units_pad = hot_units ? (u32)layout->ub_units_pad : 0u;
-  const bool packed = units && st.opts.pack24 && (layout->ub_col24 != nullptr || hot_units);
+  a.ubf_col24 = hot_units ? R.ub.col24.data() : nullptr; a.ubf_owner = hot_units ? R.ub.owner.data() : nullptr;
+  a.ubf_units_pad = hot_units ? (u32)R.ub.units_pad : 0u;
+  const bool packed = units && st.opts.pack24 && (R.ub.col24.data() != nullptr || hot_units);
   a.dense_div = !units ? 0u : (opt.dense >= 0 ? (u32)opt.dense : (packed ? 8u : st.dense_div));
   // short rows vertex by vertex: the layout's own degree-sorted CSR with its padding, the threshold it was cut for
-  const bool vs = relabelled && layout->vs_dummy != 0 && layout->vs_long_min == st.long_min && st.long_min > 0 && !coldt && !lab_flags &&
-                  layout->vs_edges > 0;
-  for (int i = 0; i < 4; ++i) a.vs_v[i] = vs ? layout->vs_v[i] : 0u;
-  a.vs_v9 = (vs && layout->vs_v9 >= layout->vs_v[1] && layout->vs_v9 <= layout->vs_v[2]) ? layout->vs_v9 : (vs ? layout->vs_v[2] : 0u);   // (unknown: nobody in the two-lane class)
-  a.vs_edges = vs ? layout->vs_edges : 0u;
-  a.vs_dummy = vs ? layout->vs_dummy : 0u;
+  const bool vs = relabelled && R.vs_dummy != 0 && R.vs_long_min == st.long_min && st.long_min > 0 && !coldt && !lab_flags &&
+                  R.vs_edges > 0;
+  for (int i = 0; i < 4; ++i) a.vs_v[i] = vs ? R.vs_v[i] : 0u;
+  a.vs_v9 = (vs && R.vs_v9 >= R.vs_v[1] && R.vs_v9 <= R.vs_v[2]) ? R.vs_v9 : (vs ? R.vs_v[2] : 0u);   // (unknown: nobody in the two-lane class)
+  a.vs_edges = vs ? R.vs_edges : 0u;
+  a.vs_dummy = vs ? R.vs_dummy : 0u;
   a.vs_div = !vs ? 0u : (opt.vshort >= 0 ? (u32)opt.vshort : st.vshort_div);
 #ifdef MGX_LAB
   a.dense_diag = opt.dense_diag;
@@ -483,23 +456,23 @@ inline bfs_launch_plan_t bfs_fused_plan(bfs_fused_state_t& st, const int* row_of
   const bool cold = cold_lists && a.dense_div;
   // (cold_dst != NULL is what "this run has cold-edge lists" reads as everywhere: a layout without the 8-byte pairs -- every slice
   //  packed, bfs_cold_body never dereferences them -- hands the packed words' address instead)
-  a.cold_owner = cold ? (layout->cold_pairs8 ? layout->cold_owner : (const int*)layout->cold_pk) : nullptr;
-  a.cold_dst = cold ? (layout->cold_pairs8 ? layout->cold_dst : (const int*)layout->cold_pk) : nullptr;
-  a.cold_slices = cold ? layout->cold_slices : 0;
+  a.cold_owner = cold ? (cold_pairs8 ? R.cold_owner.data() : (const int*)R.cold_pk.data()) : nullptr;
+  a.cold_dst = cold ? (cold_pairs8 ? R.cold_dst.data() : (const int*)R.cold_pk.data()) : nullptr;
+  a.cold_slices = cold ? R.cold_slices : 0;
   a.cold_all = (cold && flat_lists) ? 1u : 0u;
-  a.cold_all_pairs = a.cold_all ? layout->cold_pairs_total : 0ull;
-  const bool cold_pk = cold && layout->cold_pk && layout->cold_cbase && opt.cold_pack;
-  a.cold_pk = cold_pk ? layout->cold_pk : nullptr; a.cold_cbase = cold_pk ? layout->cold_cbase : nullptr;
-  a.cold_pk_mask = cold_pk ? layout->cold_pk_mask : 0ull; a.cold_ranks = 1;
-  for (int i = 0; i <= BFS_COLD_MAX_SLICES; ++i) a.cold_cb[i] = cold_pk ? layout->cold_cb[i] : 0u;
-  for (int i = 0; i < BFS_COLD_MAX_SLICES; ++i) a.cold_lo[i] = cold ? layout->cold_lo[i] : 0u;
-  for (int i = 0; i <= BFS_COLD_MAX_SLICES; ++i) { a.cold_off[i] = cold ? layout->cold_off[i] : 0u; a.cold_wgs[i] = cold ? layout->cold_wgs[i] : 0u; }
+  a.cold_all_pairs = a.cold_all ? (unsigned long long)R.cold_pairs : 0ull;
+  const bool cold_pk = cold && R.cold_pk.data() && R.cold_cbase.data() && opt.cold_pack;
+  a.cold_pk = cold_pk ? R.cold_pk.data() : nullptr; a.cold_cbase = cold_pk ? R.cold_cbase.data() : nullptr;
+  a.cold_pk_mask = cold_pk ? R.cold_pk_mask : 0ull; a.cold_ranks = 1;
+  for (int i = 0; i <= BFS_COLD_MAX_SLICES; ++i) a.cold_cb[i] = cold_pk ? R.cold_cb[i] : 0u;
+  for (int i = 0; i < BFS_COLD_MAX_SLICES; ++i) a.cold_lo[i] = cold ? R.cold_lo[i] : 0u;
+  for (int i = 0; i <= BFS_COLD_MAX_SLICES; ++i) { a.cold_off[i] = cold ? R.cold_off[i] : 0u; a.cold_wgs[i] = cold ? R.cold_wgs[i] : 0u; }
   // ... and of the short rows, for the levels that walk them vertex by vertex
-  const bool colds = cold && a.vs_div && layout->colds_dst && opt.cold != 2;
-  a.colds_owner = colds ? layout->colds_owner : nullptr;
-  a.colds_dst = colds ? layout->colds_dst : nullptr;
-  for (int i = 0; i <= BFS_COLD_MAX_SLICES; ++i) a.colds_off[i] = colds ? layout->colds_off[i] : 0u;
-  const size_t cold_words = cold ? (size_t)layout->cold_wgs[layout->cold_slices] * BFS_COLD_WORDS : 0;
+  const bool colds = cold && a.vs_div && R.colds_pairs > 0 && R.colds_dst.data() && opt.cold != 2;
+  a.colds_owner = colds ? R.colds_owner.data() : nullptr;
+  a.colds_dst = colds ? R.colds_dst.data() : nullptr;
+  for (int i = 0; i <= BFS_COLD_MAX_SLICES; ++i) a.colds_off[i] = colds ? R.colds_off[i] : 0u;
+  const size_t cold_words = cold ? (size_t)R.cold_wgs[R.cold_slices] * BFS_COLD_WORDS : 0;
   if (cold && st.cold_flush.size() < cold_words) { ctx.synchronize(); st.cold_flush = mem_t<u32>(cold_words, ctx); }
   a.cold_flush = cold ? st.cold_flush.data() : nullptr;
   // lazy queues (bfs_build_is_lazy): only k_bfs_build2 knows them, and only when both queue-less bodies are available

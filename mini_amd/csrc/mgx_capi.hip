@@ -152,15 +152,15 @@ static void ensure_nr_slices(mgx_graph_s* g) {
   if (G.nrs_tried) return;
   G.nrs_tried = true;
   if (const char* e = mgx::env("MGX_NR_SLICED")) if (atoi(e) == 0) return;
-  if (!G.has_layout || G.ub_units <= 0 || !G.d_ub_first.size() || G.vs_long_min != G.ub_min_degree || G.vs_long_min < 17 || G.vs_long_min > 64 ||
-      G.vs_v[0] == 0 || G.vs_dummy == 0) return;
+  if (!G.has_layout || G.rows.ub.units <= 0 || !G.rows.ub.first.size() || G.rows.vs_long_min != G.rows.ub_min_degree || G.rows.vs_long_min < 17 || G.rows.vs_long_min > 64 ||
+      G.rows.vs_v[0] == 0 || G.rows.vs_dummy == 0) return;
   standard_context_t& ctx = *g->c->ctx;
   const unsigned S = (unsigned)mgx::NR_HOTV;
   const long long n = G.num_nodes;
   const int all = (int)std::min<long long>((n + S - 1) / S, (long long)mgx::NRS_MAX_SLICES);      // (slices the id range has)
   int slices = std::min(all, mgx::nrs_default_slices(n));
   if (const char* e = mgx::env("MGX_NR_SLICES")) { const int v = atoi(e); if (v >= 1) slices = std::min(v, all); }   // (tests: a tail on small graphs, many slices on mid-size ones)
-  const int rows = (int)G.vs_v[0];
+  const int rows = (int)G.rows.vs_v[0];
   void* mu = nullptr;
   unsigned* off = nullptr;
   unsigned first[mgx::NRS_MAX_SLICES + 2] = {0};
@@ -396,10 +396,11 @@ int mgx_graph_attach_layout(mgx_graph_t g, const int* d_row_offsets, const int* 
   G.d_new_of_old = mem_t<int>::borrow((int*)d_new_of_old, (size_t)G.num_nodes);
   G.d_old_of_new = mem_t<int>::borrow((int*)d_old_of_new, (size_t)G.num_nodes);
   G.has_layout = true;
-  G.vs_edges = 0; G.vs_dummy = 0; G.vs_long_min = 0;      // (borrowed arrays: no padding behind them, sortedness not checked)
-  G.d_cold_owner = mem_t<int>(); G.d_cold_dst = mem_t<int>(); G.d_colds_owner = mem_t<int>(); G.d_colds_dst = mem_t<int>();
-  G.d_cold_pk = mem_t<unsigned>(); G.d_cold_cbase = mem_t<unsigned>(); G.cold_pk_mask = 0;
-  G.cold_pairs = G.colds_pairs = 0; G.cold_slices = 0;
+  mgx::row_layout_t& R = G.rows;
+  R.vs_edges = 0; R.vs_dummy = 0; R.vs_long_min = 0;      // (borrowed arrays: no padding behind them, sortedness not checked)
+  R.cold_owner = mem_t<int>(); R.cold_dst = mem_t<int>(); R.colds_owner = mem_t<int>(); R.colds_dst = mem_t<int>();
+  R.cold_pk = mem_t<unsigned>(); R.cold_cbase = mem_t<unsigned>(); R.cold_pk_mask = 0;
+  R.cold_pairs = R.colds_pairs = 0; R.cold_slices = 0;
   use_device(g->c);
   g->c->ctx->synchronize();
   build_unit_blocks(g);
@@ -416,77 +417,42 @@ int mgx_graph_attach_layout_weights(mgx_graph_t g, const float* d_layout_weights
 }
 extern "C" int mgx_layout_build_device(const int* ro, const int* ci, const float* w, int n, long long m, int* lro, int* lci,
                                        float* lw, int* new_of_old, int* old_of_new, hipStream_t stream);   // mgx_layout.hip
-extern "C" int mgx_units_build_device(const int* ro, const int* ci, int n, int min_deg, int max_deg, int ushift, unsigned hot_limit,
-                                      int** owner, int** ucol, unsigned char** ucnt, int** ufirst, long long* units, long long* units_pad,
-                                      hipStream_t stream);
-
-// Unit blocks of the layout's long rows (mgx/bfs_fused_dense.hpp).  The threshold is the
-// fused traversal's long-row threshold at build time (MGX_BFS_LONG_MIN, default mgx::LONG_MIN_DEFAULT; a unit is 64 entries whatever the
-// threshold); a run with another threshold ignores the blocks.
-namespace {
-// four 32-bit entries -> three words of 24-bit entries (little endian: entry k occupies bits [24 k, 24 k + 24) of the 96)
-__global__ __launch_bounds__(256) void k_pack24(const int4* __restrict__ in, long long quads, unsigned* __restrict__ out) {
-  for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (long long)gridDim.x * blockDim.x) {
-    const int4 e = in[q];
-    const unsigned a = (unsigned)e.x & 0xFFFFFFu, b = (unsigned)e.y & 0xFFFFFFu, c = (unsigned)e.z & 0xFFFFFFu, d = (unsigned)e.w & 0xFFFFFFu;
-    out[3 * q + 0] = a | (b << 24);
-    out[3 * q + 1] = (b >> 8) | (c << 16);
-    out[3 * q + 2] = (c >> 16) | (d << 8);
-  }
-}
-}  // namespace
+// Unit blocks of the layout's long rows (mgx/bfs_fused_dense.hpp; built by mgx_layout.hip: mgx::build_unit_blocks).  The threshold is
+// the fused traversal's long-row threshold at build time (MGX_BFS_LONG_MIN, default mgx::LONG_MIN_DEFAULT; a unit is 64 entries
+// whatever the threshold); a run with another threshold ignores the blocks.
 static void build_unit_blocks(mgx_graph_s* g) {
   graph_device_t& G = *g->g;
-  G.d_ub_col = mem_t<int>(); G.d_ub_owner = mem_t<int>(); G.ub_units = G.ub_units_pad = 0; G.ub_min_degree = 0;
-  G.d_ub_col24 = mem_t<unsigned>();
-  G.d_ub_cnt = mem_t<unsigned char>(); G.d_ub_first = mem_t<int>(); G.nr_big_rows = 0; G.d_ub_w = mem_t<float>(); G.d_ub_w16 = mem_t<unsigned short>(); G.ub_w_tried = false;
+  mgx::row_layout_t& R = G.rows;
+  R.ub = mgx::unit_blocks_t(); R.ub_min_degree = 0;
+  G.nr_big_rows = 0; G.d_ub_w = mem_t<float>(); G.d_ub_w16 = mem_t<unsigned short>(); G.ub_w_tried = false;
   G.d_nrs_mu = mem_t<unsigned>(); G.d_nrs_off = mem_t<unsigned>(); G.nrs_units = 0; G.nrs_slices = G.nrs_rows = 0; G.nrs_tier[0] = G.nrs_tier[1] = G.nrs_tier[2] = 0; G.nrs_tried = false;
   int long_min = mgx::LONG_MIN_DEFAULT;
   if (const char* e = mgx::env("MGX_BFS_LONG_MIN")) long_min = atoi(e);
   if (long_min <= 0 || !G.has_layout || G.num_edges <= 0) return;
-  int *owner = nullptr, *ucol = nullptr, *ufirst = nullptr;
-  unsigned char* ucnt = nullptr;
-  long long units = 0, units_pad = 0;
-  const int rc = mgx_units_build_device(G.d_layout_row_offsets.data(), G.d_layout_col_indices.data(), G.num_nodes, long_min,
-                                        0x7FFFFFFF, 6, 0u, &owner, &ucol, &ucnt, &ufirst, &units, &units_pad, g->c->ctx->stream());
-  if (rc != 0) throw mgx::mgx_error(MGX_E_HIP, std::string("unit blocks: ") + hipGetErrorString((hipError_t)rc));
-  if (units <= 0) return;
-  G.d_ub_owner = mem_t<int>::adopt(owner, (size_t)units_pad);
-  G.d_ub_col = mem_t<int>::adopt(ucol, ((size_t)units_pad << 6) + 4);
-  G.d_ub_cnt = mem_t<unsigned char>::adopt(ucnt, (size_t)units_pad + 16);
-  G.d_ub_first = mem_t<int>::adopt(ufirst, (size_t)G.num_nodes + 1);
-  // the neighbour-reduce over the unit blocks (mgx/nreduce.hpp) keeps its values and per-unit partials in the context's arena
-  g->c->ctx->reserve_scratch(mgx::nr_scratch_bytes(G.num_nodes, units_pad, 8));
-  G.ub_units = units; G.ub_units_pad = units_pad; G.ub_min_degree = long_min;
-  // 24-bit copy for the fused BFS (ids below 2^23: bit 23 of an entry is free, so a sign-extending unpack turns 0xFFFFFF
-  // back into -1); (units_pad * 64 + 4) entries -- the four -1 behind the blocks included -- are whole quads
+  // 24-bit copy for the fused BFS (ids below 2^23: bit 23 of an entry is free, so a sign-extending unpack turns 0xFFFFFF back into -1).
+  // Round 6 (memory): every reader of the unit blocks takes the 24-bit copy when there is one -- the fused BFS, the neighbour-reduce,
+  // the fused SSSP's sweep (with half or float weights) -- so the 32-bit entries go: 493 MB of RMAT-22's 2.03 GB of layout.
+  // (MGX_BFS_PACK24=0 at layout time keeps them and builds no copy.)
   bool pack = (long long)G.num_nodes <= (1ll << 23);
   if (const char* e = mgx::env("MGX_BFS_PACK24")) pack = pack && atoi(e) != 0;
-  if (pack) {
-    const long long quads = ((long long)units_pad << 4) + 1;
-    G.d_ub_col24 = mem_t<unsigned>((size_t)quads * 3 + 4, *g->c->ctx);
-    hipLaunchKernelGGL(k_pack24, dim3(mgx::grid_for(quads, 256, 16384)), dim3(256), 0, g->c->ctx->stream(), (const int4*)G.d_ub_col.data(), quads,
-                       G.d_ub_col24.data());
-    // Round 6 (memory): every reader of the unit blocks takes the 24-bit copy when there is one -- the fused BFS, the neighbour-reduce,
-    // the fused SSSP's sweep (with half or float weights) -- so the 32-bit entries go: 493 MB of RMAT-22's 2.03 GB of layout.
-    // (MGX_BFS_PACK24=0 at layout time keeps them and builds no copy.)
-    g->c->ctx->synchronize();
-    G.d_ub_col = mem_t<int>();
-  }
+  mgx::build_unit_blocks(R.ub, G.d_layout_row_offsets.data(), G.d_layout_col_indices.data(), G.num_nodes, long_min, 0u, mgx::owner_remap_t(), true,
+                         g->c->ctx->stream());
+  if (R.ub.units <= 0) return;
+  // the neighbour-reduce over the unit blocks (mgx/nreduce.hpp) keeps its values and per-unit partials in the context's arena
+  g->c->ctx->reserve_scratch(mgx::nr_scratch_bytes(G.num_nodes, R.ub.units_pad, 8));
+  R.ub_min_degree = long_min;
+  if (pack) mgx::pack_unit_blocks24(R.ub, false, g->c->ctx->stream());
 }
-extern "C" int mgx_cold_build_device(const int* ro, const int* ci, int n, int row0, int rows, int min_deg, unsigned hot_n, unsigned slice_n,
-                                     int slices, int** owner, int** dst, long long* pairs, int* slice_off, hipStream_t stream);
-extern "C" int mgx_cold_pack_device(const int* owner, const int* dst, int used, const unsigned* off, const unsigned* lo, int ranks,
-                                    unsigned** pk, unsigned** cbase, unsigned* cb_off, unsigned long long* mask, hipStream_t stream);
 // Cold-edge lists of the layout (mgx/bfs_fused_cold.hpp); MGX_BFS_COLD_LISTS=0 skips them.  Needs the unit blocks and the
 // degree classes (a degree-sorted layout: the long rows are [0, vs_v[0]), the short ones [vs_v[0], vs_v[3])); built only
 // when the cold entries are a small share of the long rows' entries (a skewed graph under the hub-first order) and few
 // slices hold any.  One list for the long rows, one for the short rows, the same slices.
 static void build_cold_lists(mgx_graph_s* g) {
   graph_device_t& G = *g->g;
-  G.d_cold_owner = mem_t<int>(); G.d_cold_dst = mem_t<int>(); G.d_colds_owner = mem_t<int>(); G.d_colds_dst = mem_t<int>();
-  G.cold_pairs = G.colds_pairs = 0; G.cold_slices = 0; G.cold_hot_n = 0; G.cold_long_min = 0; G.cold_majority = false; G.cold_all = false;
-  G.d_ubh_col24 = mem_t<unsigned>(); G.d_ubh_owner = mem_t<int>(); G.ubh_units = G.ubh_units_pad = 0;
+  mgx::row_layout_t& R = G.rows;
+  R.cold_owner = mem_t<int>(); R.cold_dst = mem_t<int>(); R.colds_owner = mem_t<int>(); R.colds_dst = mem_t<int>();
+  R.cold_pairs = R.colds_pairs = 0; R.cold_slices = 0; R.cold_hot_n = 0; R.cold_long_min = 0; R.cold_majority = false; R.cold_all = false;
+  R.ubh = mgx::unit_blocks_t();
   // the short rows' list too on graphs of more than 2^23 vertices (equal to marking those entries on RMAT-22, where 6 % of the entries
   // are cold; RMAT-24 -2 %, RMAT-25 -9 % of a traversal); MGX_BFS_COLD_LISTS: 0 no lists at all, 1 the long rows' only, 2 both
   bool with_short = (long long)G.num_nodes > (1ll << 23);
@@ -494,7 +460,7 @@ static void build_cold_lists(mgx_graph_s* g) {
     if (atoi(e) == 0) return;
     with_short = atoi(e) == 2;
   }
-  if (G.ub_units <= 0 || G.vs_long_min <= 0 || G.vs_long_min != G.ub_min_degree || G.vs_v[0] == 0) return;
+  if (R.ub.units <= 0 || R.vs_long_min <= 0 || R.vs_long_min != R.ub_min_degree || R.vs_v[0] == 0) return;
   const unsigned hot_n = (unsigned)mgx::BFS_COLD_WORDS * 32u, slice_n = hot_n;
   const unsigned n = (unsigned)G.num_nodes;
   if (n <= hot_n) return;                                          // everything is inside the prefix
@@ -503,15 +469,13 @@ static void build_cold_lists(mgx_graph_s* g) {
   int slices = (int)slices_ll;
   unsigned list_hot_n = hot_n;          // first vertex the lists cover (0: a FLAT graph's lists hold every entry, below)
   bool flat = false;
-  std::vector<int> off_l((size_t)slices + 1, 0), off_s((size_t)slices + 1, 0);
-  int *owner = nullptr, *dst = nullptr;
-  long long pairs = 0;
-  int rc = mgx_cold_build_device(G.d_layout_row_offsets.data(), G.d_layout_col_indices.data(), (int)n, 0, (int)G.vs_v[0],
-                                 G.vs_long_min, hot_n, slice_n, slices, &owner, &dst, &pairs, off_l.data(), g->c->ctx->stream());
-  if (rc != 0) throw mgx::mgx_error(MGX_E_HIP, std::string("cold-edge lists: ") + hipGetErrorString((hipError_t)rc));
+  const int *ro = G.d_layout_row_offsets.data(), *ci = G.d_layout_col_indices.data();
+  hipStream_t s = g->c->ctx->stream();
+  std::vector<int> off_l;
+  mem_t<int> d_owner, d_dst;
+  long long pairs = mgx::build_cold_pairs(d_owner, d_dst, off_l, ro, ci, (int)n, 0, (int)R.vs_v[0], R.vs_long_min, hot_n, slice_n, slices, s);
   if (pairs <= 0) return;
-  mem_t<int> d_owner = mem_t<int>::adopt(owner, (size_t)pairs + 256), d_dst = mem_t<int>::adopt(dst, (size_t)pairs + 256);
-  const long long long_entries = (long long)G.ub_units * 64;       // (padded: an upper bound of the long rows' entries)
+  const long long long_entries = R.ub.units * 64;                  // (padded: an upper bound of the long rows' entries)
   if (pairs * 4 > long_entries) {
     // A FLAT graph (a uniform random graph: six entries in seven point behind the LDS prefix).  Round 5 left it to the bodies that PROBE
     // the bitmap in L2 -- 134 M probes at what the L2s deliver, 1.34 ms per RMAT-22-sized traversal, whatever the kernel around them
@@ -519,93 +483,45 @@ static void build_cold_lists(mgx_graph_s* g) {
     // prefix itself); a level that holds an eighth of the graph's entries is then ONE sweep of the packed pairs by the cold-edge
     // pass's workgroups, each with its slice of the bitmap in LDS -- no probe leaves the compute unit, no mark is stored -- and the
     // other levels walk their queues and mark untested (few entries: few marks).  MGX_BFS_FLAT_LISTS=0: the probes, as in round 5.
-    G.cold_majority = true;
+    R.cold_majority = true;
     bool want = (long long)G.num_edges < (1ll << 31) - 512 && (n + (long long)slice_n - 1) / slice_n <= 64;
     if (const char* e = mgx::env("MGX_BFS_FLAT_LISTS")) want = want && atoi(e) != 0;
-    if (!want || G.vs_v[3] == 0) return;
-    d_owner = mem_t<int>(); d_dst = mem_t<int>();                    // (the long rows' cold entries: superseded)
-    slices = (int)((n + (long long)slice_n - 1) / slice_n);
-    off_l.assign((size_t)slices + 1, 0); off_s.assign((size_t)slices + 1, 0);
-    owner = nullptr; dst = nullptr; pairs = 0;
-    rc = mgx_cold_build_device(G.d_layout_row_offsets.data(), G.d_layout_col_indices.data(), (int)n, 0, (int)G.vs_v[3], 1, 0u, slice_n, slices,
-                               &owner, &dst, &pairs, off_l.data(), g->c->ctx->stream());
-    if (rc != 0) { (void)hipGetLastError(); return; }                // (no memory for 8 bytes per entry: the probes serve)
+    if (!want || R.vs_v[3] == 0) return;
+    slices = (int)((n + (long long)slice_n - 1) / slice_n);         // (the long rows' cold entries: superseded; no memory for 8 bytes per entry: the probes serve)
+    pairs = mgx::build_cold_pairs(d_owner, d_dst, off_l, ro, ci, (int)n, 0, (int)R.vs_v[3], 1, 0u, slice_n, slices, s, true);
     if (pairs <= 0) return;
-    d_owner = mem_t<int>::adopt(owner, (size_t)pairs + 256); d_dst = mem_t<int>::adopt(dst, (size_t)pairs + 256);
     list_hot_n = 0u; flat = true; with_short = false;
-    G.cold_majority = false;
+    R.cold_majority = false;
   }
   // the short rows' cold entries
-  int *owner_s = nullptr, *dst_s = nullptr;
-  long long pairs_s = 0;
+  std::vector<int> off_s((size_t)slices + 1, 0);
   mem_t<int> d_owner_s, d_dst_s;
-  if (with_short && G.vs_v[3] > G.vs_v[0]) {
-    rc = mgx_cold_build_device(G.d_layout_row_offsets.data(), G.d_layout_col_indices.data(), (int)n, (int)G.vs_v[0],
-                               (int)(G.vs_v[3] - G.vs_v[0]), 1, hot_n, slice_n, slices, &owner_s, &dst_s, &pairs_s, off_s.data(),
-                               g->c->ctx->stream());
-    if (rc != 0) throw mgx::mgx_error(MGX_E_HIP, std::string("cold-edge lists: ") + hipGetErrorString((hipError_t)rc));
-    if (pairs_s > 0) {
-      d_owner_s = mem_t<int>::adopt(owner_s, (size_t)pairs_s + 256); d_dst_s = mem_t<int>::adopt(dst_s, (size_t)pairs_s + 256);
-      if (pairs_s * 2 > (long long)G.vs_edges) { d_owner_s = mem_t<int>(); d_dst_s = mem_t<int>(); pairs_s = 0; }    // (mostly cold: leave them to the marks)
-    }
+  long long pairs_s = 0;
+  if (with_short && R.vs_v[3] > R.vs_v[0]) {
+    pairs_s = mgx::build_cold_pairs(d_owner_s, d_dst_s, off_s, ro, ci, (int)n, (int)R.vs_v[0], (int)(R.vs_v[3] - R.vs_v[0]), 1, hot_n, slice_n, slices, s);
+    if (pairs_s * 2 > (long long)R.vs_edges) { d_owner_s = mem_t<int>(); d_dst_s = mem_t<int>(); pairs_s = 0; }    // (mostly cold: leave them to the marks)
   }
   if (pairs_s <= 0) std::fill(off_s.begin(), off_s.end(), 0);
-  // the slices that hold pairs of either list; give up when there are too many of them
-  int used = 0;
-  for (int k = 0; k < slices; ++k) if (off_l[k + 1] > off_l[k] || off_s[k + 1] > off_s[k]) ++used;
-  if (used > mgx::BFS_COLD_MAX_SLICES) return;
-  int q = 0;
-  for (int k = 0; k < slices; ++k) {
-    if (!(off_l[k + 1] > off_l[k] || off_s[k + 1] > off_s[k])) continue;
-    G.cold_lo[q] = list_hot_n + (unsigned)k * slice_n;
-    G.cold_off[q] = (unsigned)off_l[k]; G.cold_off[q + 1] = (unsigned)off_l[k + 1];
-    G.colds_off[q] = (unsigned)off_s[k]; G.colds_off[q + 1] = (unsigned)off_s[k + 1];
-    ++q;
-  }
-  // workgroups per slice: in proportion to its pairs, at least one each; in all one per 131 072 pairs, 64 .. 1024
-  const long long all = pairs + pairs_s;
-  long long nwg = (all + 131071) / 131072;
+  // workgroups: one per 131 072 pairs, 64 .. 1024
+  long long nwg = (pairs + pairs_s + 131071) / 131072;
   nwg = std::max<long long>(nwg, mgx::BFS_COLD_WGS);
   nwg = std::min<long long>(nwg, mgx::BFS_COLD_WGS_MAX);
-  nwg = std::max<long long>(nwg, used);
-  unsigned left = (unsigned)nwg - (unsigned)used, acc = 0;
-  G.cold_wgs[0] = 0;
-  for (int i = 0; i < used; ++i) {
-    const long long cnt = ((long long)G.cold_off[i + 1] - (long long)G.cold_off[i]) + ((long long)G.colds_off[i + 1] - (long long)G.colds_off[i]);
-    unsigned extra = (unsigned)((cnt * (long long)((unsigned)nwg - (unsigned)used)) / all);
-    if (extra > left) extra = left;
-    left -= extra;
-    acc += 1u + extra;
-    G.cold_wgs[i + 1] = acc;
+  R.cold_owner = std::move(d_owner); R.cold_dst = std::move(d_dst); R.cold_pairs = pairs;
+  R.colds_owner = std::move(d_owner_s); R.colds_dst = std::move(d_dst_s); R.colds_pairs = pairs_s;
+  if (!mgx::cut_cold_lists(R, off_l, off_s, list_hot_n, slice_n, nwg, mgx::owner_remap_t(), true, s)) return;
+  // Round 6 (memory): with EVERY slice packed nobody reads the 8-byte pairs of the long rows again (bfs_cold_body takes the packed
+  // words slice by slice): they go -- 53 MB on RMAT-22.  (MGX_BFS_COLD_PACK=0 at layout time keeps them and packs nothing.)
+  const int used = R.cold_slices;
+  const unsigned long long every = used >= 64 ? ~0ull : ((1ull << used) - 1ull);
+  if (R.cold_pk.size() && (R.cold_pk_mask & every) == every) {
+    g->c->ctx->synchronize();
+    R.cold_owner = mem_t<int>(); R.cold_dst = mem_t<int>();
   }
-  for (int i = used + 1; i <= mgx::BFS_COLD_MAX_SLICES; ++i) { G.cold_wgs[i] = acc; G.cold_off[i] = G.cold_off[used]; G.colds_off[i] = G.colds_off[used]; }
-  G.d_cold_owner = std::move(d_owner); G.d_cold_dst = std::move(d_dst);
-  G.d_colds_owner = std::move(d_owner_s); G.d_colds_dst = std::move(d_dst_s);
-  {
-    // the long rows' pairs once more, four bytes each
-    unsigned *pk = nullptr, *cbase = nullptr;
-    unsigned long long mask = 0;
-    const int rcp = mgx_cold_pack_device(G.d_cold_owner.data(), G.d_cold_dst.data(), used, G.cold_off, G.cold_lo, 1, &pk, &cbase, G.cold_cb, &mask,
-                                         g->c->ctx->stream());
-    if (rcp != 0) throw mgx::mgx_error(MGX_E_HIP, std::string("cold-edge lists, packed copy: ") + hipGetErrorString((hipError_t)rcp));
-    if (pk && cbase) {
-      G.d_cold_pk = mem_t<unsigned>::adopt(pk, (size_t)pairs + 256);
-      G.d_cold_cbase = mem_t<unsigned>::adopt(cbase, (size_t)G.cold_cb[used] + 64);
-      G.cold_pk_mask = mask;
-      // Round 6 (memory): with EVERY slice packed nobody reads the 8-byte pairs of the long rows again (bfs_cold_body takes the
-      // packed words slice by slice): they go -- 53 MB on RMAT-22.  (MGX_BFS_COLD_PACK=0 at layout time keeps them and packs nothing.)
-      const unsigned long long every = used >= 64 ? ~0ull : ((1ull << used) - 1ull);
-      if ((mask & every) == every) {
-        g->c->ctx->synchronize();
-        G.d_cold_owner = mem_t<int>(); G.d_cold_dst = mem_t<int>();
-      }
-    }
-  }
-  G.cold_pairs = pairs; G.colds_pairs = pairs_s; G.cold_slices = used; G.cold_hot_n = list_hot_n; G.cold_long_min = G.vs_long_min;
-  G.cold_all = flat;
-  if (flat && (!G.d_cold_pk.size() || G.d_cold_owner.size())) {        // (a flat graph's lists are only worth their bytes when EVERY slice is packed: 4 per entry, what the CSR costs)
-    G.d_cold_owner = mem_t<int>(); G.d_cold_dst = mem_t<int>(); G.d_cold_pk = mem_t<unsigned>(); G.d_cold_cbase = mem_t<unsigned>();
-    G.cold_pairs = 0; G.cold_slices = 0; G.cold_all = false; G.cold_majority = true;
+  R.cold_hot_n = list_hot_n; R.cold_long_min = R.vs_long_min;
+  R.cold_all = flat;
+  if (flat && (!R.cold_pk.size() || R.cold_owner.size())) {        // (a flat graph's lists are only worth their bytes when EVERY slice is packed: 4 per entry, what the CSR costs)
+    R.cold_owner = mem_t<int>(); R.cold_dst = mem_t<int>(); R.cold_pk = mem_t<unsigned>(); R.cold_cbase = mem_t<unsigned>();
+    R.cold_pairs = 0; R.cold_slices = 0; R.cold_all = false; R.cold_majority = true;
     return;
   }
   if (flat) return;                          // (no blocks "without the lists' entries": the lists hold everything)
@@ -616,34 +532,9 @@ static void build_cold_lists(mgx_graph_s* g) {
   bool hot_units = true;
   if (const char* e = mgx::env("MGX_BFS_HOT_UNITS")) hot_units = atoi(e) != 0;
   if (const char* e = mgx::env("MGX_BFS_PACK24")) hot_units = hot_units && atoi(e) != 0;
-  if (hot_units) {
-    int *owner2 = nullptr, *ucol2 = nullptr, *ufirst2 = nullptr;
-    unsigned char* ucnt2 = nullptr;
-    long long U2 = 0, Up2 = 0;
-    const int rc3 = mgx_units_build_device(G.d_layout_row_offsets.data(), G.d_layout_col_indices.data(), G.num_nodes, G.vs_long_min, 0x7FFFFFFF, 6,
-                                           hot_n, &owner2, &ucol2, &ucnt2, &ufirst2, &U2, &Up2, g->c->ctx->stream());
-    if (ucnt2) (void)hipFree(ucnt2);
-    if (ufirst2) (void)hipFree(ufirst2);
-    if (rc3 != 0) {
-      if (owner2) (void)hipFree(owner2);
-      if (ucol2) (void)hipFree(ucol2);
-      throw mgx::mgx_error(MGX_E_HIP, std::string("unit blocks of the hot entries: ") + hipGetErrorString((hipError_t)rc3));
-    }
-    if (U2 > 0) {
-      mem_t<int> d_owner2 = mem_t<int>::adopt(owner2, (size_t)Up2);
-      mem_t<int> d_col2 = mem_t<int>::adopt(ucol2, ((size_t)Up2 << 6) + 4);          // (freed below: only the 24-bit copy is kept)
-      const long long quads = ((long long)Up2 << 4) + 1;
-      G.d_ubh_col24 = mem_t<unsigned>((size_t)quads * 3 + 4, *g->c->ctx);
-      hipLaunchKernelGGL(k_pack24, dim3(mgx::grid_for(quads, 256, 16384)), dim3(256), 0, g->c->ctx->stream(), (const int4*)d_col2.data(), quads,
-                         G.d_ubh_col24.data());
-      g->c->ctx->synchronize();
-      G.d_ubh_owner = std::move(d_owner2);
-      G.ubh_units = U2; G.ubh_units_pad = Up2;
-    } else {
-      if (owner2) (void)hipFree(owner2);
-      if (ucol2) (void)hipFree(ucol2);
-    }
-  }
+  if (!hot_units) return;
+  mgx::build_unit_blocks(R.ubh, ro, ci, G.num_nodes, R.vs_long_min, hot_n, mgx::owner_remap_t(), false, s);
+  if (R.ubh.units > 0) mgx::pack_unit_blocks24(R.ubh, false, s);
 }
 int mgx_graph_build_layout(mgx_graph_t g, int with_weights) {
   MGX_TRY
@@ -671,26 +562,18 @@ int mgx_graph_build_layout(mgx_graph_t g, int with_weights) {
   if (with_weights) { G.d_layout_col_values = std::move(lw); G.has_layout_weights = true; }
   build_unit_blocks(g);
   // degree classes of the short rows (the layout is sorted by degree): boundaries by binary search on a host copy
-  G.vs_edges = 0; G.vs_dummy = 0; G.vs_long_min = 0;
+  mgx::row_layout_t& R = G.rows;
+  R.vs_edges = 0; R.vs_dummy = 0; R.vs_long_min = 0;
   {
     int long_min = mgx::LONG_MIN_DEFAULT;
     if (const char* e = mgx::env("MGX_BFS_LONG_MIN")) long_min = atoi(e);
     if (long_min > 0 && long_min <= 64 && n > 0 && m > 0) {
       std::vector<int> h(n + 1);
       MGX_HIP(mgx::dtoh(h.data(), G.d_layout_row_offsets.data(), n + 1));
-      auto first_below = [&](int d) {            // first vertex with degree < d (degrees are non-increasing)
-        size_t lo = 0, hi = n;
-        while (lo < hi) { const size_t mid = (lo + hi) / 2; if (h[mid + 1] - h[mid] >= d) lo = mid + 1; else hi = mid; }
-        return (unsigned)lo;
-      };
-      const unsigned b0 = first_below(long_min), b1 = std::max(b0, first_below(17)), b2 = std::max(b1, first_below(5)),
-                     b3 = std::max(b2, first_below(1));
-      G.vs_v[0] = b0; G.vs_v[1] = b1; G.vs_v[2] = b2; G.vs_v[3] = b3;
-      G.vs_v9 = std::min(b2, std::max(b1, first_below(9)));
-      G.nr_big_rows = first_below(64 * mgx::NR_BIG_UNITS + 1);       // rows of more than NR_BIG_UNITS units (mgx/nreduce.hpp)
-      G.vs_edges = (unsigned)(h[b3] - h[b0]);
-      G.vs_dummy = (unsigned)m + 4u;
-      G.vs_long_min = long_min;
+      mgx::cut_degree_classes(R, h, n, long_min);
+      G.nr_big_rows = mgx::first_row_below(h, n, 64 * mgx::NR_BIG_UNITS + 1);       // rows of more than NR_BIG_UNITS units (mgx/nreduce.hpp)
+      R.vs_dummy = (unsigned)m + 4u;
+      R.vs_long_min = long_min;
     }
   }
 build_cold_lists(g);
@@ -739,17 +622,18 @@ int mgx_graph_layout_info(mgx_graph_t g, int64_t* out8) {
   for (int i = 0; i < 8; ++i) out8[i] = 0;
   if (!G.has_layout) return MGX_OK;
   out8[0] = 1;
-  out8[1] = (int64_t)G.ub_units;
-  out8[2] = G.d_ub_col24.size() ? 1 : 0;
-  out8[3] = (int64_t)G.cold_pairs;
-  out8[4] = (int64_t)G.cold_slices;
-  out8[5] = (int64_t)G.ubh_units;
-  out8[6] = G.cold_majority ? 1 : 0;
+  const mgx::row_layout_t& R = G.rows;
+  out8[1] = (int64_t)R.ub.units;
+  out8[2] = R.ub.col24.size() ? 1 : 0;
+  out8[3] = (int64_t)R.cold_pairs;
+  out8[4] = (int64_t)R.cold_slices;
+  out8[5] = (int64_t)R.ubh.units;
+  out8[6] = R.cold_majority ? 1 : 0;
   auto bytes = [](auto& m) -> int64_t { return m.owned() ? (int64_t)(m.size() * sizeof(*m.data())) : 0; };
   out8[7] = bytes(G.d_layout_row_offsets) + bytes(G.d_layout_col_indices) + bytes(G.d_layout_col_values) + bytes(G.d_new_of_old) + bytes(G.d_old_of_new) +
-            bytes(G.d_ub_col) + bytes(G.d_ub_col24) + bytes(G.d_ub_owner) + bytes(G.d_ubh_col24) + bytes(G.d_ubh_owner) + bytes(G.d_ub_w) + bytes(G.d_ub_w16) +
-            bytes(G.d_ub_cnt) + bytes(G.d_ub_first) + bytes(G.d_cold_owner) + bytes(G.d_cold_dst) + bytes(G.d_cold_pk) + bytes(G.d_cold_cbase) +
-            bytes(G.d_colds_owner) + bytes(G.d_colds_dst) + bytes(G.d_nrs_mu) + bytes(G.d_nrs_off) + bytes(G.d_nr_pos);
+            bytes(R.ub.col) + bytes(R.ub.col24) + bytes(R.ub.owner) + bytes(R.ubh.col24) + bytes(R.ubh.owner) + bytes(G.d_ub_w) + bytes(G.d_ub_w16) +
+            bytes(R.ub.cnt) + bytes(R.ub.first) + bytes(R.cold_owner) + bytes(R.cold_dst) + bytes(R.cold_pk) + bytes(R.cold_cbase) +
+            bytes(R.colds_owner) + bytes(R.colds_dst) + bytes(G.d_nrs_mu) + bytes(G.d_nrs_off) + bytes(G.d_nr_pos);
   MGX_CATCH
 }
 int mgx_graph_nr_slices_info(mgx_graph_t g, int64_t* out5) {
@@ -1512,31 +1396,24 @@ int mgx_dbfs2_build_units(mgx_dbfs2_t h, int64_t* units) {
   MGX_REQUIRE(h, "NULL argument");
   use_device(h->c);
   mgx::d2_state_t& st = h->st;
+  mgx::row_layout_t& R = st.rows;
+  standard_context_t& ctx = *h->c->ctx;
   if (units) *units = 0;
-  if (st.ub_col) { if (units) *units = st.ub_units; return MGX_OK; }
+  if (st.blocks().col.size()) { if (units) *units = st.blocks().units; return MGX_OK; }
   const int long_min = st.fs->long_min;
   if (long_min != 64 || st.n_local <= 0) return MGX_OK;     // (a unit is 64 entries: only with the default long-row threshold)
-  h->c->ctx->synchronize();
-  int *owner = nullptr, *ucol = nullptr, *ufirst = nullptr;
-  unsigned char* ucnt = nullptr;
-  long long U = 0, Up = 0;
-  const int rc = mgx_units_build_device(st.row_offsets, st.col_indices, st.n_local, long_min, 0x7FFFFFFF, 6, 0u, &owner, &ucol, &ucnt, &ufirst, &U, &Up,
-                                        h->c->ctx->stream());
-  if (rc != 0) throw mgx::mgx_error(MGX_E_HIP, std::string("partitioned BFS, unit blocks: ") + hipGetErrorString((hipError_t)rc));
-  if (ucnt) (void)hipFree(ucnt);
-  if (ufirst) (void)hipFree(ufirst);
+  ctx.synchronize();
+  const mgx::owner_remap_t global{st.ranks, st.rank, st.n_local, st.n_global};
+  mgx::build_unit_blocks(R.ub, st.row_offsets, st.col_indices, st.n_local, long_min, 0u, global, false, ctx.stream());
+  const long long U = R.ub.units;
   if (U <= 0) return MGX_OK;
-  hipLaunchKernelGGL(mgx::k_d2_owner_global, dim3((unsigned)((Up + mgx::BLOCK - 1) / mgx::BLOCK)), dim3(mgx::BLOCK), 0, h->c->ctx->stream(), owner, Up,
-                     st.ranks, st.rank, st.n_local, st.n_global);
-  h->c->ctx->synchronize();
-  st.ub_owner = owner; st.ub_col = ucol; st.ub_units = U; st.ub_units_pad = Up;
+  ctx.synchronize();
   if (const char* e = mgx::env("MGX_DIST_DENSE_DIV")) { const int d = atoi(e); if (d >= 0) st.dense_div = (unsigned)d; }
   // the short rows vertex by vertex (MGX_DIST_VSHORT=0: never; N: when a level holds 1 / N of their edges): needs rows by
   // non-increasing degree (hub-first global ids, cyclic ownership: they are) -- checked here, on the host
   {
     int vdiv = 8;
     if (const char* e = mgx::env("MGX_DIST_VSHORT")) vdiv = atoi(e);
-    standard_context_t& ctx = *h->c->ctx;
     const int n = st.n_local;
     if (n > 0) {
       // deferred hot marks only on a shard big enough to pay for their bitmaps (d2_state_t::defer_pays)
@@ -1553,22 +1430,14 @@ int mgx_dbfs2_build_units(mgx_dbfs2_t h, int64_t* units) {
       for (int i = 1; i < n && sorted; ++i) sorted = hro[i + 1] - hro[i] <= hro[i] - hro[i - 1];
       const long long m_local = hro[n];
       if (sorted && m_local > 0) {
-        auto first_below = [&](int d) {            // first row with degree < d
-          size_t lo = 0, hi = (size_t)n;
-          while (lo < hi) { const size_t mid = (lo + hi) / 2; if (hro[mid + 1] - hro[mid] >= d) lo = mid + 1; else hi = mid; }
-          return (unsigned)lo;
-        };
-        const unsigned b0 = first_below(long_min), b1 = std::max(b0, first_below(17)), b2 = std::max(b1, first_below(5)), b3 = std::max(b2, first_below(1));
-        st.vs_v[0] = b0; st.vs_v[1] = b1; st.vs_v[2] = b2; st.vs_v[3] = b3;
-        st.vs_v9 = std::min(b2, std::max(b1, first_below(9)));
-        st.vs_edges = (unsigned)(hro[b3] - hro[b0]);
+        mgx::cut_degree_classes(R, hro, (size_t)n, long_min);
         st.col_pad = mem_t<int>((size_t)m_local + 8, ctx);
         MGX_HIP(hipMemcpyAsync(st.col_pad.data(), st.col_indices, (size_t)m_local * sizeof(int), hipMemcpyDeviceToDevice, ctx.stream()));
         MGX_HIP(hipMemsetAsync(st.col_pad.data() + m_local, 0xFF, 8 * sizeof(int), ctx.stream()));
         st.front_local = mem_t<unsigned>((size_t)n / 32 + 64, ctx);
         MGX_HIP(hipMemsetAsync(st.front_local.data(), 0, st.front_local.size() * sizeof(unsigned), ctx.stream()));
         ctx.synchronize();
-        st.vs_div = st.vs_edges ? (unsigned)vdiv : 0u;
+        st.vs_div = R.vs_edges ? (unsigned)vdiv : 0u;
       }
     }
   }
@@ -1580,109 +1449,52 @@ int mgx_dbfs2_build_units(mgx_dbfs2_t h, int64_t* units) {
   if (const char* e = mgx::env("MGX_DIST_COLD")) want_cold = atoi(e) != 0;
   const unsigned hot_n = (unsigned)mgx::BFS_COLD_WORDS * 32u, slice_n = hot_n;
   const long long slices_ll = (unsigned)st.n_global > hot_n ? ((long long)st.n_global - hot_n + slice_n - 1) / slice_n : 0;
-  if (want_cold && slices_ll >= 1 && slices_ll <= 128) {
-    standard_context_t& ctx = *h->c->ctx;
-    mem_t<int> d_long = mgx::fill<int>(0, 1, ctx), d_sorted = mgx::fill<int>(1, 1, ctx);
-    hipLaunchKernelGGL(mgx::k_d2_row_facts, dim3(ctx.num_cus * 8), dim3(mgx::BLOCK), 0, ctx.stream(), st.row_offsets, st.col_indices, st.n_local, long_min,
-                       d_long.data(), d_sorted.data());
+  if (!want_cold || slices_ll < 1 || slices_ll > 128) return MGX_OK;
+  mem_t<int> d_long = mgx::fill<int>(0, 1, ctx), d_sorted = mgx::fill<int>(1, 1, ctx);
+  hipLaunchKernelGGL(mgx::k_d2_row_facts, dim3(ctx.num_cus * 8), dim3(mgx::BLOCK), 0, ctx.stream(), st.row_offsets, st.col_indices, st.n_local, long_min,
+                     d_long.data(), d_sorted.data());
+  ctx.synchronize();
+  const int long_rows = mgx::from_mem(d_long)[0];
+  const bool rows_sorted = mgx::from_mem(d_sorted)[0] == 1;
+  if (!rows_sorted || long_rows <= 0) return MGX_OK;
+  std::vector<int> off;
+  const long long pairs = mgx::build_cold_pairs(R.cold_owner, R.cold_dst, off, st.row_offsets, st.col_indices, st.n_local, 0, long_rows, long_min, hot_n,
+                                                slice_n, (int)slices_ll, ctx.stream());
+  long long nwg = (pairs + 131071) / 131072;
+  nwg = std::max<long long>(nwg, mgx::BFS_COLD_WGS);
+  // (at most 512 on a rank: every cold workgroup costs a copy of its slice into LDS and an 80 KB bitmap to write and to reduce --
+  //  RMAT-26 / 8 with 1 024 of them: push 584 us and reduce 87 us per traversal, with 512: 552 and 57, with 256: 575 and 46)
+  nwg = std::min<long long>(nwg, 512);
+  if (const char* e = mgx::env("MGX_DIST_COLD_WGS")) if (atoi(e) > 0) nwg = std::min<long long>(atoi(e), mgx::BFS_COLD_WGS_MAX);      // (measurements)
+  // the pairs once more, four bytes each
+  bool pack_pairs = true;
+  if (const char* e = mgx::env("MGX_BFS_COLD_PACK")) pack_pairs = atoi(e) != 0;
+  R.cold_pairs = pairs;
+  // (RMAT-25 / 8: a quarter of the entries, RMAT-26 / 8: a third)
+  if (pairs <= 0 || pairs * 2 > U * 64 ||
+      !mgx::cut_cold_lists(R, off, std::vector<int>(off.size(), 0), hot_n, slice_n, nwg, global, pack_pairs, ctx.stream())) {
+    R.cold_owner = mem_t<int>(); R.cold_dst = mem_t<int>(); R.cold_pairs = 0;
+    return MGX_OK;
+  }
+  st.cold_flush = mem_t<u32>((size_t)R.cold_wgs[R.cold_slices] * mgx::BFS_COLD_WORDS, ctx);
+  MGX_HIP(hipMemsetAsync(st.cold_flush.data(), 0, st.cold_flush.size() * sizeof(unsigned), ctx.stream()));
+  // a launch of its own ORs a slice's bitmaps together in front of the sweep (MGX_DIST_COLD_REDUCE=0: k_d2_newbits reads them all)
+  if (const char* e = mgx::env("MGX_DIST_COLD_REDUCE")) st.cold_reduce = atoi(e);
+  ctx.synchronize();
+  // The unit blocks again, WITHOUT the entries that now live in the pair lists (the unit-block body read them only to skip
+  // them: a third of its stream on RMAT-26 / 8) -- and what is left points into the LDS prefix, ids below 2^20: three bytes
+  // per entry do (bfs_fused_dense.hpp: ub_col24).  MGX_DIST_HOT_UNITS=0: the full blocks stay.
+  bool hot_units = true;
+  if (const char* e = mgx::env("MGX_DIST_HOT_UNITS")) hot_units = atoi(e) != 0;
+  if (hot_units) {
+    mgx::build_unit_blocks(R.ubh, st.row_offsets, st.col_indices, st.n_local, long_min, hot_n, global, false, ctx.stream());
     ctx.synchronize();
-    const int long_rows = mgx::from_mem(d_long)[0];
-    const bool rows_sorted = mgx::from_mem(d_sorted)[0] == 1;
-    const int slices = (int)slices_ll;
-    if (rows_sorted && long_rows > 0) {
-      std::vector<int> off((size_t)slices + 1, 0);
-      int *cowner = nullptr, *cdst = nullptr;
-      long long pairs = 0;
-      const int rc2 = mgx_cold_build_device(st.row_offsets, st.col_indices, st.n_local, 0, long_rows, long_min, hot_n, slice_n, slices, &cowner, &cdst,
-                                            &pairs, off.data(), ctx.stream());
-      if (rc2 != 0) throw mgx::mgx_error(MGX_E_HIP, std::string("partitioned BFS, cold-edge lists: ") + hipGetErrorString((hipError_t)rc2));
-      // (owned by the state from here on: freed with it whatever happens below; the pass is enabled by its flush buffers)
-      st.cold_owner = cowner; st.cold_dst = cdst;
-      int used = 0;
-      for (int k = 0; k < slices; ++k) if (off[k + 1] > off[k]) ++used;
-      if (pairs > 0 && pairs * 2 <= U * 64 && used <= mgx::BFS_COLD_MAX_SLICES) {      // (RMAT-25 / 8: a quarter of the entries, RMAT-26 / 8: a third)
-        hipLaunchKernelGGL(mgx::k_d2_owner_global, dim3((unsigned)((pairs + 256 + mgx::BLOCK - 1) / mgx::BLOCK)), dim3(mgx::BLOCK), 0, ctx.stream(), cowner,
-                           pairs + 256, st.ranks, st.rank, st.n_local, st.n_global);
-        int q = 0;
-        for (int k = 0; k < slices; ++k) {
-          if (off[k + 1] <= off[k]) continue;
-          st.cold_lo[q] = hot_n + (unsigned)k * slice_n;
-          st.cold_off[q] = (unsigned)off[k]; st.cold_off[q + 1] = (unsigned)off[k + 1];
-          ++q;
-        }
-        long long nwg = (pairs + 131071) / 131072;
-        nwg = std::max<long long>(nwg, mgx::BFS_COLD_WGS);
-        // (at most 512 on a rank: every cold workgroup costs a copy of its slice into LDS and an 80 KB bitmap to write and to reduce --
-        //  RMAT-26 / 8 with 1 024 of them: push 584 us and reduce 87 us per traversal, with 512: 552 and 57, with 256: 575 and 46)
-        nwg = std::min<long long>(nwg, 512);
-        if (const char* e = mgx::env("MGX_DIST_COLD_WGS")) if (atoi(e) > 0) nwg = std::min<long long>(atoi(e), mgx::BFS_COLD_WGS_MAX);      // (measurements)
-        nwg = std::max<long long>(nwg, used);
-        unsigned left = (unsigned)nwg - (unsigned)used, acc = 0;
-        st.cold_wgs[0] = 0;
-        for (int i = 0; i < used; ++i) {
-          const long long cnt = (long long)st.cold_off[i + 1] - (long long)st.cold_off[i];
-          unsigned extra = (unsigned)((cnt * (long long)((unsigned)nwg - (unsigned)used)) / pairs);
-          if (extra > left) extra = left;
-          left -= extra;
-          acc += 1u + extra;
-          st.cold_wgs[i + 1] = acc;
-        }
-        for (int i = used + 1; i <= mgx::BFS_COLD_MAX_SLICES; ++i) { st.cold_wgs[i] = acc; st.cold_off[i] = st.cold_off[used]; }
-        st.cold_flush = mem_t<u32>((size_t)acc * mgx::BFS_COLD_WORDS, ctx);
-        MGX_HIP(hipMemsetAsync(st.cold_flush.data(), 0, (size_t)acc * mgx::BFS_COLD_WORDS * sizeof(unsigned), ctx.stream()));
-        // a launch of its own ORs a slice's bitmaps together in front of the sweep (MGX_DIST_COLD_REDUCE=0: k_d2_newbits reads them all)
-        if (const char* e = mgx::env("MGX_DIST_COLD_REDUCE")) st.cold_reduce = atoi(e);
-        ctx.synchronize();
-        st.cold_pairs = pairs; st.cold_slices = used;
-        // the pairs once more, four bytes each (owners are global ids by now: `ranks` apart inside a list)
-        {
-          bool pack_pairs = true;
-          if (const char* e = mgx::env("MGX_BFS_COLD_PACK")) pack_pairs = atoi(e) != 0;
-          if (pack_pairs) {
-            unsigned *pk = nullptr, *cbase = nullptr;
-            unsigned long long mask = 0;
-            const int rcp = mgx_cold_pack_device(st.cold_owner, st.cold_dst, used, st.cold_off, st.cold_lo, st.ranks, &pk, &cbase, st.cold_cb, &mask, ctx.stream());
-            if (rcp != 0) throw mgx::mgx_error(MGX_E_HIP, std::string("partitioned BFS, packed cold-edge lists: ") + hipGetErrorString((hipError_t)rcp));
-            st.cold_pk = pk; st.cold_cbase = cbase; st.cold_pk_mask = mask;
-          }
-        }
-        // The unit blocks again, WITHOUT the entries that now live in the pair lists (the unit-block body read them only to skip
-        // them: a third of its stream on RMAT-26 / 8) -- and what is left points into the LDS prefix, ids below 2^20: three bytes
-        // per entry do (bfs_fused_dense.hpp: ub_col24).  MGX_DIST_HOT_UNITS=0: the full blocks stay.
-        bool hot_units = true;
-        if (const char* e = mgx::env("MGX_DIST_HOT_UNITS")) hot_units = atoi(e) != 0;
-        if (hot_units) {
-          int *owner2 = nullptr, *ucol2 = nullptr, *ufirst2 = nullptr;
-          unsigned char* ucnt2 = nullptr;
-          long long U2 = 0, Up2 = 0;
-          const int rc3 = mgx_units_build_device(st.row_offsets, st.col_indices, st.n_local, long_min, 0x7FFFFFFF, 6, hot_n, &owner2, &ucol2, &ucnt2,
-                                                 &ufirst2, &U2, &Up2, ctx.stream());
-          if (rc3 != 0) throw mgx::mgx_error(MGX_E_HIP, std::string("partitioned BFS, unit blocks of the hot entries: ") + hipGetErrorString((hipError_t)rc3));
-          if (ucnt2) (void)hipFree(ucnt2);
-          if (ufirst2) (void)hipFree(ufirst2);
-          if (U2 > 0) {
-            hipLaunchKernelGGL(mgx::k_d2_owner_global, dim3((unsigned)((Up2 + mgx::BLOCK - 1) / mgx::BLOCK)), dim3(mgx::BLOCK), 0, ctx.stream(), owner2, Up2,
-                               st.ranks, st.rank, st.n_local, st.n_global);
-            ctx.synchronize();
-            (void)hipFree(st.ub_owner); (void)hipFree(st.ub_col);
-            st.ub_owner = owner2; st.ub_col = ucol2; st.ub_units = U2; st.ub_units_pad = Up2;
-            if (units) *units = U2;
-            bool pack = true;
-            if (const char* e = mgx::env("MGX_BFS_PACK24")) pack = atoi(e) != 0;
-            if (pack) {
-              const long long quads = ((long long)Up2 << 4) + 1;
-              st.ub_col24 = mem_t<unsigned>((size_t)quads * 3 + 4, ctx);
-              hipLaunchKernelGGL(k_pack24, dim3(mgx::grid_for(quads, 256, 16384)), dim3(256), 0, ctx.stream(), (const int4*)st.ub_col, quads,
-                                 st.ub_col24.data());
-              ctx.synchronize();
-            }
-          }
-        }
-      } else {
-        if (cowner) (void)hipFree(cowner);
-        if (cdst) (void)hipFree(cdst);
-        st.cold_owner = nullptr; st.cold_dst = nullptr;
-      }
+    if (R.ubh.units > 0) {
+      R.ub = mgx::unit_blocks_t();
+      if (units) *units = R.ubh.units;
+      bool pack = true;
+      if (const char* e = mgx::env("MGX_BFS_PACK24")) pack = atoi(e) != 0;
+      if (pack) mgx::pack_unit_blocks24(R.ubh, true, ctx.stream());
     }
   }
   MGX_CATCH
@@ -1697,7 +1509,7 @@ int mgx_dbfs2_cold_levels(mgx_dbfs2_t h, int64_t* levels, int64_t* pairs) {
   MGX_TRY
   MGX_REQUIRE(h && levels, "NULL argument");
   *levels = (int64_t)h->st.fs->host_ctrl->cold_slots;
-  if (pairs) *pairs = (int64_t)h->st.cold_pairs;
+  if (pairs) *pairs = (int64_t)h->st.rows.cold_pairs;
   MGX_CATCH
 }
 int mgx_dbfs2_path_levels(mgx_dbfs2_t h, int64_t* out4) {
@@ -1707,7 +1519,7 @@ int mgx_dbfs2_path_levels(mgx_dbfs2_t h, int64_t* out4) {
   out4[0] = (int64_t)hc->small_levels;                       // levels whose push appended its discoveries to the id list itself
   out4[1] = (int64_t)hc->vshort_slots;                       // levels whose short rows were walked vertex by vertex
   out4[2] = (int64_t)hc->d2_declared_level >= 0 ? 1 : 0;     // a sweep declared its list overflowed (the last such level is kept, not a count)
-  out4[3] = (int64_t)(h->st.cold_pk ? __builtin_popcountll(h->st.cold_pk_mask) : 0);   // slices whose pairs are packed to 4 bytes
+  out4[3] = (int64_t)(h->st.rows.cold_pk.data() ? __builtin_popcountll(h->st.rows.cold_pk_mask) : 0);   // slices whose pairs are packed to 4 bytes
   MGX_CATCH
 }
 int mgx_dbfs2_free(mgx_dbfs2_t h) {
@@ -2114,20 +1926,20 @@ static void ensure_unit_weights(mgx_graph_s* g) {
   if (G.ub_w_tried) return;
   G.ub_w_tried = true;
   // (the sweep reads the long rows from the unit blocks and walks the short ones by degree class: any threshold the two were cut by together)
-  if (!G.has_layout || !G.has_layout_weights || G.ub_units <= 0 || !G.d_ub_first.size() || G.vs_long_min != G.ub_min_degree || G.vs_long_min < 17 || G.vs_long_min > 64) return;
+  if (!G.has_layout || !G.has_layout_weights || G.rows.ub.units <= 0 || !G.rows.ub.first.size() || G.rows.vs_long_min != G.rows.ub_min_degree || G.rows.vs_long_min < 17 || G.rows.vs_long_min > 64) return;
   if (const char* e = mgx::env("MGX_SSSP_DENSE")) if (atoi(e) == 0) return;
   standard_context_t& ctx = *g->c->ctx;
   float* w = nullptr;
-  const size_t entries = ((size_t)G.ub_units_pad << 6) + 4;
+  const size_t entries = ((size_t)G.rows.ub.units_pad << 6) + 4;
   if (hipMalloc((void**)&w, entries * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return; }
   G.d_ub_w = mem_t<float>::adopt(w, entries);
   MGX_HIP(hipMemsetAsync(w, 0, entries * sizeof(float), ctx.stream()));
   hipLaunchKernelGGL(mgx::k_sssp_unit_weights, dim3(4096), dim3(mgx::BLOCK), 0, ctx.stream(), G.d_layout_row_offsets.data(),
-                     G.d_layout_col_values.data(), G.d_ub_first.data(), G.num_nodes, w);
+                     G.d_layout_col_values.data(), G.rows.ub.first.data(), G.num_nodes, w);
   MGX_CHECK_LAUNCH("unit-block weights");
   // ... and as halves, for the sweep's packed stream: only with the 24-bit entries, only when every weight survives the round trip
   G.d_ub_w16 = mem_t<unsigned short>();
-  if (G.d_ub_col24.size()) {
+  if (G.rows.ub.col24.size()) {
     mem_t<unsigned short> w16(entries + 8, ctx);
     mem_t<int> exact = mgx::fill<int>(1, 1, ctx);
     hipLaunchKernelGGL(mgx::k_sssp_unit_weights16, dim3(4096), dim3(mgx::BLOCK), 0, ctx.stream(), (const float*)w, (long long)entries, w16.data(), exact.data());
@@ -2161,11 +1973,11 @@ int mgx_sssp_run_delta(mgx_sssp_t p, int src, float delta, int64_t* stats) {
     layout.old_of_new = G.d_old_of_new.data();
     ensure_unit_weights(p->g);
     if (G.d_ub_w.size()) {
-      layout.ub_col = G.d_ub_col.size() ? G.d_ub_col.data() : nullptr; layout.ub_w = G.d_ub_w.data(); layout.ub_cnt = G.d_ub_cnt.data(); layout.ub_owner = G.d_ub_owner.data();
-      if (G.d_ub_col24.size()) layout.ub_col24 = G.d_ub_col24.data();
-      if (G.d_ub_col24.size() && G.d_ub_w16.size()) layout.ub_w16 = G.d_ub_w16.data();
-      layout.ub_units_pad = (unsigned)G.ub_units_pad;
-      for (int i = 0; i < 4; ++i) layout.vs_v[i] = G.vs_v[i];
+      layout.ub_col = G.rows.ub.col.size() ? G.rows.ub.col.data() : nullptr; layout.ub_w = G.d_ub_w.data(); layout.ub_cnt = G.rows.ub.cnt.data(); layout.ub_owner = G.rows.ub.owner.data();
+      if (G.rows.ub.col24.size()) layout.ub_col24 = G.rows.ub.col24.data();
+      if (G.rows.ub.col24.size() && G.d_ub_w16.size()) layout.ub_w16 = G.d_ub_w16.data();
+      layout.ub_units_pad = (unsigned)G.rows.ub.units_pad;
+      for (int i = 0; i < 4; ++i) layout.vs_v[i] = G.rows.vs_v[i];
       layout.m_edges = (long long)G.num_edges;
     }
   }

@@ -10,8 +10,13 @@
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <string>
+
+#include "mgx/row_layout.hpp"
+#include "mgx/wave.hpp"
 
 namespace {
 
@@ -396,6 +401,160 @@ extern "C" int mgx_cold_pack_device(const int* owner, const int* dst, int used, 
   *mask = all & ~badmask;
   return 0;
 }
+
+// ---- the row layout's build steps (mgx/row_layout.hpp) ----------------------------------------------------------------
+// What the fused BFS runs on, built the same way for a graph's hub-first layout and a rank's shard (mgx_capi.hip:
+// mgx_graph_build_layout / mgx_graph_attach_layout, mgx_dbfs2_build_units); each caller brings its own policy as values.
+extern "C" {      // (C linkage: the kernel's symbol is plain `k_pack24`, the name the traces and profiles know it by)
+namespace {
+// four 32-bit entries -> three words of 24-bit entries (little endian: entry k occupies bits [24 k, 24 k + 24) of the 96)
+__global__ __launch_bounds__(256) void k_pack24(const int4* __restrict__ in, long long quads, unsigned* __restrict__ out) {
+  for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (long long)gridDim.x * blockDim.x) {
+    const int4 e = in[q];
+    const unsigned a = (unsigned)e.x & 0xFFFFFFu, b = (unsigned)e.y & 0xFFFFFFu, c = (unsigned)e.z & 0xFFFFFFu, d = (unsigned)e.w & 0xFFFFFFu;
+    out[3 * q + 0] = a | (b << 24);
+    out[3 * q + 1] = (b >> 8) | (c << 16);
+    out[3 * q + 2] = (c >> 16) | (d << 8);
+  }
+}
+}  // namespace
+}  // extern "C"
+
+namespace {
+void throw_hip(const char* what, int rc) {
+  throw mgx::mgx_error(MGX_E_HIP, std::string(what) + hipGetErrorString((hipError_t)rc));
+}
+}  // namespace
+
+namespace mgx {
+
+// unit owners as the builder numbers them (local rows; n_local for padding units) -> global ids (n_global for padding)
+__global__ __launch_bounds__(BLOCK) void k_d2_owner_global(int* __restrict__ owner, long long units_pad, int ranks, int rank, int n_local,
+                                                           int n_global) {
+  const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= units_pad) return;
+  const int o = owner[i];
+  owner[i] = (o >= n_local) ? n_global : o * ranks + rank;
+}
+
+static void remap_owners(int* owner, long long count, const owner_remap_t& r, hipStream_t s) {
+  if (r.ranks <= 0) return;
+  hipLaunchKernelGGL(k_d2_owner_global, dim3((unsigned)((count + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, owner, count, r.ranks, r.rank, r.n_local,
+                     r.n_global);
+}
+
+void build_unit_blocks(unit_blocks_t& ub, const int* ro, const int* ci, int n, int min_deg, unsigned hot_limit, const owner_remap_t& remap,
+                       bool keep_index, hipStream_t s) {
+  ub = unit_blocks_t();
+  int *owner = nullptr, *ucol = nullptr, *ufirst = nullptr;
+  unsigned char* ucnt = nullptr;
+  long long units = 0, units_pad = 0;
+  const int rc = mgx_units_build_device(ro, ci, n, min_deg, 0x7FFFFFFF, 6, hot_limit, &owner, &ucol, &ucnt, &ufirst, &units, &units_pad, s);
+  if (rc != 0) throw_hip(hot_limit ? "unit blocks of the hot entries: " : "unit blocks: ", rc);
+  mem_t<unsigned char> cnt = mem_t<unsigned char>::adopt(ucnt, (size_t)units_pad + 16);
+  mem_t<int> first = mem_t<int>::adopt(ufirst, (size_t)n + 1);
+  if (units <= 0) return;
+  ub.owner = mem_t<int>::adopt(owner, (size_t)units_pad);
+  ub.col = mem_t<int>::adopt(ucol, ((size_t)units_pad << 6) + 4);
+  if (keep_index) { ub.cnt = std::move(cnt); ub.first = std::move(first); }
+  ub.units = units; ub.units_pad = units_pad;
+  remap_owners(ub.owner.data(), units_pad, remap, s);
+}
+
+void pack_unit_blocks24(unit_blocks_t& ub, bool keep_col, hipStream_t s) {
+  // (units_pad * 64 + 4) entries -- the four -1 behind the blocks included -- are whole quads
+  const long long quads = (ub.units_pad << 4) + 1;
+  unsigned* col24 = nullptr;
+  const hipError_t e = hipMalloc((void**)&col24, ((size_t)quads * 3 + 4) * sizeof(unsigned));
+  if (e != hipSuccess) throw_hip("unit blocks, 24-bit copy: ", (int)e);
+  ub.col24 = mem_t<unsigned>::adopt(col24, (size_t)quads * 3 + 4);
+  hipLaunchKernelGGL(k_pack24, dim3(grid_for(quads, 256, 16384)), dim3(256), 0, s, (const int4*)ub.col.data(), quads, ub.col24.data());
+  MGX_HIP(hipStreamSynchronize(s));
+  if (!keep_col) ub.col = mem_t<int>();
+}
+
+unsigned first_row_below(const std::vector<int>& h, size_t n, int d) {
+  size_t lo = 0, hi = n;
+  while (lo < hi) { const size_t mid = (lo + hi) / 2; if (h[mid + 1] - h[mid] >= d) lo = mid + 1; else hi = mid; }
+  return (unsigned)lo;
+}
+
+void cut_degree_classes(row_layout_t& L, const std::vector<int>& h, size_t n, int long_min) {
+  const unsigned b0 = first_row_below(h, n, long_min), b1 = std::max(b0, first_row_below(h, n, 17)), b2 = std::max(b1, first_row_below(h, n, 5)),
+                 b3 = std::max(b2, first_row_below(h, n, 1));
+  L.vs_v[0] = b0; L.vs_v[1] = b1; L.vs_v[2] = b2; L.vs_v[3] = b3;
+  L.vs_v9 = std::min(b2, std::max(b1, first_row_below(h, n, 9)));
+  L.vs_edges = (unsigned)(h[b3] - h[b0]);
+}
+
+long long build_cold_pairs(mem_t<int>& owner, mem_t<int>& dst, std::vector<int>& off, const int* ro, const int* ci, int n, int row0, int rows,
+                           int min_deg, unsigned hot_n, unsigned slice_n, int slices, hipStream_t s, bool tolerate) {
+  owner = mem_t<int>(); dst = mem_t<int>();
+  off.assign((size_t)slices + 1, 0);
+  int *o = nullptr, *d = nullptr;
+  long long pairs = 0;
+  const int rc = mgx_cold_build_device(ro, ci, n, row0, rows, min_deg, hot_n, slice_n, slices, &o, &d, &pairs, off.data(), s);
+  if (rc != 0) {
+    if (!tolerate) throw_hip("cold-edge lists: ", rc);
+    (void)hipGetLastError();
+    return -1;
+  }
+  if (pairs <= 0) return pairs;
+  owner = mem_t<int>::adopt(o, (size_t)pairs + 256); dst = mem_t<int>::adopt(d, (size_t)pairs + 256);
+  return pairs;
+}
+
+bool cut_cold_lists(row_layout_t& L, const std::vector<int>& off_l, const std::vector<int>& off_s, unsigned lo0, unsigned slice_n, long long wgs,
+                    const owner_remap_t& remap, bool pack, hipStream_t s) {
+  // the slices that hold pairs of either list; give up when there are too many of them
+  const int slices = (int)off_l.size() - 1;
+  int used = 0;
+  for (int k = 0; k < slices; ++k) if (off_l[k + 1] > off_l[k] || off_s[k + 1] > off_s[k]) ++used;
+  if (used > row_layout_t::MAX_SLICES) {
+    L.cold_owner = mem_t<int>(); L.cold_dst = mem_t<int>(); L.colds_owner = mem_t<int>(); L.colds_dst = mem_t<int>();
+    L.cold_pairs = L.colds_pairs = 0;
+    return false;
+  }
+  remap_owners(L.cold_owner.data(), L.cold_pairs + 256, remap, s);
+  int q = 0;
+  for (int k = 0; k < slices; ++k) {
+    if (!(off_l[k + 1] > off_l[k] || off_s[k + 1] > off_s[k])) continue;
+    L.cold_lo[q] = lo0 + (unsigned)k * slice_n;
+    L.cold_off[q] = (unsigned)off_l[k]; L.cold_off[q + 1] = (unsigned)off_l[k + 1];
+    L.colds_off[q] = (unsigned)off_s[k]; L.colds_off[q + 1] = (unsigned)off_s[k + 1];
+    ++q;
+  }
+  // workgroups per slice: in proportion to its pairs, at least one each
+  const long long all = L.cold_pairs + L.colds_pairs;
+  const long long nwg = std::max<long long>(wgs, used);
+  unsigned left = (unsigned)nwg - (unsigned)used, acc = 0;
+  L.cold_wgs[0] = 0;
+  for (int i = 0; i < used; ++i) {
+    const long long cnt = ((long long)L.cold_off[i + 1] - (long long)L.cold_off[i]) + ((long long)L.colds_off[i + 1] - (long long)L.colds_off[i]);
+    unsigned extra = (unsigned)((cnt * (long long)((unsigned)nwg - (unsigned)used)) / all);
+    if (extra > left) extra = left;
+    left -= extra;
+    acc += 1u + extra;
+    L.cold_wgs[i + 1] = acc;
+  }
+  for (int i = used + 1; i <= row_layout_t::MAX_SLICES; ++i) { L.cold_wgs[i] = acc; L.cold_off[i] = L.cold_off[used]; L.colds_off[i] = L.colds_off[used]; }
+  L.cold_slices = used;
+  if (!pack) return true;
+  // the long rows' pairs once more, four bytes each (a rank's owners are global ids by now: `ranks` apart inside a list)
+  unsigned *pk = nullptr, *cbase = nullptr;
+  unsigned long long mask = 0;
+  const int rc = mgx_cold_pack_device(L.cold_owner.data(), L.cold_dst.data(), used, L.cold_off, L.cold_lo, remap.ranks > 0 ? remap.ranks : 1, &pk,
+                                      &cbase, L.cold_cb, &mask, s);
+  if (rc != 0) throw_hip("cold-edge lists, packed copy: ", rc);
+  if (pk && cbase) {
+    L.cold_pk = mem_t<unsigned>::adopt(pk, (size_t)L.cold_pairs + 256);
+    L.cold_cbase = mem_t<unsigned>::adopt(cbase, (size_t)L.cold_cb[used] + 64);
+    L.cold_pk_mask = mask;
+  }
+  return true;
+}
+
+}  // namespace mgx
 
 // ---- genuine CSC (transpose) of a device CSR ------------------------------------------------------------------------
 // The reference's loader always ends up with csc == csr (its transposed copy goes into a shadowed local), which
