@@ -42,6 +42,7 @@ typedef struct mgx_bfs_s* mgx_bfs_t;
 typedef struct mgx_sssp_s* mgx_sssp_t;
 typedef struct mgx_pr_s* mgx_pr_t;
 typedef struct mgx_kcore_s* mgx_kcore_t;
+typedef struct mgx_color_s* mgx_color_t;
 typedef struct mgx_dbfs_s* mgx_dbfs_t;
 typedef struct mgx_dbfs2_s* mgx_dbfs2_t;
 typedef struct mgx_dsssp_s* mgx_dsssp_t;
@@ -495,6 +496,26 @@ MGX_API int mgx_kcore_free(mgx_kcore_t p);
 MGX_API int mgx_kcore_enact(mgx_kcore_t p, int* largest_k_core, int64_t* stats);
 MGX_API int mgx_kcore_num_cores(mgx_kcore_t p, int* host_num_cores);       /* extract() :51-53        */
 MGX_API int mgx_kcore_degrees(mgx_kcore_t p, int* host_degrees);           /* the working degrees (<= 0 once a run is over) */
+
+/* ---- graph colouring: coloring_problem_t / coloring_functor.hxx / coloring_enactor_t (gunrock/src/coloring/) ----
+ * Two colours per round from local minima and maxima of a per-round key: salt_i = fmix32(seed + 0x9E3779B9 * (i + 1)),
+ * key_i(v) = fmix32(v ^ salt_i), unsigned.  Round i, every v uncoloured at its start: key_i(v) <= min of its uncoloured
+ * neighbours' keys -> colour 2i + 1, else >= their max -> 2i + 2 (0: uncoloured).  Keys are distinct, so self-loops and parallel
+ * entries change nothing.  Stops after max_iter rounds or when none is left; max_iter <= 0: until none is left (at most
+ * ceil(n / 2) rounds).  Proper on a symmetric graph; a directed one is coloured by its out-rows, not necessarily properly.
+ * Every run starts from all-uncoloured, on the context's stream.  stats (may be NULL): [0] rounds run, [1] vertices left
+ * uncoloured, [2] largest colour (0: none), [3] host waits the run made. */
+MGX_API int mgx_color_create(mgx_graph_t g, mgx_color_t* out);
+MGX_API int mgx_color_free(mgx_color_t p);
+/* the fused path (mgx/color_fused.hpp): one launch per round, rounds enqueued in batches, one host wait per batch */
+MGX_API int mgx_color_run(mgx_color_t p, unsigned seed, int max_iter, int64_t* stats);
+/* the operator path (coloring_enactor.hxx): neighbourhood max / min reduce over the iota frontier, filter over the active */
+MGX_API int mgx_color_enact(mgx_color_t p, unsigned seed, int max_iter, int64_t* stats);
+/* colours of the last run of either path (MGX_E_INVALID before any run); the device pointer stays valid until the next run or free */
+MGX_API int mgx_color_colors(mgx_color_t p, int* host_colors);
+MGX_API int mgx_color_colors_device(mgx_color_t p, const int** d_colors);
+/* active vertices at the start of each round of the last run: *rounds gets the round count, at most cap are written */
+MGX_API int mgx_color_round_trace(mgx_color_t p, int64_t* active_at_round_start, int cap, int* rounds);
 
 /* ---- synthetic input: counter-based R-MAT (the reference ships none, F4) ----
  * Writes edges [first_edge, first_edge+count) of the (scale, seed) stream to device arrays. */

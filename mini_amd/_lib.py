@@ -198,6 +198,13 @@ SIGNATURES = {
     "mgx_kcore_enact": [_vp, _pi, _pi64],
     "mgx_kcore_num_cores": [_vp, _vp],
     "mgx_kcore_degrees": [_vp, _vp],
+    "mgx_color_create": [_vp, _pvp],
+    "mgx_color_free": [_vp],
+    "mgx_color_run": [_vp, C.c_uint, _i, _pi64],
+    "mgx_color_enact": [_vp, C.c_uint, _i, _pi64],
+    "mgx_color_colors": [_vp, _vp],
+    "mgx_color_colors_device": [_vp, _pvp],
+    "mgx_color_round_trace": [_vp, _pi64, _i, _pi],
     "mgx_rmat_edges": [_vp, _i, _i64, _i64, _u64, _i, _vp, _vp, _vp],
 }
 _RESTYPES = {"mgx_comm_library": C.c_char_p, "mgx_strerror": C.c_char_p, "mgx_last_error": C.c_char_p, "mgx_host_free": None}

@@ -2,7 +2,8 @@
 
 Names follow the reference (gunrock/src/*.hxx): Graph ~ graph_device_t, Frontier ~ frontier_t<int>,
 BfsProblem ~ bfs_problem_t + bfs_enactor_t, SsspProblem ~ sssp_problem_t + sssp_enactor_t,
-PrProblem ~ pr_problem_t + pr_enactor_t, KcoreProblem ~ kcore_problem_t + kcore_enactor_t.  Every method is one C-ABI call; nothing is computed here.
+PrProblem ~ pr_problem_t + pr_enactor_t, KcoreProblem ~ kcore_problem_t + kcore_enactor_t,
+ColorProblem ~ coloring_problem_t + coloring_enactor_t.  Every method is one C-ABI call; nothing is computed here.
 """
 import ctypes as C
 
@@ -577,6 +578,59 @@ class KcoreProblem:
     def close(self):
         if self._h:
             lib.mgx_kcore_free(self._h)
+            self._h = None
+
+
+class ColorProblem:
+    """coloring_problem_t + coloring_enactor_t (gunrock/src/coloring/), and the fused path beside them.  Every run starts
+    from all-uncoloured; colors() / round_trace() describe the last run of either path."""
+
+    SEED = 15485863        # the reference driver's defaults (tests/coloring/test_coloring.cu)
+    MAX_ITER = 10
+
+    def __init__(self, graph):
+        h = C.c_void_p()
+        check(lib.mgx_color_create(graph._h, C.byref(h)))
+        self.graph, self._h = graph, h
+
+    @staticmethod
+    def _stats(st):
+        return {"rounds": st[0], "uncolored": st[1], "max_color": st[2], "host_waits": st[3]}
+
+    def run(self, seed=SEED, max_iter=MAX_ITER):
+        """fused path -> {"rounds", "uncolored", "max_color", "host_waits"}; max_iter <= 0: until none is left"""
+        st = (C.c_int64 * 4)()
+        check(lib.mgx_color_run(self._h, C.c_uint(seed & 0xFFFFFFFF), int(max_iter), st))
+        return self._stats(st)
+
+    def enact(self, seed=SEED, max_iter=MAX_ITER):
+        """operator path (neighbourhood reduce + filter); the same stats"""
+        st = (C.c_int64 * 4)()
+        check(lib.mgx_color_enact(self._h, C.c_uint(seed & 0xFFFFFFFF), int(max_iter), st))
+        return self._stats(st)
+
+    def colors(self):
+        out = np.empty(self.graph.num_nodes, dtype=np.int32)
+        check(lib.mgx_color_colors(self._h, _ptr(out)))
+        return out
+
+    @property
+    def colors_device_ptr(self):
+        p = C.c_void_p()
+        check(lib.mgx_color_colors_device(self._h, C.byref(p)))
+        return p.value
+
+    def round_trace(self):
+        """active vertices at the start of every round of the last run (int64 array)"""
+        rounds = C.c_int()
+        check(lib.mgx_color_round_trace(self._h, None, 0, C.byref(rounds)))
+        out = np.zeros(max(rounds.value, 1), dtype=np.int64)
+        check(lib.mgx_color_round_trace(self._h, out.ctypes.data_as(C.POINTER(C.c_int64)), rounds.value, C.byref(rounds)))
+        return out[:rounds.value]
+
+    def close(self):
+        if self._h:
+            lib.mgx_color_free(self._h)
             self._h = None
 
 

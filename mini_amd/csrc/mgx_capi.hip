@@ -9,11 +9,13 @@
 #include <string>
 
 #include "gunrock/bfs/bfs_enactor.hxx"
+#include "gunrock/coloring/coloring_enactor.hxx"
 #include "gunrock/pr/pr_enactor.hxx"
 #include "gunrock/kcore/kcore_enactor.hxx"
 #include "gunrock/sssp/sssp_enactor.hxx"
 #include "mgx/bfs_dist.hpp"
 #include "mgx/bfs_dist2.hpp"
+#include "mgx/color_fused.hpp"
 #include "mgx/env.hpp"
 #include "mgx/sssp_dist.hpp"
 #include "mgx/rmat.hpp"
@@ -69,6 +71,15 @@ struct mgx_kcore_s {
   mgx_graph_t g = nullptr;
   std::shared_ptr<kcore::kcore_problem_t> p;
   std::unique_ptr<kcore::kcore_enactor_t> e;
+};
+
+struct mgx_color_s {
+  mgx_graph_t g = nullptr;
+  std::unique_ptr<mgx::color_fused_state_t> fused;                // lazily: the fused path's O(n) state
+  std::shared_ptr<coloring::coloring_problem_t> p;                // lazily: the operator path's
+  std::unique_ptr<coloring::coloring_enactor_t> e;
+  const int* colors = nullptr;                                    // the last run's colours (nullptr: no run yet)
+  std::vector<long long> trace;                                   // its active vertices per round
 };
 
 struct mgx_dbfs_s {
@@ -2121,6 +2132,83 @@ int mgx_kcore_degrees(mgx_kcore_t p, int* host) {
   use_device(p->g->c);
   p->g->c->ctx->synchronize();
   MGX_HIP(mgx::dtoh(host, p->p->d_degrees.data(), (size_t)p->g->g->num_nodes));
+  MGX_CATCH
+}
+
+
+// ---- graph colouring -------------------------------------------------------------------------
+int mgx_color_create(mgx_graph_t g, mgx_color_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(g && out, "NULL argument");
+  auto* h = new mgx_color_s();
+  h->g = g;
+  *out = h;
+  MGX_CATCH
+}
+int mgx_color_free(mgx_color_t p) {
+  MGX_TRY
+  if (p) { use_device(p->g->c); delete p; }
+  MGX_CATCH
+}
+static void color_stats(int64_t* stats, long long rounds, long long left, long long largest, long long waits) {
+  if (!stats) return;
+  stats[0] = rounds;
+  stats[1] = left;
+  stats[2] = largest;
+  stats[3] = waits;
+}
+int mgx_color_run(mgx_color_t p, unsigned seed, int max_iter, int64_t* stats) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  use_device(p->g->c);
+  standard_context_t& ctx = *p->g->c->ctx;
+  graph_device_t& g = *p->g->g;
+  if (!p->fused) p->fused.reset(new mgx::color_fused_state_t(g.num_nodes, g.num_edges, ctx));
+  p->colors = nullptr;
+  const std::vector<long long> st = p->fused->run(g.d_row_offsets.data(), g.d_col_indices.data(), seed, max_iter, ctx, p->trace);
+  p->colors = p->fused->colour.data();
+  color_stats(stats, st[0], st[1], st[2], st[3]);
+  MGX_CATCH
+}
+int mgx_color_enact(mgx_color_t p, unsigned seed, int max_iter, int64_t* stats) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  use_device(p->g->c);
+  standard_context_t& ctx = *p->g->c->ctx;
+  graph_device_t& g = *p->g->g;
+  if (!p->p) p->p = std::make_shared<coloring::coloring_problem_t>(p->g->g, seed, max_iter, ctx);
+  if (!p->e) p->e.reset(new coloring::coloring_enactor_t(ctx, g.num_nodes, g.num_edges));
+  p->p->seed = seed;
+  p->p->max_iter = max_iter;
+  p->colors = nullptr;
+  p->e->enact(p->p, ctx);
+  ctx.synchronize();
+  p->colors = p->p->d_colors.data();
+  p->trace = p->e->trace;
+  color_stats(stats, p->e->rounds, p->e->left, p->e->largest, p->e->waits);
+  MGX_CATCH
+}
+int mgx_color_colors(mgx_color_t p, int* host) {
+  MGX_TRY
+  MGX_REQUIRE(p && host, "NULL argument");
+  MGX_REQUIRE(p->colors, "mgx_color_colors: no run yet");
+  use_device(p->g->c);
+  p->g->c->ctx->synchronize();
+  MGX_HIP(mgx::dtoh(host, p->colors, (size_t)p->g->g->num_nodes));
+  MGX_CATCH
+}
+int mgx_color_colors_device(mgx_color_t p, const int** out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  MGX_REQUIRE(p->colors, "mgx_color_colors_device: no run yet");
+  *out = p->colors;
+  MGX_CATCH
+}
+int mgx_color_round_trace(mgx_color_t p, int64_t* active_at_round_start, int cap, int* rounds) {
+  MGX_TRY
+  MGX_REQUIRE(p && rounds && (active_at_round_start || cap <= 0), "NULL argument");
+  *rounds = (int)p->trace.size();
+  for (int i = 0; i < cap && i < (int)p->trace.size(); ++i) active_at_round_start[i] = p->trace[i];
   MGX_CATCH
 }
 
