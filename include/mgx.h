@@ -43,6 +43,7 @@ typedef struct mgx_sssp_s* mgx_sssp_t;
 typedef struct mgx_pr_s* mgx_pr_t;
 typedef struct mgx_kcore_s* mgx_kcore_t;
 typedef struct mgx_color_s* mgx_color_t;
+typedef struct mgx_lspar_s* mgx_lspar_t;
 typedef struct mgx_dbfs_s* mgx_dbfs_t;
 typedef struct mgx_dbfs2_s* mgx_dbfs2_t;
 typedef struct mgx_dsssp_s* mgx_dsssp_t;
@@ -516,6 +517,40 @@ MGX_API int mgx_color_colors(mgx_color_t p, int* host_colors);
 MGX_API int mgx_color_colors_device(mgx_color_t p, const int** d_colors);
 /* active vertices at the start of each round of the last run: *rounds gets the round count, at most cap are written */
 MGX_API int mgx_color_round_trace(mgx_color_t p, int64_t* active_at_round_start, int cap, int* rounds);
+
+/* ---- local graph sparsification: lspar_problem_t / lspar_functor.hxx / lspar_enactor_t (gunrock/src/lspar/) ----
+ * One definition, rows read as they stand (duplicates and self-loops count):
+ *   salt_j = fmix32(seed + 0x9E3779B9 * (j + 1)), h_j(u) = fmix32(u ^ salt_j), j = 0 .. k - 1 (colouring's keys)
+ *   mh_j(v) = unsigned min of h_j over the entries of row v (0xFFFFFFFF: empty row)
+ *   sim of entry (v, u) = number of j with mh_j(v) == mh_j(u), 0 .. k
+ *   t(v) = min(d, floor(pow(d, e) * (1 + 2^-40))) in double, d = the row's length
+ *   row v keeps its first t(v) entries in the order (sim descending, position ascending), written in row order.
+ * The result is a CSR of the same n: out_ro (n + 1), out_ci (kept neighbours), out_eid (index into the input col_indices),
+ * out_sim.  k must be 1 .. 32 and e finite and >= 0 (else MGX_E_INVALID before any device work); the reference driver's
+ * defaults are seed 15485863, k = 1, e = 0.5.  Everything runs on the context's stream.  stats (may be NULL): [0] kept
+ * entries, [1] rows cut (t < d), [2] host waits the run made. */
+MGX_API int mgx_lspar_create(mgx_graph_t g, mgx_lspar_t* out);
+MGX_API int mgx_lspar_free(mgx_lspar_t p);
+/* the fused path (mgx/lspar_fused.hpp): a minhash pass and a select pass, one host wait */
+MGX_API int mgx_lspar_run(mgx_lspar_t p, unsigned seed, int k, double e, int64_t* stats);
+/* the operator path (lspar_enactor.hxx): neighbourhood reduce, advance, segmented sort, advance, compaction, segmented sort */
+MGX_API int mgx_lspar_enact(mgx_lspar_t p, unsigned seed, int k, double e, int64_t* stats);
+/* the last run's result (MGX_E_INVALID before any run); NULL skips an array.  Sizes: n + 1 and stats[0] */
+MGX_API int mgx_lspar_result(mgx_lspar_t p, int* h_ro, int* h_ci, int* h_eid, int* h_sim);
+/* the same on the device, valid until the next run or free (NULL skips one) */
+MGX_API int mgx_lspar_result_device(mgx_lspar_t p, const int** d_ro, const int** d_ci, const int** d_eid, const int** d_sim);
+/* the last run's minhash table, n x k, vertex-major */
+MGX_API int mgx_lspar_minhashes(mgx_lspar_t p, unsigned* h_minhashes);
+/* a NEW graph that owns a device copy of the last result (weights: the kept entries' input weights, gathered by eid);
+ * free it with mgx_graph_free */
+MGX_API int mgx_lspar_graph(mgx_lspar_t p, mgx_graph_t* out);
+
+/* ---- segmented sort (mgpu::segmented_sort, lspar_enactor.hxx:85; mgx/segsort.hpp) ----
+ * Sorts d_keys[0, count) (and d_vals with them; NULL: keys only) in place, stably, ascending or descending, within segments:
+ * d_segments holds num_segments heads, ascending, duplicates allowed; whatever lies before the first head is a segment too,
+ * the last ends at count.  On the context's stream; returns when the sort is done. */
+MGX_API int mgx_segmented_sort_i32(mgx_ctx_t ctx, int* d_keys, int* d_vals, int64_t count, const int* d_segments, int num_segments,
+                                   int descending);
 
 /* ---- synthetic input: counter-based R-MAT (the reference ships none, F4) ----
  * Writes edges [first_edge, first_edge+count) of the (scale, seed) stream to device arrays. */

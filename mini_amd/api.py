@@ -3,7 +3,7 @@
 Names follow the reference (gunrock/src/*.hxx): Graph ~ graph_device_t, Frontier ~ frontier_t<int>,
 BfsProblem ~ bfs_problem_t + bfs_enactor_t, SsspProblem ~ sssp_problem_t + sssp_enactor_t,
 PrProblem ~ pr_problem_t + pr_enactor_t, KcoreProblem ~ kcore_problem_t + kcore_enactor_t,
-ColorProblem ~ coloring_problem_t + coloring_enactor_t.  Every method is one C-ABI call; nothing is computed here.
+ColorProblem ~ coloring_problem_t + coloring_enactor_t, LsparProblem ~ lspar_problem_t + lspar_enactor_t.  Every method is one C-ABI call; nothing is computed here.
 """
 import ctypes as C
 
@@ -634,11 +634,83 @@ class ColorProblem:
             self._h = None
 
 
+class LsparProblem:
+    """lspar_problem_t + lspar_enactor_t (gunrock/src/lspar/), and the fused path beside them.  result() / minhashes() /
+    graph() describe the last run of either path; `source` is the input graph."""
+
+    SEED = 15485863        # the reference driver's defaults
+    K = 1
+    E = 0.5
+
+    def __init__(self, graph):
+        h = C.c_void_p()
+        check(lib.mgx_lspar_create(graph._h, C.byref(h)))
+        self.source, self._h = graph, h
+        self._kept, self._k = None, None
+
+    def _go(self, fn, seed, k, e):
+        st = (C.c_int64 * 3)()
+        self._kept = None
+        check(fn(self._h, C.c_uint(seed & 0xFFFFFFFF), int(k), float(e), st))
+        self._kept, self._k = st[0], int(k)
+        return {"kept": st[0], "rows_cut": st[1], "host_waits": st[2]}
+
+    def run(self, seed=SEED, k=K, e=E):
+        """fused path -> {"kept", "rows_cut", "host_waits"}"""
+        return self._go(lib.mgx_lspar_run, seed, k, e)
+
+    def enact(self, seed=SEED, k=K, e=E):
+        """operator path (neighbourhood reduce, advance, segmented sort, advance, compaction, segmented sort); the same stats"""
+        return self._go(lib.mgx_lspar_enact, seed, k, e)
+
+    def result(self):
+        """(out_ro int32[n + 1], out_ci, out_eid, out_sim int32[kept])"""
+        if self._kept is None:
+            check(lib.mgx_lspar_result(self._h, None, None, None, None))       # raises: no run yet
+        n, m = self.source.num_nodes, self._kept
+        ro = np.empty(n + 1, dtype=np.int32)
+        ci, eid, sim = (np.empty(max(m, 1), dtype=np.int32) for _ in range(3))
+        check(lib.mgx_lspar_result(self._h, _ptr(ro), _ptr(ci), _ptr(eid), _ptr(sim)))
+        return ro, ci[:m], eid[:m], sim[:m]
+
+    def result_device_ptrs(self):
+        p = [C.c_void_p() for _ in range(4)]
+        check(lib.mgx_lspar_result_device(self._h, *(C.byref(x) for x in p)))
+        return tuple(x.value for x in p)
+
+    def minhashes(self):
+        """(n, k) uint32, vertex-major"""
+        if self._kept is None:
+            check(lib.mgx_lspar_minhashes(self._h, None))                      # raises
+        out = np.empty((self.source.num_nodes, self._k), dtype=np.uint32)
+        check(lib.mgx_lspar_minhashes(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def graph(self):
+        """a new Graph owning a device copy of the last result"""
+        h = C.c_void_p()
+        check(lib.mgx_lspar_graph(self._h, C.byref(h)))
+        return Graph(self.source.ctx, h)
+
+    def close(self):
+        if self._h:
+            lib.mgx_lspar_free(self._h)
+            self._h = None
+
+
 # building blocks ------------------------------------------------------------------------------
 def scan_exclusive_i32(ctx, d_in, n, d_out):
     v = _i64()
     check(lib.mgx_scan_exclusive_i32(ctx._h, _dev_ptr(d_in), int(n), _dev_ptr(d_out), C.byref(v)))
     return v.value
+
+
+def segmented_sort(ctx, keys, segments, values=None, descending=False):
+    """mgpu::segmented_sort on int32 device tensors, in place on the context's stream: stable within the segments whose heads
+    `segments` lists (ascending; what lies before the first head is a segment too).  Returns (keys, values)."""
+    check(lib.mgx_segmented_sort_i32(ctx._h, _dev_ptr(keys), _dev_ptr(values), int(keys.numel()), _dev_ptr(segments),
+                                     int(segments.numel()), int(bool(descending))))
+    return keys, values
 
 
 def scan_frontier_degrees(graph, frontier, use_csc=False):

@@ -10,12 +10,14 @@
 
 #include "gunrock/bfs/bfs_enactor.hxx"
 #include "gunrock/coloring/coloring_enactor.hxx"
+#include "gunrock/lspar/lspar_enactor.hxx"
 #include "gunrock/pr/pr_enactor.hxx"
 #include "gunrock/kcore/kcore_enactor.hxx"
 #include "gunrock/sssp/sssp_enactor.hxx"
 #include "mgx/bfs_dist.hpp"
 #include "mgx/bfs_dist2.hpp"
 #include "mgx/color_fused.hpp"
+#include "mgx/lspar_fused.hpp"
 #include "mgx/env.hpp"
 #include "mgx/sssp_dist.hpp"
 #include "mgx/rmat.hpp"
@@ -80,6 +82,21 @@ struct mgx_color_s {
   std::unique_ptr<coloring::coloring_enactor_t> e;
   const int* colors = nullptr;                                    // the last run's colours (nullptr: no run yet)
   std::vector<long long> trace;                                   // its active vertices per round
+};
+
+struct mgx_lspar_s {
+  mgx_graph_t g = nullptr;
+  std::unique_ptr<mgx::lspar_fused_state_t> fused;                // lazily: the fused path's state
+  std::shared_ptr<lspar::lspar_problem_t> p;                      // lazily: the operator path's
+  std::unique_ptr<lspar::lspar_enactor_t> e;
+  // the last run's result (ro == nullptr: no run yet) and minhash table (n x mh_stride, k columns used)
+  const int* ro = nullptr;
+  const int* ci = nullptr;
+  const int* eid = nullptr;
+  const int* sim = nullptr;
+  const unsigned* mh = nullptr;
+  int mh_stride = 0, k = 0;
+  long long kept = 0;
 };
 
 struct mgx_dbfs_s {
@@ -2209,6 +2226,161 @@ int mgx_color_round_trace(mgx_color_t p, int64_t* active_at_round_start, int cap
   MGX_REQUIRE(p && rounds && (active_at_round_start || cap <= 0), "NULL argument");
   *rounds = (int)p->trace.size();
   for (int i = 0; i < cap && i < (int)p->trace.size(); ++i) active_at_round_start[i] = p->trace[i];
+  MGX_CATCH
+}
+
+
+// ---- local graph sparsification ----------------------------------------------------------------
+int mgx_lspar_create(mgx_graph_t g, mgx_lspar_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(g && out, "NULL argument");
+  auto* h = new mgx_lspar_s();
+  h->g = g;
+  *out = h;
+  MGX_CATCH
+}
+int mgx_lspar_free(mgx_lspar_t p) {
+  MGX_TRY
+  if (p) { use_device(p->g->c); delete p; }
+  MGX_CATCH
+}
+static void lspar_check_params(int k, double e) {
+  MGX_REQUIRE(k >= 1 && k <= mgx::LSPAR_K_MAX, "lspar: k must be 1 .. 32");
+  MGX_REQUIRE(std::isfinite(e) && e >= 0.0, "lspar: e must be finite and >= 0");
+}
+static void lspar_stats(int64_t* stats, long long kept, long long cut, long long waits) {
+  if (!stats) return;
+  stats[0] = kept;
+  stats[1] = cut;
+  stats[2] = waits;
+}
+int mgx_lspar_run(mgx_lspar_t p, unsigned seed, int k, double e, int64_t* stats) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  lspar_check_params(k, e);
+  use_device(p->g->c);
+  standard_context_t& ctx = *p->g->c->ctx;
+  graph_device_t& g = *p->g->g;
+  if (!p->fused) p->fused.reset(new mgx::lspar_fused_state_t(g.num_nodes, g.num_edges, ctx));
+  p->ro = nullptr;
+  const std::vector<long long> st = p->fused->run(g.d_row_offsets.data(), g.d_col_indices.data(), seed, k, e, ctx);
+  mgx::lspar_fused_state_t& f = *p->fused;
+  p->ro = f.oro.data(); p->ci = f.oci.data(); p->eid = f.oeid.data(); p->sim = f.osim.data();
+  p->mh = f.mh.data(); p->mh_stride = f.S; p->k = k; p->kept = st[0];
+  lspar_stats(stats, st[0], st[1], st[2]);
+  MGX_CATCH
+}
+int mgx_lspar_enact(mgx_lspar_t p, unsigned seed, int k, double e, int64_t* stats) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  lspar_check_params(k, e);
+  use_device(p->g->c);
+  standard_context_t& ctx = *p->g->c->ctx;
+  graph_device_t& g = *p->g->g;
+  if (!p->p) p->p = std::make_shared<lspar::lspar_problem_t>(p->g->g, seed, k, e, ctx);
+  else p->p->reset(seed, k, e, ctx);
+  if (!p->e) p->e.reset(new lspar::lspar_enactor_t(ctx, g.num_nodes, g.num_edges));
+  p->ro = nullptr;
+  p->e->enact(p->p, ctx);
+  ctx.synchronize();
+  lspar::lspar_enactor_t& E = *p->e;
+  p->ro = E.d_out_ro.data(); p->ci = E.d_out_ci.data(); p->eid = E.d_out_eid.data(); p->sim = E.d_out_sim.data();
+  p->mh = p->p->d_minwise_hashs.data(); p->mh_stride = k; p->k = k; p->kept = E.kept;
+  lspar_stats(stats, E.kept, E.cut, E.waits);
+  MGX_CATCH
+}
+int mgx_lspar_result(mgx_lspar_t p, int* h_ro, int* h_ci, int* h_eid, int* h_sim) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  MGX_REQUIRE(p->ro, "mgx_lspar_result: no run yet");
+  use_device(p->g->c);
+  p->g->c->ctx->synchronize();
+  const size_t n = (size_t)p->g->g->num_nodes, m = (size_t)p->kept;
+  if (h_ro) MGX_HIP(mgx::dtoh(h_ro, p->ro, n + 1));
+  if (m) {
+    if (h_ci) MGX_HIP(mgx::dtoh(h_ci, p->ci, m));
+    if (h_eid) MGX_HIP(mgx::dtoh(h_eid, p->eid, m));
+    if (h_sim) MGX_HIP(mgx::dtoh(h_sim, p->sim, m));
+  }
+  MGX_CATCH
+}
+int mgx_lspar_result_device(mgx_lspar_t p, const int** d_ro, const int** d_ci, const int** d_eid, const int** d_sim) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  MGX_REQUIRE(p->ro, "mgx_lspar_result_device: no run yet");
+  if (d_ro) *d_ro = p->ro;
+  if (d_ci) *d_ci = p->ci;
+  if (d_eid) *d_eid = p->eid;
+  if (d_sim) *d_sim = p->sim;
+  MGX_CATCH
+}
+int mgx_lspar_minhashes(mgx_lspar_t p, unsigned* h) {
+  MGX_TRY
+  MGX_REQUIRE(p && h, "NULL argument");
+  MGX_REQUIRE(p->ro, "mgx_lspar_minhashes: no run yet");
+  use_device(p->g->c);
+  p->g->c->ctx->synchronize();
+  const size_t n = (size_t)p->g->g->num_nodes;
+  if (n)
+    MGX_HIP(hipMemcpy2D(h, (size_t)p->k * sizeof(unsigned), p->mh, (size_t)p->mh_stride * sizeof(unsigned), (size_t)p->k * sizeof(unsigned),
+                        n, hipMemcpyDeviceToHost));
+  MGX_CATCH
+}
+int mgx_lspar_graph(mgx_lspar_t p, mgx_graph_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  MGX_REQUIRE(p->ro, "mgx_lspar_graph: no run yet");
+  mgx_ctx_s* const c = p->g->c;
+  use_device(c);
+  standard_context_t& ctx = *c->ctx;
+  const graph_device_t& in = *p->g->g;
+  const int n = in.num_nodes;
+  const long long m = p->kept;
+  auto g = std::make_shared<graph_device_t>();
+  g->num_nodes = n;
+  g->num_edges = (int)m;
+  g->d_row_offsets = mem_t<int>((size_t)n + 1, ctx);
+  MGX_HIP(mgx::dtod(g->d_row_offsets.data(), p->ro, (size_t)n + 1, ctx.stream()));
+  g->d_col_indices = mem_t<int>((size_t)m, ctx);
+  g->d_col_values = mem_t<float>((size_t)m, ctx);
+  if (m) {
+    MGX_HIP(mgx::dtod(g->d_col_indices.data(), p->ci, (size_t)m, ctx.stream()));
+    const float* const w = in.d_col_values.data();
+    const int* const eid = p->eid;
+    float* const kw = g->d_col_values.data();
+    transform([=] __device__(int i) { kw[i] = w[eid[i]]; }, m, ctx);
+  }
+  g->d_col_offsets = mem_t<int>::borrow(g->d_row_offsets.data(), g->d_row_offsets.size());
+  g->d_row_indices = mem_t<int>::borrow(g->d_col_indices.data(), g->d_col_indices.size());
+  g->d_row_values = mem_t<float>::borrow(g->d_col_values.data(), g->d_col_values.size());
+  g->csc_is_csr = true;
+  finish_graph(c, *g);
+  ctx.synchronize();
+  auto* h = new mgx_graph_s();
+  h->c = c;
+  h->g = g;
+  *out = h;
+  MGX_CATCH
+}
+
+// ---- segmented sort ----------------------------------------------------------------------------
+int mgx_segmented_sort_i32(mgx_ctx_t c, int* d_keys, int* d_vals, int64_t count, const int* d_segments, int num_segments,
+                           int descending) {
+  MGX_TRY
+  MGX_REQUIRE(c && (d_keys || count == 0) && (d_segments || num_segments == 0) && count >= 0 && num_segments >= 0,
+              "mgx_segmented_sort_i32: bad argument");
+  MGX_REQUIRE(count <= 2147483647LL, "mgx_segmented_sort_i32: count must fit int32");
+  use_device(c);
+  standard_context_t& ctx = *c->ctx;
+  auto up = [] __device__(int a, int b) { return a < b; };
+  auto down = [] __device__(int a, int b) { return a > b; };
+  if (d_vals) {
+    if (descending) mgx::segmented_sort(d_keys, d_vals, count, d_segments, num_segments, down, ctx);
+    else mgx::segmented_sort(d_keys, d_vals, count, d_segments, num_segments, up, ctx);
+  } else {
+    if (descending) mgx::segmented_sort(d_keys, count, d_segments, num_segments, down, ctx);
+    else mgx::segmented_sort(d_keys, count, d_segments, num_segments, up, ctx);
+  }
   MGX_CATCH
 }
 
