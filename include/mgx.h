@@ -44,6 +44,7 @@ typedef struct mgx_pr_s* mgx_pr_t;
 typedef struct mgx_kcore_s* mgx_kcore_t;
 typedef struct mgx_color_s* mgx_color_t;
 typedef struct mgx_lspar_s* mgx_lspar_t;
+typedef struct mgx_cc_s* mgx_cc_t;
 typedef struct mgx_dbfs_s* mgx_dbfs_t;
 typedef struct mgx_dbfs2_s* mgx_dbfs2_t;
 typedef struct mgx_dsssp_s* mgx_dsssp_t;
@@ -544,6 +545,26 @@ MGX_API int mgx_lspar_minhashes(mgx_lspar_t p, unsigned* h_minhashes);
 /* a NEW graph that owns a device copy of the last result (weights: the kept entries' input weights, gathered by eid);
  * free it with mgx_graph_free */
 MGX_API int mgx_lspar_graph(mgx_lspar_t p, mgx_graph_t* out);
+
+/* ---- connected components ----
+ * Weakly connected components: every CSR entry (v, u) is read as the undirected pair {v, u}; self-loops and duplicate entries
+ * change nothing, a vertex without entries is a component of its own.  label[v] = the smallest vertex id of v's component, in
+ * original ids (an attached hub-first layout is ignored).  stats (may be NULL): [0] components (v with label[v] == v), [1] size of
+ * the largest, [2] its label (on a tie in size, the smallest label), [3] vertices whose rows the fused final pass skipped (always
+ * 0 on the operator path), [4] host waits the run made.  Every run starts afresh, on the context's stream. */
+MGX_API int mgx_cc_create(mgx_graph_t g, mgx_cc_t* out);
+MGX_API int mgx_cc_free(mgx_cc_t p);
+/* the fused path (mgx/cc_fused.hpp): Afforest-style union-find, one host wait.  symmetric != 0 is the caller's word that every
+ * entry has its reverse: the labels are right on a symmetric graph; on a directed one only with symmetric = 0, which is right on
+ * any graph (the final pass then uses the graph's genuine CSC if it has one, else skips nothing).  seed picks the 1024 sampled
+ * vertices; the labels do not depend on it.  stats[3]: vertices in the sampled largest set after the two neighbour rounds that
+ * had entries left to link (out-entries from the third on, or in-entries of the genuine CSC) */
+MGX_API int mgx_cc_run(mgx_cc_t p, int symmetric, unsigned seed, int64_t* stats);
+/* the operator path (include/gunrock/cc/): Shiloach-Vishkin hook advances and pointer-jumping filters; right on any graph */
+MGX_API int mgx_cc_enact(mgx_cc_t p, int64_t* stats);
+/* labels of the last run of either path (MGX_E_INVALID before any run); the device pointer stays valid until the next run or free */
+MGX_API int mgx_cc_labels(mgx_cc_t p, int* host_labels);
+MGX_API int mgx_cc_labels_device(mgx_cc_t p, const int** d_labels);
 
 /* ---- segmented sort (mgpu::segmented_sort, lspar_enactor.hxx:85; mgx/segsort.hpp) ----
  * Sorts d_keys[0, count) (and d_vals with them; NULL: keys only) in place, stably, ascending or descending, within segments:

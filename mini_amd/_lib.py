@@ -214,6 +214,12 @@ SIGNATURES = {
     "mgx_lspar_minhashes": [_vp, _vp],
     "mgx_lspar_graph": [_vp, _pvp],
     "mgx_segmented_sort_i32": [_vp, _vp, _vp, _i64, _vp, _i, _i],
+    "mgx_cc_create": [_vp, _pvp],
+    "mgx_cc_free": [_vp],
+    "mgx_cc_run": [_vp, _i, C.c_uint, _pi64],
+    "mgx_cc_enact": [_vp, _pi64],
+    "mgx_cc_labels": [_vp, _vp],
+    "mgx_cc_labels_device": [_vp, _pvp],
     "mgx_rmat_edges": [_vp, _i, _i64, _i64, _u64, _i, _vp, _vp, _vp],
 }
 _RESTYPES = {"mgx_comm_library": C.c_char_p, "mgx_strerror": C.c_char_p, "mgx_last_error": C.c_char_p, "mgx_host_free": None}

@@ -3,7 +3,8 @@
 Names follow the reference (gunrock/src/*.hxx): Graph ~ graph_device_t, Frontier ~ frontier_t<int>,
 BfsProblem ~ bfs_problem_t + bfs_enactor_t, SsspProblem ~ sssp_problem_t + sssp_enactor_t,
 PrProblem ~ pr_problem_t + pr_enactor_t, KcoreProblem ~ kcore_problem_t + kcore_enactor_t,
-ColorProblem ~ coloring_problem_t + coloring_enactor_t, LsparProblem ~ lspar_problem_t + lspar_enactor_t.  Every method is one C-ABI call; nothing is computed here.
+ColorProblem ~ coloring_problem_t + coloring_enactor_t, LsparProblem ~ lspar_problem_t + lspar_enactor_t,
+CcProblem ~ cc_problem_t + cc_enactor_t.  Every method is one C-ABI call; nothing is computed here.
 """
 import ctypes as C
 
@@ -695,6 +696,50 @@ class LsparProblem:
     def close(self):
         if self._h:
             lib.mgx_lspar_free(self._h)
+            self._h = None
+
+
+class CcProblem:
+    """Connected components: cc_problem_t + cc_enactor_t, and the fused path beside them.  labels() describes the last
+    run of either path: label[v] = the smallest vertex id of v's weakly connected component."""
+
+    SEED = 15485863
+
+    def __init__(self, graph):
+        h = C.c_void_p()
+        check(lib.mgx_cc_create(graph._h, C.byref(h)))
+        self.graph, self._h = graph, h
+
+    @staticmethod
+    def _stats(st):
+        return {"components": st[0], "largest": st[1], "largest_label": st[2], "skipped": st[3], "host_waits": st[4]}
+
+    def run(self, symmetric=False, seed=SEED):
+        """fused path -> {"components", "largest", "largest_label", "skipped", "host_waits"}.  symmetric=True is the caller's word
+        that every entry has its reverse (the final pass then skips the sampled largest set); False is right on any graph."""
+        st = (C.c_int64 * 5)()
+        check(lib.mgx_cc_run(self._h, int(bool(symmetric)), C.c_uint(seed & 0xFFFFFFFF), st))
+        return self._stats(st)
+
+    def enact(self):
+        """operator path (hook advances, pointer-jumping filters); the same stats, skipped = 0"""
+        st = (C.c_int64 * 5)()
+        check(lib.mgx_cc_enact(self._h, st))
+        return self._stats(st)
+
+    def labels(self):
+        out = np.empty(self.graph.num_nodes, dtype=np.int32)
+        check(lib.mgx_cc_labels(self._h, _ptr(out)))
+        return out
+
+    def labels_device_ptr(self):
+        p = C.c_void_p()
+        check(lib.mgx_cc_labels_device(self._h, C.byref(p)))
+        return p.value
+
+    def close(self):
+        if self._h:
+            lib.mgx_cc_free(self._h)
             self._h = None
 
 

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "gunrock/bfs/bfs_enactor.hxx"
+#include "gunrock/cc/cc_enactor.hxx"
 #include "gunrock/coloring/coloring_enactor.hxx"
 #include "gunrock/lspar/lspar_enactor.hxx"
 #include "gunrock/pr/pr_enactor.hxx"
@@ -16,6 +17,7 @@
 #include "gunrock/sssp/sssp_enactor.hxx"
 #include "mgx/bfs_dist.hpp"
 #include "mgx/bfs_dist2.hpp"
+#include "mgx/cc_fused.hpp"
 #include "mgx/color_fused.hpp"
 #include "mgx/lspar_fused.hpp"
 #include "mgx/env.hpp"
@@ -97,6 +99,15 @@ struct mgx_lspar_s {
   const unsigned* mh = nullptr;
   int mh_stride = 0, k = 0;
   long long kept = 0;
+};
+
+struct mgx_cc_s {
+  mgx_graph_t g = nullptr;
+  std::unique_ptr<mgx::cc_fused_state_t> fused;                   // lazily: the fused path's O(n + m / 32) state
+  std::shared_ptr<cc::cc_problem_t> p;                            // lazily: the operator path's
+  std::unique_ptr<cc::cc_enactor_t> e;
+  std::unique_ptr<mgx::cc_label_stats_t> label_stats;             // lazily: the operator path's stats
+  const int* labels = nullptr;                                    // the last run's labels (nullptr: no run yet)
 };
 
 struct mgx_dbfs_s {
@@ -2381,6 +2392,77 @@ int mgx_segmented_sort_i32(mgx_ctx_t c, int* d_keys, int* d_vals, int64_t count,
     if (descending) mgx::segmented_sort(d_keys, count, d_segments, num_segments, down, ctx);
     else mgx::segmented_sort(d_keys, count, d_segments, num_segments, up, ctx);
   }
+  MGX_CATCH
+}
+
+
+// ---- connected components ----------------------------------------------------------------------
+int mgx_cc_create(mgx_graph_t g, mgx_cc_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(g && out, "NULL argument");
+  auto* h = new mgx_cc_s();
+  h->g = g;
+  *out = h;
+  MGX_CATCH
+}
+int mgx_cc_free(mgx_cc_t p) {
+  MGX_TRY
+  if (p) { use_device(p->g->c); delete p; }
+  MGX_CATCH
+}
+static void cc_stats(int64_t* stats, const std::vector<long long>& s, long long skipped, long long waits) {
+  if (!stats) return;
+  stats[0] = s[0];
+  stats[1] = s[1];
+  stats[2] = s[2];
+  stats[3] = skipped;
+  stats[4] = waits;
+}
+int mgx_cc_run(mgx_cc_t p, int symmetric, unsigned seed, int64_t* stats) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  use_device(p->g->c);
+  standard_context_t& ctx = *p->g->c->ctx;
+  graph_device_t& g = *p->g->g;
+  if (!p->fused) p->fused.reset(new mgx::cc_fused_state_t(g.num_nodes, g.num_edges, ctx));
+  p->labels = nullptr;
+  const bool csc = !g.csc_is_csr;
+  const std::vector<long long> st = p->fused->run(g.d_row_offsets.data(), g.d_col_indices.data(), csc ? g.d_col_offsets.data() : nullptr,
+                                                  csc ? g.d_row_indices.data() : nullptr, symmetric != 0, seed, ctx);
+  p->labels = p->fused->comp.data();
+  cc_stats(stats, st, st[3], st[4]);
+  MGX_CATCH
+}
+int mgx_cc_enact(mgx_cc_t p, int64_t* stats) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  use_device(p->g->c);
+  standard_context_t& ctx = *p->g->c->ctx;
+  graph_device_t& g = *p->g->g;
+  if (!p->p) p->p = std::make_shared<cc::cc_problem_t>(p->g->g, ctx);
+  if (!p->e) p->e.reset(new cc::cc_enactor_t(ctx, g.num_nodes, g.num_edges));
+  if (!p->label_stats) p->label_stats.reset(new mgx::cc_label_stats_t(g.num_nodes, ctx));
+  p->labels = nullptr;
+  p->e->enact(p->p, ctx);
+  const std::vector<long long> st = p->label_stats->run(p->p->d_comp.data(), g.num_nodes, ctx);
+  p->labels = p->p->d_comp.data();
+  cc_stats(stats, st, 0, p->e->waits + 1);
+  MGX_CATCH
+}
+int mgx_cc_labels(mgx_cc_t p, int* host) {
+  MGX_TRY
+  MGX_REQUIRE(p && host, "NULL argument");
+  MGX_REQUIRE(p->labels, "mgx_cc_labels: no run yet");
+  use_device(p->g->c);
+  p->g->c->ctx->synchronize();
+  MGX_HIP(mgx::dtoh(host, p->labels, (size_t)p->g->g->num_nodes));
+  MGX_CATCH
+}
+int mgx_cc_labels_device(mgx_cc_t p, const int** out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  MGX_REQUIRE(p->labels, "mgx_cc_labels_device: no run yet");
+  *out = p->labels;
   MGX_CATCH
 }
 
