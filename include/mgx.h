@@ -496,6 +496,18 @@ MGX_API int mgx_kcore_free(mgx_kcore_t p);
  * entries, an upstream quirk that is kept).  stats[0] = k values tried, [1] = passes, [2] = entries expanded,
  * [3] = vertices removed (stats may be NULL).  The run consumes the working degrees: mgx_kcore_reset before another one. */
 MGX_API int mgx_kcore_enact(mgx_kcore_t p, int* largest_k_core, int64_t* stats);
+/* the fused path (mgx/kcore_fused.hpp): the same peeling as worklists -- a pass looks only at the vertices whose degree the
+ * pass before took below k, and the next k is 1 + the smallest positive working degree.  Core numbers, working degrees and
+ * *largest_k_core equal mgx_kcore_enact's on every graph (stranded vertices and the k <= n cap included), on the
+ * plain CSR in original ids.  It starts afresh by itself, on the context's stream: no mgx_kcore_reset before or after, and it may
+ * follow an enact directly.  stats (may be NULL): [0] levels (values of k at which somebody left), [1] removing passes,
+ * [2] entries expanded, [3] vertices removed, [4] stranded vertices (degree from >= k to <= 0 within one pass: core 0),
+ * [5] host waits.  Against mgx_kcore_enact's stats e: [1] = e[1] - e[0], [2] = e[2], [3] = e[3]. */
+MGX_API int mgx_kcore_run(mgx_kcore_t p, int* largest_k_core, int64_t* stats);
+/* what every launch of the last fused run was, in order (for joining a kernel trace with the run's steps): 1 smallest degree,
+ * 2 list the level's first front, 3 expand, 4 filter, 6 one workgroup's own passes on a small front, 5 behind the end.
+ * *launches: how many the run enqueued; min(*launches, cap, 65536) kinds are written.  MGX_E_INVALID before any fused run. */
+MGX_API int mgx_kcore_step_kinds(mgx_kcore_t p, int* host_kinds, int cap, int64_t* launches);
 MGX_API int mgx_kcore_num_cores(mgx_kcore_t p, int* host_num_cores);       /* extract() :51-53        */
 MGX_API int mgx_kcore_degrees(mgx_kcore_t p, int* host_degrees);           /* the working degrees (<= 0 once a run is over) */
 

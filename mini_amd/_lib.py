@@ -196,6 +196,8 @@ SIGNATURES = {
     "mgx_kcore_reset": [_vp],
     "mgx_kcore_free": [_vp],
     "mgx_kcore_enact": [_vp, _pi, _pi64],
+    "mgx_kcore_run": [_vp, _pi, _pi64],
+    "mgx_kcore_step_kinds": [_vp, _vp, C.c_int, _pi64],
     "mgx_kcore_num_cores": [_vp, _vp],
     "mgx_kcore_degrees": [_vp, _vp],
     "mgx_color_create": [_vp, _pvp],

@@ -566,6 +566,24 @@ class KcoreProblem:
         check(lib.mgx_kcore_enact(self._h, C.byref(largest), st))
         return largest.value, {"rounds": st[0], "passes": st[1], "expanded": st[2], "removed": st[3]}
 
+    def run(self):
+        """The fused path (worklist peeling): the same core numbers, degrees and largest k-core as enact(), from a fresh start
+        of its own (no reset() needed).  -> (largest_k_core, {"levels", "passes", "expanded", "removed", "stranded", "host_waits"})"""
+        largest = C.c_int()
+        st = (C.c_int64 * 6)()
+        check(lib.mgx_kcore_run(self._h, C.byref(largest), st))
+        return largest.value, {"levels": st[0], "passes": st[1], "expanded": st[2], "removed": st[3], "stranded": st[4],
+                               "host_waits": st[5]}
+
+    STEP_KINDS = {1: "min", 2: "list", 3: "expand", 4: "filter", 5: "idle", 6: "mini"}
+
+    def step_kinds(self):
+        """what every launch of the last run() was, in order (the first 65536): codes of STEP_KINDS"""
+        n = C.c_int64()
+        out = np.empty(1 << 16, dtype=np.int32)
+        check(lib.mgx_kcore_step_kinds(self._h, _ptr(out), len(out), C.byref(n)))
+        return out[:min(n.value, len(out))].copy()
+
     def num_cores(self):
         out = np.empty(self.graph.num_nodes, dtype=np.int32)
         check(lib.mgx_kcore_num_cores(self._h, _ptr(out)))

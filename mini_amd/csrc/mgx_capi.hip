@@ -18,6 +18,7 @@
 #include "mgx/bfs_dist.hpp"
 #include "mgx/bfs_dist2.hpp"
 #include "mgx/cc_fused.hpp"
+#include "mgx/kcore_fused.hpp"
 #include "mgx/color_fused.hpp"
 #include "mgx/lspar_fused.hpp"
 #include "mgx/env.hpp"
@@ -75,6 +76,7 @@ struct mgx_kcore_s {
   mgx_graph_t g = nullptr;
   std::shared_ptr<kcore::kcore_problem_t> p;
   std::unique_ptr<kcore::kcore_enactor_t> e;
+  std::unique_ptr<mgx::kcore_fused_state_t> fused;                // lazily: the fused path's worklists and state words
 };
 
 struct mgx_color_s {
@@ -2144,6 +2146,34 @@ int mgx_kcore_enact(mgx_kcore_t p, int* largest_k_core, int64_t* stats) {
     stats[2] = p->e->expanded;
     stats[3] = p->e->removed;
   }
+  MGX_CATCH
+}
+int mgx_kcore_run(mgx_kcore_t p, int* largest_k_core, int64_t* stats) {
+  MGX_TRY
+  MGX_REQUIRE(p && largest_k_core, "NULL argument");
+  use_device(p->g->c);
+  standard_context_t& ctx = *p->g->c->ctx;
+  graph_device_t& g = *p->g->g;
+  if (!p->fused) p->fused.reset(new mgx::kcore_fused_state_t(g.num_nodes, g.num_edges, ctx));
+  p->p->reset(ctx);                               // every run starts afresh: core numbers 0, degrees = row lengths
+  int largest = -1;
+  const std::vector<long long> st = p->fused->run(g.d_row_offsets.data(), g.d_col_indices.data(), p->p->d_degrees.data(),
+                                                  p->p->d_num_cores.data(), ctx, largest);
+  p->p->largest_k_core = largest;
+  *largest_k_core = largest;
+  if (stats)
+    for (int j = 0; j < 6; ++j) stats[j] = st[(size_t)j];
+  MGX_CATCH
+}
+int mgx_kcore_step_kinds(mgx_kcore_t p, int* host_kinds, int cap, int64_t* launches) {
+  MGX_TRY
+  MGX_REQUIRE(p && launches && cap >= 0 && (host_kinds || cap == 0), "bad argument");
+  MGX_REQUIRE(p->fused, "mgx_kcore_step_kinds: no fused run yet");
+  use_device(p->g->c);
+  p->g->c->ctx->synchronize();
+  *launches = p->fused->launches;
+  const long long have = std::min<long long>(std::min<long long>(p->fused->launches, mgx::KCORE_LOG_CAP), cap);
+  MGX_HIP(mgx::dtoh(host_kinds, p->fused->ctl.data()->log, (size_t)have));
   MGX_CATCH
 }
 int mgx_kcore_num_cores(mgx_kcore_t p, int* host) {

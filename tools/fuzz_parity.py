@@ -250,6 +250,12 @@ for name, n, ro, ci, w in graphs():
         largest, kst = kc.enact()
         wc, wl = orc.kcore_cpu(ro, ci)
         assert largest == wl and np.array_equal(kc.num_cores(), wc), (name, n, "k-core", largest, wl)
+        # ... and the fused path (worklist peeling) against the operator path: degrees and stats too.  It starts afresh by itself
+        edeg = kc.degrees()
+        flargest, fst = kc.run()
+        assert flargest == largest and np.array_equal(kc.num_cores(), wc) and np.array_equal(kc.degrees(), edeg), (name, n, "fused k-core")
+        assert fst["passes"] == kst["passes"] - kst["rounds"] and fst["expanded"] == kst["expanded"] and fst["removed"] == kst["removed"], \
+            (name, n, "fused k-core stats", fst, kst)
         kc.close()
     ran += 1
     print("ok %-18s n=%-7d m=%-9d layout=%d" % (name, n, len(ci), layout), flush=True)
