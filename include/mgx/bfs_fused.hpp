@@ -43,6 +43,7 @@
 #pragma once
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 
 #include "runtime.hpp"
 #include "env.hpp"
@@ -337,21 +338,24 @@ __device__ __forceinline__ void bfs_seed_queue(const bfs_fused_args_t& a, u32 ro
 // Start of a traversal, one launch: clears labels (-1), bitmap(s) and marks, and seeds the source.  The thread that
 // clears the element holding the source's label / bit writes the seed value instead, so there is no ordering
 // between workgroups to worry about.
-// prev_ctrl / prev_head (batches of sources, bfs_fused_run_many): the head of the control block as the PREVIOUS traversal of
-// the batch left it goes to (pinned) host memory first -- by the workgroup whose thread 0 then resets it; nobody else
+// prev_ctrl / prev_head (batches of sources, bfs_fused_run_many): the head of the control block as the traversal that used
+// this state BEFORE left it goes to (pinned) host memory first -- by the workgroup whose thread 0 then resets it; nobody else
 // touches the block here.
-__global__ __launch_bounds__(BLOCK) void k_bfs_fused_init(bfs_fused_args_t a, int src, long long nwords, const bfs_ctrl_t* prev_ctrl,
-                                                          bfs_ctrl_t* prev_head, int head_words) {
-  if (prev_head && blockIdx.x == 0) {
+// The body as a device function, block `blk` of `nblk` blocks of NT threads: a launch of its own (k_bfs_fused_init) or one
+// role of a seam launch of a batch (bfs_fused_run.hpp), where the grid holds another traversal's workgroups too.
+template <int NT>
+__device__ __forceinline__ void bfs_init_body(const bfs_fused_args_t& a, int src, long long nwords, const bfs_ctrl_t* prev_ctrl,
+                                              bfs_ctrl_t* prev_head, int head_words, u32 blk, u32 nblk) {
+  if (prev_head && blk == 0) {
     const u32* const from = (const u32*)prev_ctrl;
     u32* const to = (u32*)prev_head;
-    for (int i = threadIdx.x; i < head_words; i += BLOCK) to[i] = from[i];
+    for (int i = threadIdx.x; i < head_words; i += NT) to[i] = from[i];
     __syncthreads();
   }
   const int src_old = src;
   if (a.new_of_old) src = a.new_of_old[src];           // labels live in ORIGINAL id space, everything else in layout space
-  const long long tid = (long long)blockIdx.x * BLOCK + threadIdx.x;
-  const long long nth = (long long)gridDim.x * BLOCK;
+  const long long tid = (long long)blk * NT + threadIdx.x;
+  const long long nth = (long long)nblk * NT;
   const long long n = a.n;
   for (long long i = tid; i < (n + 3) / 4; i += nth) {              // 4 labels / 4 marks per step
     if (i * 4 + 4 <= n) {
@@ -376,6 +380,10 @@ __global__ __launch_bounds__(BLOCK) void k_bfs_fused_init(bfs_fused_args_t a, in
     bfs_slot_marks_clear(a, 1);
     bfs_seed_queue(a, (u32)src);
   }
+}
+__global__ __launch_bounds__(BLOCK) void k_bfs_fused_init(bfs_fused_args_t a, int src, long long nwords, const bfs_ctrl_t* prev_ctrl,
+                                                          bfs_ctrl_t* prev_head, int head_words) {
+  bfs_init_body<BLOCK>(a, src, nwords, prev_ctrl, prev_head, head_words, blockIdx.x, gridDim.x);
 }
 
 // Opening a level (one thread): termination flag, trace, TEPS numerator, direction decision.  Returns false when
@@ -1113,6 +1121,19 @@ __global__ void k_bfs_publish(const bfs_ctrl_t* __restrict__ c, bfs_ctrl_t* __re
   if (threadIdx.x == 0) __hip_atomic_store(host_seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// ... of a batch whose traversals alternate between two states (bfs_fused_run_many): the heads of the last TWO traversals, each
+// from the control block of its own state (every earlier one was copied by the init that reset its state).
+__global__ void k_bfs_publish2(const bfs_ctrl_t* __restrict__ c0, bfs_ctrl_t* __restrict__ host0, const bfs_ctrl_t* __restrict__ c1,
+                               bfs_ctrl_t* __restrict__ host1, u64* host_seq, u64 seq, int words) {
+  for (int i = threadIdx.x; i < words; i += blockDim.x) {
+    ((u32*)host0)[i] = ((const u32*)c0)[i];
+    ((u32*)host1)[i] = ((const u32*)c1)[i];
+  }
+  __threadfence_system();
+  __syncthreads();
+  if (threadIdx.x == 0) __hip_atomic_store(host_seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // Tuning switches of the fused traversal, read from the environment ONCE per handle (when its state is made -- the
 // parity tests set them and then create the problem), never per traversal or per launch.  Every one of them selects
 // between product paths that the default thresholds pick by size; the shapes that lost their A/B runs and the
@@ -1145,6 +1166,8 @@ struct bfs_run_opts_t {
   int build_list = 0;      // MGX_BFS_BUILD_LIST=1: the list-based queue build (k_bfs_build) instead of k_bfs_build2
   int mini = 1;            // MGX_BFS_MINI=0: no M launches (mid-size levels take device-wide slots; bfs_fused_mini.hpp); 1: on graphs of at
                            // least 2^22 vertices; 2: always
+  int batch_overlap = 1;   // MGX_BFS_BATCH_OVERLAP=0: a batch (mgx_bfs_run_many) runs every traversal in the handle's one state, its launches strictly
+                           // one after the other (default: two states, the tail launches of a traversal share a launch with the head of the next)
   int many_spare = 0;      // (no switch since round 6: re-runs teach the handle, auto_spare) launch slots a traversal of a batch (mgx_bfs_run_many) gets beyond what the last
                            // traversals of the graph needed (the most any of the last four needed: one that still does not finish is run
                            // again on its own, and the chain behind a traversal's last slot takes stragglers of up to BFS_CHAIN_CAP_BIG edges)
@@ -1183,6 +1206,7 @@ struct bfs_run_opts_t {
     geti("MGX_BFS_TAIL_FRONT", o.tail_front);
     geti("MGX_BFS_CHAIN_BIG_EDGES", o.chain_big);
     geti("MGX_BFS_MINI", o.mini);
+    geti("MGX_BFS_BATCH_OVERLAP", o.batch_overlap);
     if (o.many_spare < 0) o.many_spare = 0;
     geti("MGX_BFS_LAZY", o.lazy);
     if (o.lazy > (1 << 20)) o.lazy = 1 << 20;     // (edges < 2^38: no overflow)
@@ -1193,6 +1217,43 @@ struct bfs_run_opts_t {
 #else
 #endif
     return o;
+  }
+};
+
+// The SECOND traversal state of a handle (batches of sources, bfs_fused_run_many): everything a traversal writes and that its head
+// or tail launches touch -- control block, bitmaps, marks, the four queue pairs, the mark counters and a label array of its own.
+// Allocated at the first batch of two or more sources.  (The flush buffers of the deferred marks and of the cold-edge pass stay
+// single: only device-wide slots use them, and device-wide slots of two traversals never overlap.)
+struct bfs_alt_state_t {
+  mem_t<char> pool;                  // ONE allocation (a batch makes it while the device works: every call counts), carved into:
+  u32 *visited = nullptr, *frontier_bits = nullptr;
+  unsigned char* mark = nullptr;
+  u32 *fr_row[2] = {}, *fr_off[2] = {}, *lq_row[2] = {}, *lq_off[2] = {};
+  bfs_ctrl_t* ctrl = nullptr;
+  u32* slot_marks = nullptr;
+  int* labels = nullptr;
+  // NULL when the device has no room for it (37 bytes per vertex): the caller goes on with the one state it has
+  static std::unique_ptr<bfs_alt_state_t> make(int num_nodes, size_t words, standard_context_t& ctx) {
+    std::unique_ptr<bfs_alt_state_t> t(new bfs_alt_state_t());
+    const size_t n = (size_t)num_nodes;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t off = at; at += (bytes + 255) & ~(size_t)255; return off; };
+    const size_t o_vis = take(words * 4), o_fb = take(words * 4), o_mark = take(n + 64), o_ctrl = take(sizeof(bfs_ctrl_t)),
+                 o_sm = take((size_t)2 * BFS_MARK_CTRS * BFS_MARK_STRIDE * 4), o_lab = take((n + 4) * 4);
+    size_t o_q[8];
+    for (int i = 0; i < 8; ++i) o_q[i] = take((n + 1) * 4);
+    char* b = nullptr;
+    if (hipMalloc((void**)&b, at) != hipSuccess || !b) { (void)hipGetLastError(); return nullptr; }
+    t->pool = mem_t<char>::adopt(b, at);
+    t->visited = (u32*)(b + o_vis); t->frontier_bits = (u32*)(b + o_fb); t->mark = (unsigned char*)(b + o_mark);
+    t->ctrl = (bfs_ctrl_t*)(b + o_ctrl); t->slot_marks = (u32*)(b + o_sm); t->labels = (int*)(b + o_lab);
+    for (int i = 0; i < 2; ++i) {
+      t->fr_row[i] = (u32*)(b + o_q[i]); t->fr_off[i] = (u32*)(b + o_q[2 + i]);
+      t->lq_row[i] = (u32*)(b + o_q[4 + i]); t->lq_off[i] = (u32*)(b + o_q[6 + i]);
+    }
+    // (the two bitmaps lie next to each other: one fill -- the kernels copy a fixed-size prefix into LDS, behind the words an init writes)
+    MGX_HIP(hipMemsetAsync(t->visited, 0, o_mark - o_vis, ctx.stream()));
+    return t;
   }
 };
 
@@ -1235,6 +1296,8 @@ struct bfs_fused_state_t {
   unsigned lazy_div = 4;             // the build behind a push with >= n / lazy_div mark stores writes no queues (bfs_build_is_lazy; 0: never)
   mem_t<u32> slot_marks;             // the counters it looks at (bfs_fused_args_t::slot_marks)
   mem_t<u32> cold_flush;             // cold-edge pass: one bitmap of BFS_COLD_WORDS words per cold workgroup (allocated on demand)
+  std::unique_ptr<bfs_alt_state_t> alt;   // the second traversal state (batches of sources; allocated on demand)
+  bool alt_refused = false;               // ... the device had no room for it: the handle's batches stay in one state
   unsigned dense_div = 2;            // long rows are read from the unit blocks when the frontier holds at least
                                      // 1 / dense_div of the units (bfs_fused_dense.hpp; 0: never)
   int long_min = LONG_MIN_DEFAULT;   // rows at least this long go to the long-row queue (0: no such queue)

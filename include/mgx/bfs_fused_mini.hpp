@@ -47,8 +47,11 @@ __device__ __forceinline__ bool bfs_level_is_mini(const bfs_fused_args_t& a, con
          E <= (u64)(late ? BFS_MINI_EDGES_LATE : BFS_MINI_EDGES_EARLY);
 }
 
+// The launch's body as a device function: workgroup `blk` of the `nblk` workgroups that run THIS launch's level -- the whole grid of
+// k_bfs_mini, or the first BFS_MINI_WGS workgroups of a seam launch of a batch (bfs_fused_run.hpp: the rest of that grid belongs to
+// another traversal).  The shares and the forwarding path's "last workgroup through" count by nblk, never by the grid.
 template <int NT>
-__global__ __launch_bounds__(NT) void k_bfs_mini(bfs_fused_args_t a, int arg) {
+__device__ __forceinline__ void bfs_mini_body(const bfs_fused_args_t& a, int arg, u32 blk, u32 nblk) {
   constexpr int NW = NT / WAVE;
   constexpr u64 CNT1 = 1ull << 40;
   constexpr u64 DEGMASK = CNT1 - 1ull;
@@ -69,7 +72,7 @@ __global__ __launch_bounds__(NT) void k_bfs_mini(bfs_fused_args_t a, int arg) {
   const int nf_s = (int)(cur >> BFS_VSHIFT), nf_l = (int)(lcur >> BFS_VSHIFT);
   const u32 Es = (u32)(cur & BFS_EMASK), Rl = (u32)(lcur & BFS_EMASK);
   const int in = slot & 1, out = (slot + 1) & 1;
-  const bool first_thread = blockIdx.x == 0 && threadIdx.x == 0;
+  const bool first_thread = blk == 0 && threadIdx.x == 0;
   // NOTHING a workgroup bases its decisions on below (ring entry slot % 3, lazy_slot, reached, done, mode) is written by
   // this launch before every workgroup has made them: the bookkeeping touches the NEXT slot's entries only, discoveries
   // count into reached_mini, and a forwarded level's flags move when the last workgroup is through.
@@ -81,7 +84,7 @@ __global__ __launch_bounds__(NT) void k_bfs_mini(bfs_fused_args_t a, int arg) {
     }
     return;
   }
-  const long long gtid = (long long)blockIdx.x * NT + threadIdx.x, gthreads = (long long)gridDim.x * NT;
+  const long long gtid = (long long)blk * NT + threadIdx.x, gthreads = (long long)nblk * NT;
   if (!bfs_level_is_mini(a, c, slot)) {
     // ---- forward: the level moves to slot + 1 as it is ------------------------------------------------------------
     const bool lazy = c->lazy_slot == slot;
@@ -93,7 +96,7 @@ __global__ __launch_bounds__(NT) void k_bfs_mini(bfs_fused_args_t a, int arg) {
     __syncthreads();
     if (threadIdx.x == 0) {
       __threadfence();
-      if (atomicAdd(&c->mini_blocks[slot & 3], 1u) == gridDim.x - 1u) {       // the last workgroup through: everybody has decided (and copied)
+      if (atomicAdd(&c->mini_blocks[slot & 3], 1u) == nblk - 1u) {       // the last workgroup through: everybody has decided (and copied)
         c->mini_blocks[slot & 3] = 0u;
         c->cursor[(slot + 1) % 3] = cur; c->lcursor[(slot + 1) % 3] = lcur; c->ledges[(slot + 1) % 3] = ledges;
         c->cursor[(slot + 2) % 3] = 0; c->lcursor[(slot + 2) % 3] = 0; c->ledges[(slot + 2) % 3] = 0;
@@ -203,7 +206,7 @@ __global__ __launch_bounds__(NT) void k_bfs_mini(bfs_fused_args_t a, int arg) {
   // ---- long rows: 64-edge units (the queue's offsets count padded degrees), equal shares per wave -----------------------
   {
     const u32 U = Rl >> 6;
-    const u32 Wt = (u32)gridDim.x * NW, w0 = (u32)blockIdx.x * NW + (u32)wave;
+    const u32 Wt = nblk * NW, w0 = blk * NW + (u32)wave;
     const u32 iters = (U + Wt - 1u) / Wt;                  // (grid-uniform)
     for (u32 t = 0; t < iters; ++t) {
       const u32 u = w0 + t * Wt;
@@ -288,6 +291,10 @@ __global__ __launch_bounds__(NT) void k_bfs_mini(bfs_fused_args_t a, int arg) {
   flush();
   found = (int)wave_sum((u32)found);
   if (lane == 0 && found) atomicAdd(&c->reached_mini, (u64)found);
+}
+template <int NT>
+__global__ __launch_bounds__(NT) void k_bfs_mini(bfs_fused_args_t a, int arg) {
+  bfs_mini_body<NT>(a, arg, blockIdx.x, gridDim.x);
 }
 
 }  // namespace mgx

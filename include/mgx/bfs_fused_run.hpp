@@ -8,6 +8,7 @@
 // ctrl->slot_level[slot & 3].  RMAT-22: init + chain + 4 slots + chain + publish = 12 launches for 7 levels.
 // The partitioned path (bfs_dist2.hpp) drives the queue-walk bodies with explicit level numbers (k_bfs_push_level).
 #pragma once
+#include <cassert>
 #include <cstring>
 #include <vector>
 #include <unistd.h>
@@ -194,7 +195,7 @@ __global__ __launch_bounds__(1024, 8) void k_bfs_push(bfs_fused_args_t a, int ar
 //     chain_big_edges edges run here, back to back, and the traversal ends without another slot.
 // The first level that is not small is left in the SAME slot's queues (bfs_chain_body<., true, .>): the slot's push
 // launch opens it.  Nothing to do (a big level, an empty or lazy slot, the traversal over): returns at once (~2.5 us).
-__global__ __launch_bounds__(1024) void k_bfs_chain_inplace(bfs_fused_args_t a, int arg) {
+__device__ __forceinline__ void bfs_chain_inplace_body(const bfs_fused_args_t& a, int arg) {
   const bfs_ctrl_t* const c = a.ctrl;
   int slot, level;
   bfs_resolve(c, arg, slot, level);
@@ -203,6 +204,43 @@ __global__ __launch_bounds__(1024) void k_bfs_chain_inplace(bfs_fused_args_t a, 
   if (c->lazy_slot == slot) return;                                  // (the build before wrote no queues: nothing to stage in)
   if (!bfs_level_is_chained(a, cur, lcur, c->ledges[slot % 3], a.chain_big_edges, BFS_CHAIN_CAP_BIG)) return;
   bfs_chain_body<1024, true, BFS_CHAIN_CAP_BIG>(a, slot, level);
+}
+__global__ __launch_bounds__(1024) void k_bfs_chain_inplace(bfs_fused_args_t a, int arg) {
+  bfs_chain_inplace_body(a, arg);
+}
+
+// The SEAM between two traversals of a batch (bfs_fused_run_many): traversal A ends with [M][chain], traversal B begins with
+// [init][chain][M] -- five launches of one to 64 workgroups (or a 21 MB fill), strictly one after the other, 37-47 us of RMAT-22's
+// 305 per traversal, although A's two and B's first two have nothing to do with each other once the two traversals live in
+// two STATES (bfs_alt_state_t).  Here they pair up INSIDE a launch: a workgroup takes one role by its block index, on its own
+// traversal's arguments; the two roles share no memory that either writes and never wait for each other -- no flags, no spins, no
+// fences between them, so a seam launch can hang no more than the launches it replaces.  The launch boundaries in front of and behind
+// it order each role against its own traversal's neighbours exactly as before.
+//   k_bfs_seam_mini_init    [A: the M launch behind the slots, BFS_MINI_WGS workgroups][B: init, the rest of the grid]
+//   k_bfs_seam_chain_chain  [A: the chain behind that, one workgroup][B: the chain at the start, one workgroup]
+//   k_bfs_seam_chain_init   (plans without M launches) [A: the chain behind the slots][B: init]; B's chain is a launch of its own
+// B's init resets the state that the traversal BEFORE A used and copies that one's head out first (init.prev_ctrl == B's own control
+// block): a launch boundary lies between that traversal's last write and this read.  A's head is NOT copied here -- the launch is
+// still working on it.
+struct bfs_seam_init_t {
+  long long nwords;
+  const bfs_ctrl_t* prev_ctrl;
+  bfs_ctrl_t* prev_head;
+  int src, head_words;
+};
+static_assert(2 * sizeof(bfs_fused_args_t) + sizeof(bfs_seam_init_t) + 64 <= 4096, "a seam launch's two argument structs fit the 4 KB of kernel arguments");
+__global__ __launch_bounds__(1024) void k_bfs_seam_mini_init(bfs_fused_args_t a, int arg_a, bfs_fused_args_t b, bfs_seam_init_t init) {
+  if (blockIdx.x < (u32)BFS_MINI_WGS) bfs_mini_body<1024>(a, arg_a, blockIdx.x, (u32)BFS_MINI_WGS);
+  else bfs_init_body<1024>(b, init.src, init.nwords, init.prev_ctrl, init.prev_head, init.head_words, blockIdx.x - (u32)BFS_MINI_WGS,
+                           gridDim.x - (u32)BFS_MINI_WGS);
+}
+__global__ __launch_bounds__(1024) void k_bfs_seam_chain_chain(bfs_fused_args_t a, int arg_a, bfs_fused_args_t b, int arg_b) {
+  if (blockIdx.x == 0) bfs_chain_inplace_body(a, arg_a);
+  else bfs_chain_inplace_body(b, arg_b);
+}
+__global__ __launch_bounds__(1024) void k_bfs_seam_chain_init(bfs_fused_args_t a, int arg_a, bfs_fused_args_t b, bfs_seam_init_t init) {
+  if (blockIdx.x == 0) bfs_chain_inplace_body(a, arg_a);
+  else bfs_init_body<1024>(b, init.src, init.nwords, init.prev_ctrl, init.prev_head, init.head_words, blockIdx.x - 1u, gridDim.x - 1u);
 }
 
 #ifdef MGX_LAB
@@ -282,6 +320,9 @@ inline void bfs_set_kernel_attributes() {
   MGX_SET_LDS(k_bfs_push_stream_diag);
 #endif
   MGX_SET_LDS(k_bfs_chain_inplace);
+  MGX_SET_LDS(k_bfs_seam_chain_chain);
+  MGX_SET_LDS(k_bfs_seam_chain_init);
+  MGX_HIP(hipFuncSetAttribute((const void*)k_bfs_seam_mini_init, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bfs_mini_lds_bytes()));
   // (k_bfs_mini has static LDS too: the attribute carries what it needs, not the whole 160 KB)
   MGX_HIP(hipFuncSetAttribute((const void*)k_bfs_mini<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bfs_mini_lds_bytes()));
   MGX_SET_LDS(k_bfs_push_level<false>);
@@ -557,6 +598,61 @@ inline int bfs_enqueue_start(const bfs_fused_state_t& st, const bfs_launch_plan_
   if (plan.minis && front_mini) { bfs_enqueue_mini(plan, 0, s); return 1; }
   return 0;
 }
+// the plan of a handle's SECOND state: the same inputs, the other state's arrays (allocated at the first batch that asks).
+// false: the device has no room for a second state (remembered: later batches do not ask again)
+inline bool bfs_fused_plan_alt(bfs_fused_state_t& st, const bfs_launch_plan_t& plan, standard_context_t& ctx, bfs_launch_plan_t& p) {
+  if (!st.alt && !st.alt_refused) {
+    st.alt = bfs_alt_state_t::make(st.n, st.bitmap_words(), ctx);
+    st.alt_refused = !st.alt;
+  }
+  if (!st.alt) return false;
+  bfs_alt_state_t& t = *st.alt;
+  p = plan;
+  bfs_fused_args_t& a = p.a;
+  a.labels = p.labels = t.labels;
+  a.visited = t.visited;
+  a.mark = t.mark;
+  a.frontier_bits = t.frontier_bits;
+  for (int i = 0; i < 2; ++i) {
+    a.fr_row[i] = t.fr_row[i]; a.fr_off[i] = t.fr_off[i];
+    a.lq_row[i] = t.lq_row[i]; a.lq_off[i] = t.lq_off[i];
+  }
+  a.ctrl = t.ctrl;
+  a.slot_marks = t.slot_marks;
+  return true;
+}
+// The seam launches of a batch (see k_bfs_seam_mini_init): traversal A's tail -- its M launch in slot `sl_a` (plans with M launches)
+// and the chain behind it, with the list capacity as its limit (tail_a) -- paired with the init and the first chain of traversal B,
+// which starts from `src` in the other state.  prev_head: where the head of the traversal that used B's state before goes (NULL: none did).
+inline void bfs_enqueue_seam(const bfs_fused_state_t& st, const bfs_launch_plan_t& plan_a, const bfs_launch_plan_t& tail_a, int sl_a,
+                             const bfs_launch_plan_t& plan_b, int src, bfs_ctrl_t* prev_head, int head_words, standard_context_t& ctx) {
+  hipStream_t s = ctx.stream();
+  bfs_seam_init_t init;
+  init.nwords = plan_b.nwords;
+  init.prev_ctrl = plan_b.a.ctrl;
+  init.prev_head = prev_head;
+  init.src = src;
+  init.head_words = head_words;
+  const int want = grid_for(((long long)st.n + 3) / 4, 1024, 1 << 20);       // init workgroups of 1024 threads, four labels a thread
+  if (plan_a.minis) {
+    // one workgroup of this launch per CU (the M body's registers): the init role gets the CUs the M role leaves, so that the whole
+    // grid is resident at once -- 192 workgroups of 1024 threads stream RMAT-22's 21 MB in the time the 64 M workgroups need anyway
+    int ninit = ctx.num_cus - BFS_MINI_WGS;
+    if (ninit < 64) ninit = 64;
+    if (ninit > want) ninit = want;
+    hipLaunchKernelGGL(k_bfs_seam_mini_init, dim3(BFS_MINI_WGS + ninit), dim3(1024), bfs_mini_lds_bytes(), s, plan_a.a, bfs_slot_arg(sl_a),
+                       plan_b.a, init);
+    hipLaunchKernelGGL(k_bfs_seam_chain_chain, dim3(2), dim3(1024), bfs_chain_lds_bytes(BFS_CHAIN_CAP_BIG), s, tail_a.a, bfs_slot_arg(sl_a + 1),
+                       plan_b.a, bfs_slot_arg(0));
+  } else {
+    int ninit = ctx.num_cus - 1;                                              // (the chain's LDS: one workgroup per CU)
+    if (ninit < 16) ninit = 16;
+    if (ninit > want) ninit = want;
+    hipLaunchKernelGGL(k_bfs_seam_chain_init, dim3(1 + ninit), dim3(1024), bfs_chain_lds_bytes(BFS_CHAIN_CAP_BIG), s, tail_a.a, bfs_slot_arg(sl_a),
+                       plan_b.a, init);
+    bfs_enqueue_chain_inplace(plan_b, 0, s);
+  }
+}
 inline void bfs_enqueue_build(const bfs_fused_state_t& st, const bfs_launch_plan_t& plan, int arg, hipStream_t s) {
   if (st.opts.build_list || !plan.build2_ok)
     hipLaunchKernelGGL((k_bfs_build<512, true>), dim3(bfs_build_grid(st.n, 512)), dim3(512), 0, s, plan.a, arg,
@@ -787,7 +883,8 @@ inline void bfs_fused_run(bfs_fused_state_t& st, const int* row_offsets, const i
 // look in between, so the ~18 us between the publish of one traversal and the first kernel of the next (the host's
 // wake-up, the call, the first launch) and the publish kernel itself disappear.  Each traversal gets the slots the last
 // traversals of the graph needed plus one; the head of its control block is copied to heads[i] by the NEXT traversal's
-// init kernel (the last one's by k_bfs_publish).  A traversal that did not finish within its slots (a source with an
+// init kernel (the last one's by k_bfs_publish) -- with two states (below): by the init of the next traversal in the SAME state, the last
+// two by k_bfs_publish2.  A traversal that did not finish within its slots (a source with an
 // unusual level structure) is run again on its own afterwards -- then the last source too, so that labels[] always holds
 // the LAST source's traversal when the call returns.  heads: pinned host memory, bfs_many_head_bytes() apart.
 constexpr size_t bfs_head_bytes() { return offsetof(bfs_ctrl_t, trace) + 64 * sizeof(u64); }
@@ -820,6 +917,11 @@ inline bfs_ctrl_t* bfs_many_head(char* heads, int i) { return (bfs_ctrl_t*)(head
 //     round-robin to XCDs and shader engines whatever the mask left of each: 14 of 496 workgroups start a whole workgroup run
 //     late (tools/cumask_probe2.hip), which doubles a launch of equal static shares; a symmetric reservation costs 32 CUs.
 //     (profiles/r03/lanes_and_cu_masks.txt)
+// What differs in the shape that stayed (two states on ONE stream, k_bfs_seam_*): none of the three above ever put two small launches
+// side by side -- each put a small launch beside a device-wide one, across streams, at ~6 us per event.  Here A's [M][chain] and B's
+// [init][chain] pair up inside two launches, a role per workgroup: nothing device-wide runs beside them, there is no event and no
+// wait, and B's device-wide slots still start only when A is complete.  Measured: HISTORY.md, "Batched BFS" (the seam between two
+// traversals 41 -> 32 us; short of the 3 % of a traversal it was built for: what is left of a seam is B's own three dependent launches).
 inline int bfs_fused_run_many(bfs_fused_state_t& st, const int* row_offsets, const int* col_indices, int* labels,
                               const int* srcs, int count, standard_context_t& ctx, char* heads, const bfs_layout_t* layout = nullptr,
                               int mode = 0, float alpha = 0.f, const int* in_offsets = nullptr, const int* in_indices = nullptr) {
@@ -856,32 +958,77 @@ inline int bfs_fused_run_many(bfs_fused_state_t& st, const int* row_offsets, con
     return 0;
   }
   if (nslots < 1) nslots = 1;
-  const int saved_tail = st.tail_from;
+  struct tail_guard_t {            // st.tail_from is the batch's own while it is enqueued: the handle's comes back on every way out
+    int& at; const int saved; bool armed;
+    void release() { if (armed) { at = saved; armed = false; } }
+    ~tail_guard_t() { release(); }
+  } tail_guard{st.tail_from, st.tail_from, true};
   st.tail_from = plan.minis ? (1 << 30) : nslots - 1;      // (no M launches: a chain launch in front of the last slot and behind the batch)
   const bool tail = a.chain_big_edges && st.opts.tail_chain;
   std::vector<int> last_slots((size_t)count, nslots), classes((size_t)count, BFS_SRC_UNKNOWN);   // per traversal: the slot the chain behind it works in (where an unfinished one stands), its class
   // the chain behind a traversal's last slot may run levels up to the list capacity here (a lone workgroup needs ~4.3 us per
   // 1000 edges: slower than a slot above ~4000 edges, but far cheaper than running the whole traversal again)
-  bfs_launch_plan_t plan_tail = plan;
-  plan_tail.a.chain_big_edges = BFS_CHAIN_CAP_BIG;
+  // Two states (MGX_BFS_BATCH_OVERLAP, default on; top-down batches with both chain launches): traversal i runs in state
+  // (count - 1 - i) & 1 -- the LAST one in state 0, whose label array is the caller's -- and where two neighbours run in different
+  // states the tail launches of the first share their launches with the head of the second (bfs_enqueue_seam).  Every traversal
+  // still writes all of its labels, an odd one into the second state's array, which nobody reads -- as before, where the next
+  // traversal overwrote them.
+  // The handle's FIRST such batch allocates the second state -- behind the device-wide launches of its first two traversals, which run in
+  // state 0 one after the other as ever: the device is busy with them while the host allocates (RMAT-22: 156 MB), and the batch
+  // alternates from there.
+  // A device without room for the second state: the batch goes on in state 0 alone, as under MGX_BFS_BATCH_OVERLAP=0.
+  bool overlap = st.opts.batch_overlap != 0 && mode == 0 && count >= 2 && tail && !st.alt_refused;
+  const int lead = (overlap && !st.alt) ? (count - 1 < 2 ? count - 1 : 2) : 0;
+  bfs_launch_plan_t plans[2] = {plan, plan}, tails[2];
+  for (int k = 0; k < 2; ++k) { tails[k] = plans[k]; tails[k].a.chain_big_edges = BFS_CHAIN_CAP_BIG; }
+  auto second_state = [&]() {      // plans[1] / tails[1] on the second state's arrays; no such state: one state from here on
+    if (!bfs_fused_plan_alt(st, plan, ctx, plans[1])) { overlap = false; return; }
+    tails[1] = plans[1]; tails[1].a.chain_big_edges = BFS_CHAIN_CAP_BIG;
+  };
+  if (overlap && st.alt) second_state();
+  // (asked about traversals >= lead only once `overlap` is settled: a refused allocation clears it before anybody asks about traversal `lead`)
+  auto state_of = [&](int i) { return (overlap && i >= lead) ? ((count - 1 - i) & 1) : 0; };
+  int pending[2] = {-1, -1};       // per state: the traversal that ran in it last -- its head is still in the state's control block
   for (int i = 0; i < count; ++i) {
-    // (the head of the control block as the previous traversal left it goes to the host before the init kernel resets it)
     // (per source: which of the launches in front of the device-wide slots will find work, and how many slots its class needs)
     const int cls = bfs_classify_source(st, plan, layout, srcs[i], i);
     int my_slots = cls == BFS_SRC_UNKNOWN ? nslots : bfs_class_slots(st, cls) + st.opts.many_spare + st.auto_spare;
     if (my_slots > 30) my_slots = 30;
     if (my_slots < 1) my_slots = 1;
-    int sl = bfs_enqueue_start(st, plan, srcs[i], ctx, i > 0 ? st.ctrl.data() : (const bfs_ctrl_t*)nullptr,
-                               i > 0 ? bfs_many_head(heads, i - 1) : (bfs_ctrl_t*)nullptr, head_words, cls != BFS_SRC_SKIP);
-    for (int k = 0; k < my_slots; ++k, ++sl) bfs_enqueue_slot(st, plan, sl, ctx);
-    if (plan.minis) { bfs_enqueue_mini(plan, sl, s); ++sl; }
-    if (tail) bfs_enqueue_chain_inplace(plan_tail, sl, s);
+    const int me = state_of(i);
+    const bfs_launch_plan_t& P = plans[me];
+    // (the head of the control block as the last traversal in this state left it goes to the host before the init resets it)
+    bfs_ctrl_t* const prev_head = pending[me] >= 0 ? bfs_many_head(heads, pending[me]) : (bfs_ctrl_t*)nullptr;
+    pending[me] = i;
+    int sl;
+    if (i == 0 || state_of(i - 1) == me) {
+      sl = bfs_enqueue_start(st, P, srcs[i], ctx, prev_head ? P.a.ctrl : (const bfs_ctrl_t*)nullptr, prev_head, head_words, cls != BFS_SRC_SKIP);
+    } else {
+      // traversal i - 1 (the other state) has left its tail launches to this seam: its M launch in last_slots[i - 1] - 1 (plans with
+      // M launches), its chain in last_slots[i - 1]
+      const int sl_a = plan.minis ? last_slots[(size_t)i - 1] - 1 : last_slots[(size_t)i - 1];
+      bfs_enqueue_seam(st, plans[me ^ 1], tails[me ^ 1], sl_a, P, srcs[i], prev_head, head_words, ctx);
+      sl = 0;
+      if (plan.minis && cls != BFS_SRC_SKIP) { bfs_enqueue_mini(P, 0, s); sl = 1; }
+    }
+    for (int k = 0; k < my_slots; ++k, ++sl) bfs_enqueue_slot(st, P, sl, ctx);
+    // (the handle's first such batch: the allocation, behind the slots of the last traversal of the lead and in front of the decision
+    //  who runs that traversal's tail -- a refused allocation leaves the tail where it was)
+    if (overlap && i + 1 == lead && !st.alt) second_state();
+    const bool seam_behind = i + 1 < count && state_of(i + 1) != me;          // (the next traversal's seam runs this one's tail)
+    if (plan.minis) { if (!seam_behind) bfs_enqueue_mini(P, sl, s); ++sl; }
+    if (tail && !seam_behind) bfs_enqueue_chain_inplace(tails[me], sl, s);
     last_slots[(size_t)i] = sl;
     classes[(size_t)i] = cls;
   }
-  st.tail_from = saved_tail;
+  tail_guard.release();
   const u64 seq = ++st.seq;
-  hipLaunchKernelGGL(k_bfs_publish, dim3(1), dim3(256), 0, s, (const bfs_ctrl_t*)st.ctrl.data(), bfs_many_head(heads, count - 1), st.host_seq, seq, head_words);
+  assert(pending[0] == count - 1);     // the last traversal ran in state 0 (state_of(count - 1) == 0): the caller's labels are its labels
+  if (pending[1] >= 0)
+    hipLaunchKernelGGL(k_bfs_publish2, dim3(1), dim3(256), 0, s, (const bfs_ctrl_t*)plans[0].a.ctrl, bfs_many_head(heads, pending[0]),
+                       (const bfs_ctrl_t*)plans[1].a.ctrl, bfs_many_head(heads, pending[1]), st.host_seq, seq, head_words);
+  else
+    hipLaunchKernelGGL(k_bfs_publish, dim3(1), dim3(256), 0, s, (const bfs_ctrl_t*)st.ctrl.data(), bfs_many_head(heads, count - 1), st.host_seq, seq, head_words);
   MGX_CHECK_LAUNCH("fused BFS (batch of sources): kernel launch");
   {
     volatile u64* const flag = st.host_seq;

@@ -31,6 +31,7 @@ inline const env_switch_t* env_switches(int* count) {
     {"MGX_BFS_HOT_UNITS", "0: no second copy of the unit blocks without the cold lists' entries"},
     {"MGX_BFS_PACK24", "0: 32-bit unit-block entries instead of the 24-bit copy"},
     {"MGX_BFS_MINI", "0 / 2: no M launches / M launches on every graph (default: from 2^22 vertices on)"},
+    {"MGX_BFS_BATCH_OVERLAP", "0: a batch of sources runs in one traversal state, no launch shared by two traversals"},
     {"MGX_BFS_SEED_CHAIN", "0: the chain of small levels at the start runs inside slot 0's push launch"},
     {"MGX_BFS_TAIL_CHAIN", "0: no in-place chain launch behind the last slots"},
     {"MGX_BFS_TAIL_FRONT", "0: no chain in front of the last slots"},
