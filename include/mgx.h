@@ -45,6 +45,7 @@ typedef struct mgx_kcore_s* mgx_kcore_t;
 typedef struct mgx_color_s* mgx_color_t;
 typedef struct mgx_lspar_s* mgx_lspar_t;
 typedef struct mgx_cc_s* mgx_cc_t;
+typedef struct mgx_pagerank_s* mgx_pagerank_t;
 typedef struct mgx_dbfs_s* mgx_dbfs_t;
 typedef struct mgx_dbfs2_s* mgx_dbfs2_t;
 typedef struct mgx_dsssp_s* mgx_dsssp_t;
@@ -577,6 +578,34 @@ MGX_API int mgx_cc_enact(mgx_cc_t p, int64_t* stats);
 /* labels of the last run of either path (MGX_E_INVALID before any run); the device pointer stays valid until the next run or free */
 MGX_API int mgx_cc_labels(mgx_cc_t p, int* host_labels);
 MGX_API int mgx_cc_labels_device(mgx_cc_t p, const int** d_labels);
+
+/* ---- PageRank to convergence (mgx/pagerank_fused.hpp, include/gunrock/pagerank/) ----
+ * Not mgx_pr_*: that is the reference's pr_enactor_t loop, kept quirk for quirk.  This is PageRank: CSR entry (u, v) is an edge
+ * u -> v (duplicates count once each, self-loops count), d(u) the length of row u, r_0 = 1 / n,
+ *   r_{t+1}[v] = (1 - alpha) / n + alpha * (sum of r_t[u] / d(u) over the in-entries (u, v) + D_t / n),  D_t = the ranks of the
+ * vertices without out-entries, e_{t+1} = |r_{t+1} - r_t|_1; the run stops after the first iteration with e <= tol (converged) or
+ * after max_iter iterations.  Ranks are float, D and e double; the ranks sum to 1.
+ * symmetric != 0 is the caller's word that every entry has its reverse: the in-entries of v are then row v of the CSR.
+ * symmetric == 0: the in-entries come from the graph's genuine CSC (mgx_graph_build_csc, or one uploaded); a graph without one gets
+ * MGX_E_INVALID.  Every run starts afresh, on the context's stream. */
+MGX_API int mgx_pagerank_create(mgx_graph_t g, mgx_pagerank_t* out);
+MGX_API int mgx_pagerank_free(mgx_pagerank_t p);
+/* alpha in [0, 1), tol >= 0 and finite, max_iter >= 1: else MGX_E_INVALID before any device work.
+ * stats (may be NULL): [0] iterations run, [1] converged (0 / 1), [2] vertices without out-entries,
+ * [3] reduce path (1: the layout's sliced kernels, 0: general; always 0 from mgx_pagerank_enact, whose operator chooses for itself),
+ * [4] host waits the run made, [5] launches the path enqueued (mgx_pagerank_enact: without the operator's own).
+ * *residual (may be NULL): e of the last iteration.
+ * mgx_pagerank_run: the fused path -- the iterations end on the device, the host looks once per batch of them; two runs with the same
+ * arguments give bit-equal ranks and residuals.  mgx_pagerank_enact: the operator path (neighbourhood-reduce + update, two host
+ * waits per iteration), right on any graph under the same rule for symmetric. */
+MGX_API int mgx_pagerank_run  (mgx_pagerank_t p, double alpha, double tol, int max_iter, int symmetric, int64_t* stats, double* residual);
+MGX_API int mgx_pagerank_enact(mgx_pagerank_t p, double alpha, double tol, int max_iter, int symmetric, int64_t* stats, double* residual);
+/* ranks of the last run of either path by original id (MGX_E_INVALID before any run); the device pointer stays valid until the next
+ * run or free */
+MGX_API int mgx_pagerank_ranks(mgx_pagerank_t p, float* host_ranks);
+MGX_API int mgx_pagerank_ranks_device(mgx_pagerank_t p, const float** d_ranks);
+/* e_1 .. of the last run: min(cap, iterations, 65536) values into host_e; *iterations (may be NULL) = iterations run */
+MGX_API int mgx_pagerank_residuals(mgx_pagerank_t p, double* host_e, int cap, int* iterations);
 
 /* ---- segmented sort (mgpu::segmented_sort, lspar_enactor.hxx:85; mgx/segsort.hpp) ----
  * Sorts d_keys[0, count) (and d_vals with them; NULL: keys only) in place, stably, ascending or descending, within segments:

@@ -222,6 +222,13 @@ SIGNATURES = {
     "mgx_cc_enact": [_vp, _pi64],
     "mgx_cc_labels": [_vp, _vp],
     "mgx_cc_labels_device": [_vp, _pvp],
+    "mgx_pagerank_create": [_vp, _pvp],
+    "mgx_pagerank_free": [_vp],
+    "mgx_pagerank_run": [_vp, C.c_double, C.c_double, _i, _i, _pi64, C.POINTER(C.c_double)],
+    "mgx_pagerank_enact": [_vp, C.c_double, C.c_double, _i, _i, _pi64, C.POINTER(C.c_double)],
+    "mgx_pagerank_ranks": [_vp, _vp],
+    "mgx_pagerank_ranks_device": [_vp, _pvp],
+    "mgx_pagerank_residuals": [_vp, C.POINTER(C.c_double), _i, _pi],
     "mgx_rmat_edges": [_vp, _i, _i64, _i64, _u64, _i, _vp, _vp, _vp],
 }
 _RESTYPES = {"mgx_comm_library": C.c_char_p, "mgx_strerror": C.c_char_p, "mgx_last_error": C.c_char_p, "mgx_host_free": None}

@@ -4,7 +4,7 @@ Names follow the reference (gunrock/src/*.hxx): Graph ~ graph_device_t, Frontier
 BfsProblem ~ bfs_problem_t + bfs_enactor_t, SsspProblem ~ sssp_problem_t + sssp_enactor_t,
 PrProblem ~ pr_problem_t + pr_enactor_t, KcoreProblem ~ kcore_problem_t + kcore_enactor_t,
 ColorProblem ~ coloring_problem_t + coloring_enactor_t, LsparProblem ~ lspar_problem_t + lspar_enactor_t,
-CcProblem ~ cc_problem_t + cc_enactor_t.  Every method is one C-ABI call; nothing is computed here.
+CcProblem ~ cc_problem_t + cc_enactor_t, PageRankProblem ~ pagerank_problem_t + pagerank_enactor_t.  Every method is one C-ABI call; nothing is computed here.
 """
 import ctypes as C
 
@@ -758,6 +758,52 @@ class CcProblem:
     def close(self):
         if self._h:
             lib.mgx_cc_free(self._h)
+            self._h = None
+
+
+class PageRankProblem:
+    """PageRank to convergence: pagerank_problem_t + pagerank_enactor_t, and the fused path beside them.  Not PrProblem,
+    which is the reference's loop.  ranks() / residuals() describe the last run of either path."""
+
+    def __init__(self, graph):
+        h = C.c_void_p()
+        check(lib.mgx_pagerank_create(graph._h, C.byref(h)))
+        self.graph, self._h = graph, h
+
+    def _go(self, fn, alpha, tol, max_iter, symmetric):
+        st, res = (C.c_int64 * 6)(), C.c_double()
+        check(fn(self._h, C.c_double(alpha), C.c_double(tol), int(max_iter), int(bool(symmetric)), st, C.byref(res)))
+        return {"iterations": st[0], "converged": st[1], "dangling": st[2], "layout_path": st[3], "host_waits": st[4],
+                "launches": st[5], "residual": res.value}
+
+    def run(self, alpha=0.85, tol=1e-6, max_iter=100, symmetric=False):
+        """fused path -> {"iterations", "converged", "dangling", "layout_path", "host_waits", "launches", "residual"}.
+        symmetric=True is the caller's word that every entry has its reverse; False needs the graph's genuine CSC (build_csc)."""
+        return self._go(lib.mgx_pagerank_run, alpha, tol, max_iter, symmetric)
+
+    def enact(self, alpha=0.85, tol=1e-6, max_iter=100, symmetric=False):
+        """operator path (neighbourhood-reduce, update, two host waits per iteration); the same stats, layout_path = 0"""
+        return self._go(lib.mgx_pagerank_enact, alpha, tol, max_iter, symmetric)
+
+    def ranks(self):
+        out = np.empty(self.graph.num_nodes, dtype=np.float32)
+        check(lib.mgx_pagerank_ranks(self._h, _ptr(out)))
+        return out
+
+    def ranks_device_ptr(self):
+        p = C.c_void_p()
+        check(lib.mgx_pagerank_ranks_device(self._h, C.byref(p)))
+        return p.value
+
+    def residuals(self, cap=65536):
+        """e_1 .. e_T of the last run (at most 65 536 are kept)"""
+        out, it = np.empty(max(int(cap), 1), dtype=np.float64), C.c_int()
+        check(lib.mgx_pagerank_residuals(self._h, out.ctypes.data_as(C.POINTER(C.c_double)), int(cap), C.byref(it)))
+        return out[:min(int(cap), it.value)].copy()
+
+    def close(self):
+        if self._h:
+            lib.mgx_pagerank_free(self._h)
             self._h = None
 
 

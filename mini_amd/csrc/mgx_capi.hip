@@ -12,6 +12,7 @@
 #include "gunrock/cc/cc_enactor.hxx"
 #include "gunrock/coloring/coloring_enactor.hxx"
 #include "gunrock/lspar/lspar_enactor.hxx"
+#include "gunrock/pagerank/pagerank_enactor.hxx"
 #include "gunrock/pr/pr_enactor.hxx"
 #include "gunrock/kcore/kcore_enactor.hxx"
 #include "gunrock/sssp/sssp_enactor.hxx"
@@ -21,6 +22,7 @@
 #include "mgx/kcore_fused.hpp"
 #include "mgx/color_fused.hpp"
 #include "mgx/lspar_fused.hpp"
+#include "mgx/pagerank_fused.hpp"
 #include "mgx/env.hpp"
 #include "mgx/sssp_dist.hpp"
 #include "mgx/rmat.hpp"
@@ -110,6 +112,12 @@ struct mgx_cc_s {
   std::unique_ptr<cc::cc_enactor_t> e;
   std::unique_ptr<mgx::cc_label_stats_t> label_stats;             // lazily: the operator path's stats
   const int* labels = nullptr;                                    // the last run's labels (nullptr: no run yet)
+};
+
+struct mgx_pagerank_s {
+  mgx_graph_t g = nullptr;
+  std::shared_ptr<pagerank::pagerank_problem_t> p;                // lazily: the O(n) state both paths run on
+  std::unique_ptr<pagerank::pagerank_enactor_t> e;                // lazily: the operator path's iota frontier
 };
 
 struct mgx_dbfs_s {
@@ -2493,6 +2501,128 @@ int mgx_cc_labels_device(mgx_cc_t p, const int** out) {
   MGX_REQUIRE(p && out, "NULL argument");
   MGX_REQUIRE(p->labels, "mgx_cc_labels_device: no run yet");
   *out = p->labels;
+  MGX_CATCH
+}
+
+// ---- PageRank to convergence --------------------------------------------------------
+int mgx_pagerank_create(mgx_graph_t g, mgx_pagerank_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(g && out, "NULL argument");
+  auto* h = new mgx_pagerank_s();
+  h->g = g;
+  *out = h;
+  MGX_CATCH
+}
+int mgx_pagerank_free(mgx_pagerank_t p) {
+  MGX_TRY
+  if (p) { use_device(p->g->c); delete p; }
+  MGX_CATCH
+}
+// the arguments both paths refuse before any device work
+static void pagerank_check(mgx_pagerank_t p, double alpha, double tol, int max_iter, int symmetric, const char* who) {
+  MGX_REQUIRE(p, "NULL argument");
+  MGX_REQUIRE(alpha >= 0.0 && alpha < 1.0, std::string(who) + ": alpha must be in [0, 1)");
+  MGX_REQUIRE(tol >= 0.0 && std::isfinite(tol), std::string(who) + ": tol must be finite and >= 0");
+  MGX_REQUIRE(max_iter >= 1, std::string(who) + ": max_iter must be >= 1");
+  MGX_REQUIRE(symmetric != 0 || !p->g->g->csc_is_csr,
+              std::string(who) + ": symmetric = 0 needs the graph's genuine CSC for the in-entries (mgx_graph_build_csc, or upload one); "
+                                 "pass symmetric = 1 only if every entry has its reverse");
+}
+static void pagerank_stats(int64_t* stats, double* residual, const mgx::pagerank_stats_t& s) {
+  if (stats) {
+    stats[0] = s.iterations; stats[1] = s.converged; stats[2] = s.dangling; stats[3] = s.layout_path; stats[4] = s.waits; stats[5] = s.launches;
+  }
+  if (residual) *residual = s.residual;
+}
+// the layout reduce's view of the graph (the conditions of neighborhood.hxx:59-62, 91-92); false: the general reduce serves
+static bool pagerank_layout(mgx_graph_s* g, mgx::nr_layout_t& L) {
+  graph_device_t& G = *g->g;
+  if (!G.has_layout || G.num_edges <= 0) return false;
+  ensure_nr_slices(g);
+  standard_context_t& ctx = *g->c->ctx;
+  if (!(G.rows.ub.units > 0 && G.rows.ub_min_degree == G.rows.vs_long_min && G.rows.vs_long_min >= 17 && G.rows.vs_long_min <= 64 &&
+        G.rows.ub.cnt.size() && G.rows.ub.first.size() && G.rows.vs_dummy != 0)) return false;
+  if (!(G.nrs_units > 0 && G.nrs_slices > 0 && G.nrs_rows == G.rows.vs_v[0] && G.d_nrs_mu.size() && G.d_nrs_off.size() &&
+        ctx.scratch_bytes >= mgx::nr_scratch_bytes(G.num_nodes, G.nrs_units, sizeof(float)))) return false;
+  L = mgx::nr_layout_t();
+  L.new_of_old = G.d_new_of_old.data();
+  L.row_offsets = (const mgx::u32*)G.d_layout_row_offsets.data();
+  L.col_indices = G.d_layout_col_indices.data();
+  L.old_of_new = G.d_old_of_new.data();
+  L.ub_col = G.rows.ub.col.size() ? G.rows.ub.col.data() : nullptr;
+  L.ub_col24 = G.rows.ub.col24.size() ? G.rows.ub.col24.data() : nullptr;
+  L.ub_cnt = G.rows.ub.cnt.data();
+  L.ub_first = G.rows.ub.first.data();
+  L.ub_units = (mgx::u32)G.rows.ub.units; L.ub_units_pad = (mgx::u32)G.rows.ub.units_pad;
+  for (int i = 0; i < 4; ++i) L.vs_v[i] = G.rows.vs_v[i];
+  L.vs_dummy = G.rows.vs_dummy;
+  L.big_rows = G.nr_big_rows;
+  L.n = G.num_nodes;
+  L.nrs_mu = (const uint4*)G.d_nrs_mu.data();
+  L.nrs_off = G.d_nrs_off.data();
+  for (int i = 0; i < mgx::NRS_MAX_SLICES + 2; ++i) L.nrs_first[i] = G.nrs_first[i];
+  L.nrs_slices = G.nrs_slices; L.nrs_rows = G.nrs_rows;
+  for (int i = 0; i < 3; ++i) L.nrs_tier[i] = G.nrs_tier[i];
+  return true;
+}
+int mgx_pagerank_run(mgx_pagerank_t p, double alpha, double tol, int max_iter, int symmetric, int64_t* stats, double* residual) {
+  MGX_TRY
+  pagerank_check(p, alpha, tol, max_iter, symmetric, "mgx_pagerank_run");
+  use_device(p->g->c);
+  standard_context_t& ctx = *p->g->c->ctx;
+  graph_device_t& G = *p->g->g;
+  if (!p->p) p->p = std::make_shared<pagerank::pagerank_problem_t>(p->g->g, ctx);
+  mgx::pagerank_graph_t pg;
+  mgx::nr_layout_t L;
+  pg.out_off = G.d_row_offsets.data();
+  pg.in_off = symmetric ? G.d_row_offsets.data() : G.d_col_offsets.data();
+  pg.in_idx = symmetric ? G.d_col_indices.data() : G.d_row_indices.data();
+  pg.in_entries = G.num_edges;
+  if (symmetric && pagerank_layout(p->g, L)) {
+    pg.layout = &L;
+    pg.old_of_new = G.d_old_of_new.data();
+  }
+  pagerank_stats(stats, residual, p->p->state.run(pg, alpha, tol, max_iter, ctx));
+  MGX_CATCH
+}
+int mgx_pagerank_enact(mgx_pagerank_t p, double alpha, double tol, int max_iter, int symmetric, int64_t* stats, double* residual) {
+  MGX_TRY
+  pagerank_check(p, alpha, tol, max_iter, symmetric, "mgx_pagerank_enact");
+  use_device(p->g->c);
+  standard_context_t& ctx = *p->g->c->ctx;
+  graph_device_t& G = *p->g->g;
+  if (!p->p) p->p = std::make_shared<pagerank::pagerank_problem_t>(p->g->g, ctx);
+  if (!p->e) p->e.reset(new pagerank::pagerank_enactor_t(ctx, G.num_nodes, G.num_edges));
+  if (G.has_layout && G.csc_is_csr) ensure_nr_slices(p->g);      // (the operator's full-frontier reduce may take them)
+  pagerank_stats(stats, residual, p->e->enact(p->p, alpha, tol, max_iter, ctx));
+  MGX_CATCH
+}
+int mgx_pagerank_ranks(mgx_pagerank_t p, float* host) {
+  MGX_TRY
+  MGX_REQUIRE(p && host, "NULL argument");
+  MGX_REQUIRE(p->p && p->p->state.result, "mgx_pagerank_ranks: no run yet");
+  use_device(p->g->c);
+  p->g->c->ctx->synchronize();
+  MGX_HIP(mgx::dtoh(host, p->p->state.result, (size_t)p->g->g->num_nodes));
+  MGX_CATCH
+}
+int mgx_pagerank_ranks_device(mgx_pagerank_t p, const float** out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  MGX_REQUIRE(p->p && p->p->state.result, "mgx_pagerank_ranks_device: no run yet");
+  *out = p->p->state.result;
+  MGX_CATCH
+}
+int mgx_pagerank_residuals(mgx_pagerank_t p, double* host_e, int cap, int* iterations) {
+  MGX_TRY
+  MGX_REQUIRE(p && cap >= 0 && (host_e || cap == 0), "bad argument");
+  MGX_REQUIRE(p->p && p->p->state.result, "mgx_pagerank_residuals: no run yet");
+  use_device(p->g->c);
+  mgx::pagerank_state_t& s = p->p->state;
+  if (iterations) *iterations = s.last_iterations;
+  const int k = std::min(std::min(cap, s.last_iterations), s.trace_cap);
+  p->g->c->ctx->synchronize();
+  if (k > 0) MGX_HIP(mgx::dtoh(host_e, (const double*)s.trace.data(), (size_t)k));
   MGX_CATCH
 }
 
