@@ -481,6 +481,25 @@ MGX_API int mgx_sssp_set_kernel_timing(mgx_sssp_t p, int on);
  * ms from device-side timestamps taken when an iteration is opened (0 for the last one); *iterations = how many there were */
 MGX_API int mgx_sssp_iteration_trace(mgx_sssp_t p, int cap, int64_t* frontier, int64_t* edges, float* ms, int* iterations);
 MGX_API int mgx_sssp_kernel_times(mgx_sssp_t p, int64_t* out2);
+/* which paths the last mgx_sssp_run / mgx_sssp_run_delta took (include/mgx/sssp_fused.hpp); MGX_E_INVALID before the first run.
+ *   out8[0]  1: the heavy iterations' sweep over the unit blocks was available to the run (a weighted layout the library built
+ *            with a long-row threshold of 17 .. 64 and at least 16 units, the direct queue build, no near / far buckets,
+ *            MGX_SSSP_DENSE not 0)
+ *   out8[1]  the sweep's variant: 0 none (out8[0] == 0); 1 32-bit ids + float weights; 2 24-bit ids + float weights;
+ *            3 24-bit ids + half weights (every weight of the unit blocks survives the round trip through IEEE half)
+ *   out8[2]  iterations the sweep relaxed
+ *   out8[3]  iterations the queue walk relaxed with the hubs' distance bounds in LDS (MGX_SSSP_HOT_MIN_EDGES)
+ *   out8[4]  iterations the queue walk relaxed without them
+ *   out8[5]  queue build: 0 direct (k_sssp_build2), 1 list (k_sssp_build: MGX_SSSP_BUILD_LIST=1 or row offsets off 16 bytes)
+ *   out8[6]  iterations that only moved the near / far threshold (0 in a plain run)
+ *   out8[7]  1: the run relaxed in layout space
+ * out8[2] + out8[3] + out8[4] + out8[6] == stats[0] of the run.  Counted on the host, when asked, from the per-iteration trace
+ * the device keeps, with the very predicates the kernels select by; the trace holds 4096 iterations: MGX_E_INVALID for a
+ * longer run.
+ * The sweep never runs on a layout attached with mgx_graph_attach_layout / _attach_layout_weights: its short-row walk loads 16
+ * bytes from a row's start whatever the row's length, and borrowed arrays end at exactly num_edges entries (a layout the library
+ * builds carries 8 entries of slack).  out8[0] is 0 there. */
+MGX_API int mgx_sssp_path_info(mgx_sssp_t p, int64_t* out8);
 
 /* ---- PR: pr_problem_t / pr_functor_t / pr_enactor_t (gunrock/src/pr/) ---- */
 MGX_API int mgx_pr_create(mgx_graph_t g, int max_iter, mgx_pr_t* out);    /* pr_problem.hxx:33-44   */

@@ -184,6 +184,17 @@ __device__ __forceinline__ void sssp_open(const sssp_args_t& a, int it) {
   c->sum_frontier += cur >> BFS_VSHIFT;
 }
 
+// The two size tests that pick an iteration's path, written ONCE: k_sssp_relax, k_sssp_relax_dense and the host's count of the
+// paths a run took (sssp_count_paths below, mgx_sssp_path_info) all call these -- a second copy of either could drift, and the
+// report would then describe a selection the kernels do not make.  E: the iteration's frontier edges (the low word the kernels see).
+//   heavy    the sweep over the unit blocks and degree classes relaxes the iteration (`sweep`: the run carries the unit blocks'
+//            weights at all), the queue walk returns at once
+//   bounds   the queue walk keeps the hubs' 16-bit distance bounds in LDS
+__host__ __device__ inline bool sssp_iteration_heavy(bool sweep, u32 E, u32 dense_div, unsigned long long m_edges) {
+  return sweep && (u64)E * (u64)dense_div >= m_edges;
+}
+__host__ __device__ inline bool sssp_iteration_bounds(u32 E, u32 hot_min_edges) { return E >= hot_min_edges; }
+
 constexpr int SSSP_EPT = 4;
 constexpr int SSSP_TILE = WAVE * SSSP_EPT;
 // Upper bounds of the distances of the first SSSP_HOTN vertices (the hubs under the hub-first layout: the targets
@@ -476,7 +487,7 @@ __global__ __launch_bounds__(NT, 4) void k_sssp_relax_dense(sssp_args_t a, int i
   extern __shared__ __attribute__((aligned(16))) u32 s_hot_dense[];
   const u64 cur = a.ctrl->cursor[it % 3];
   const u32 E = (u32)(cur & BFS_EMASK);
-  if ((cur >> BFS_VSHIFT) == 0 || !a.ub_w || (u64)E * (u64)a.dense_div < a.m_edges) return;
+  if ((cur >> BFS_VSHIFT) == 0 || !sssp_iteration_heavy(a.ub_w != nullptr, E, a.dense_div, a.m_edges)) return;
   const u32 hot_n = sssp_load_bounds<NT, SSSP_HOTN_DENSE>(a.dist, a.n, s_hot_dense);
   if (a.ub_col24 && a.ub_w16) sssp_dense_long<NT, true, true>(a, s_hot_dense, hot_n, blockIdx.x, gridDim.x);      // (grid-uniform)
   else if (a.ub_col24) sssp_dense_long<NT, true, false>(a, s_hot_dense, hot_n, blockIdx.x, gridDim.x);
@@ -512,8 +523,8 @@ __global__ __launch_bounds__(NT, 8) void k_sssp_relax(sssp_args_t a, int it) {
   unsigned char* mark = a.mark;
 
   extern __shared__ __attribute__((aligned(16))) u32 s_hot[];        // SSSP_HOTN / 2 words: two bounds per word
-  if (a.ub_w && (u64)E * (u64)a.dense_div >= a.m_edges) return;     // a heavy iteration (grid-uniform): k_sssp_relax_dense's
-  const bool use_hot = E >= a.hot_min_edges;
+  if (sssp_iteration_heavy(a.ub_w != nullptr, E, a.dense_div, a.m_edges)) return;     // a heavy iteration (grid-uniform): k_sssp_relax_dense's
+  const bool use_hot = sssp_iteration_bounds(E, a.hot_min_edges);
   const u32 hot_n = use_hot ? sssp_load_bounds<NT, SSSP_HOTN>(dist, a.n, s_hot) : 0u;
   const unsigned short* const hot16 = (const unsigned short*)s_hot;
 
@@ -875,7 +886,23 @@ __global__ __launch_bounds__(BLOCK) void k_sssp_unpermute(const u32* __restrict_
     dist_out[old_of_new[v]] = dist_layout[v];
 }
 
+// Which paths the last run took (mgx_sssp_path_info).  The selection is recorded by the host when it fills sssp_args_t; the
+// per-iteration counts are made afterwards, on demand, from the iteration trace the device keeps anyway (sssp_open) with the
+// predicates the kernels use -- nothing is added to the kernels or to a run that nobody asks about.
+struct sssp_path_t {
+  bool valid = false;                // a run has finished
+  bool counted = false;              // swept .. thr_moves below are those of that run
+  bool sweep = false;                // the sweep was available (sssp_fused_run's `dense`)
+  int variant = 0;                   // 0 none; 1 32-bit ids + float weights; 2 24-bit ids + float weights; 3 24-bit ids + half weights
+  bool build_list = false;           // k_sssp_build (the list) instead of k_sssp_build2
+  bool layout_space = false;
+  u32 dense_div = 0, hot_min_edges = 0;
+  unsigned long long m_edges = 0;
+  long long swept = 0, walked_bounds = 0, walked_plain = 0, thr_moves = 0;
+};
+
 struct sssp_fused_state_t {
+  sssp_path_t path;
   mem_t<unsigned char> mark;
   mem_t<u32> dist_layout;            // only with a layout: distances in layout order
   mem_t<u32> q_row[2], q_off[2], q_du[2];
@@ -953,6 +980,15 @@ inline void sssp_fused_run(sssp_fused_state_t& st, const int* row_offsets, const
   if (dense) { a.m_edges = (unsigned long long)layout->m_edges; a.frontier_bits = st.frontier_bits.data(); }
   const char* const hme = mgx::env("MGX_SSSP_HOT_MIN_EDGES");        // (tests force the LDS bounds on small graphs)
   a.hot_min_edges = hme ? (u32)atoll(hme) : SSSP_HOT_MIN_EDGES;
+  st.path = sssp_path_t();
+  st.path.sweep = dense;
+  st.path.variant = !dense ? 0 : (a.ub_col24 && a.ub_w16) ? 3 : a.ub_col24 ? 2 : 1;      // (k_sssp_relax_dense's choice of sssp_dense_long)
+  st.path.build_list = !build2;
+  st.path.layout_space = layout != nullptr;
+  st.path.dense_div = a.dense_div; st.path.hot_min_edges = a.hot_min_edges; st.path.m_edges = a.m_edges;
+  // near / far buckets: an iteration that only moves the threshold writes no trace slot (sssp_open), and the slots are not
+  // cleared between runs -- zero them, so that sssp_count_paths tells such an iteration (0) from one that relaxed (never 0)
+  if (a.delta > 0.f) MGX_HIP(hipMemsetAsync((char*)st.ctrl.data() + offsetof(bfs_ctrl_t, trace), 0, sizeof(u64) * BFS_MAX_TRACE, s));
   hipLaunchKernelGGL(k_sssp_init, dim3(grid_for(((long long)st.n + 3) / 4, BLOCK, ctx.num_cus * 8)), dim3(BLOCK), 0, s, a, src,
                      layout ? layout->new_of_old : (const int*)nullptr);
   static unsigned char attr_seen[64] = {};
@@ -994,12 +1030,39 @@ inline void sssp_fused_run(sssp_fused_state_t& st, const int* row_offsets, const
     }
   }
   st.iters_hint = st.host_ctrl->levels > 0 ? st.host_ctrl->levels : 1;
+  st.path.valid = true;
   if (layout) {
     hipLaunchKernelGGL(k_sssp_unpermute, dim3(grid_for(st.n, BLOCK, ctx.num_cus * 8)), dim3(BLOCK), 0, s, st.dist_layout.data(),
                        layout->old_of_new, (u32*)d_dist, (long long)st.n);
     MGX_CHECK_LAUNCH("fused SSSP: unpermute launch");
     MGX_HIP(hipStreamSynchronize(s));
   }
+}
+
+// Counts the iterations of the last run by the path that relaxed them, from the device's iteration trace: a run copies back the
+// first 64 slots; a longer run's are fetched here, once.  The trace holds BFS_MAX_TRACE (4096) iterations: false for a longer run
+// (the selection in st.path is valid either way).  swept + walked_bounds + walked_plain + thr_moves == iterations.
+inline bool sssp_count_paths(sssp_fused_state_t& st, standard_context_t& ctx) {
+  sssp_path_t& p = st.path;
+  if (p.counted) return true;
+  const int levels = st.host_ctrl->levels;
+  if (levels > BFS_MAX_TRACE) return false;
+  if (levels > 64) {
+    MGX_HIP(hipMemcpyAsync(st.host_ctrl->trace, (const char*)st.ctrl.data() + offsetof(bfs_ctrl_t, trace), sizeof(u64) * (size_t)levels,
+                           hipMemcpyDeviceToHost, ctx.stream()));
+    MGX_HIP(hipStreamSynchronize(ctx.stream()));
+  }
+  p.swept = p.walked_bounds = p.walked_plain = p.thr_moves = 0;
+  for (int it = 0; it < levels; ++it) {
+    const u64 cur = st.host_ctrl->trace[it];
+    const u32 E = (u32)(cur & BFS_EMASK);
+    if ((cur >> BFS_VSHIFT) == 0) ++p.thr_moves;                       // (only with near / far buckets: the queue was empty, vertices waited)
+    else if (sssp_iteration_heavy(p.sweep, E, p.dense_div, p.m_edges)) ++p.swept;
+    else if (sssp_iteration_bounds(E, p.hot_min_edges)) ++p.walked_bounds;
+    else ++p.walked_plain;
+  }
+  p.counted = true;
+  return true;
 }
 
 }  // namespace mgx

@@ -508,6 +508,17 @@ class SsspProblem:
         check(lib.mgx_sssp_kernel_times(self._h, c))
         return {"launches": c[0], "ns": c[1]}
 
+    SWEEP_VARIANTS = {0: "none", 1: "ids32+f32", 2: "ids24+f32", 3: "ids24+f16"}
+
+    def path_info(self):
+        """which paths the last run() took (mgx_sssp_path_info; MgxError before the first run): swept + walked_with_bounds +
+        walked_without_bounds + threshold_moves == iterations"""
+        o = (C.c_int64 * 8)()
+        check(lib.mgx_sssp_path_info(self._h, o))
+        return {"sweep_available": bool(o[0]), "sweep_variant": int(o[1]), "swept": int(o[2]), "walked_with_bounds": int(o[3]),
+                "walked_without_bounds": int(o[4]), "queue_build": "list" if o[5] else "direct", "threshold_moves": int(o[6]),
+                "layout_space": bool(o[7])}
+
     def run(self, src, delta=None):
         """fused device-resident loop; delta: near / far bucket width (None / 0: plain frontier Bellman-Ford)"""
         st = (C.c_int64 * 3)()

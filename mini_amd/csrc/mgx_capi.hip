@@ -2055,6 +2055,23 @@ int mgx_sssp_iteration_trace(mgx_sssp_t p, int cap, int64_t* frontier, int64_t* 
   }
   MGX_CATCH
 }
+int mgx_sssp_path_info(mgx_sssp_t p, int64_t* out8) {
+  MGX_TRY
+  MGX_REQUIRE(p && out8, "NULL argument");
+  MGX_REQUIRE(p->fused != nullptr && p->fused->path.valid, "mgx_sssp_path_info: no mgx_sssp_run yet");
+  use_device(p->g->c);
+  MGX_REQUIRE(mgx::sssp_count_paths(*p->fused, *p->g->c->ctx), "mgx_sssp_path_info: the run had more iterations than the trace holds (4096)");
+  const mgx::sssp_path_t& P = p->fused->path;
+  out8[0] = P.sweep ? 1 : 0;
+  out8[1] = P.variant;
+  out8[2] = P.swept;
+  out8[3] = P.walked_bounds;
+  out8[4] = P.walked_plain;
+  out8[5] = P.build_list ? 1 : 0;
+  out8[6] = P.thr_moves;
+  out8[7] = P.layout_space ? 1 : 0;
+  MGX_CATCH
+}
 int mgx_sssp_set_kernel_timing(mgx_sssp_t p, int on) {
   MGX_TRY
   MGX_REQUIRE(p, "NULL argument");
