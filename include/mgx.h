@@ -45,6 +45,7 @@ typedef struct mgx_kcore_s* mgx_kcore_t;
 typedef struct mgx_color_s* mgx_color_t;
 typedef struct mgx_lspar_s* mgx_lspar_t;
 typedef struct mgx_cc_s* mgx_cc_t;
+typedef struct mgx_tc_s* mgx_tc_t;
 typedef struct mgx_pagerank_s* mgx_pagerank_t;
 typedef struct mgx_dbfs_s* mgx_dbfs_t;
 typedef struct mgx_dbfs2_s* mgx_dbfs2_t;
@@ -597,6 +598,41 @@ MGX_API int mgx_cc_enact(mgx_cc_t p, int64_t* stats);
 /* labels of the last run of either path (MGX_E_INVALID before any run); the device pointer stays valid until the next run or free */
 MGX_API int mgx_cc_labels(mgx_cc_t p, int* host_labels);
 MGX_API int mgx_cc_labels_device(mgx_cc_t p, const int** d_labels);
+
+/* ---- triangle counting ----
+ * Triangles of the underlying simple undirected graph: every CSR entry (v, u) with v != u is read as the pair {v, u}; self-loops
+ * and duplicate entries change nothing; original ids (an attached hub-first layout is ignored).  tri[v] = the triangles that
+ * contain v (64 bits), total = sum of tri / 3, sdeg[v] = the distinct neighbours of v other than v.  Both paths count on the same
+ * oriented graph (DAG), built on the device at the first run and kept on the handle per `symmetric` value: dag_ro[n + 1],
+ * dag_ci[m_dag], row a = the distinct neighbours of a of higher rank, ascending by id; a triangle of ranks a < b < c is counted
+ * once, at entry (a, b).  symmetric != 0 is the caller's word that every entry has its reverse: rank = (row length, id) and only
+ * the entries with rank(v) < rank(u) are kept -- the counts are right on a symmetric graph; symmetric = 0 is right on any graph
+ * (deg(v) = row length + entries that name v, every entry oriented from its lower-ranked end).  stats (int64, may be NULL):
+ * [0] triangles, [1] m_dag (the simple undirected edges), [2] the longest oriented row, [3] oriented wedges (sum of d+(d+ - 1)/2),
+ * [4] 1 if the rows were found ascending and used as they are (symmetric != 0 only), 0 if a sorted copy was made, [5] 1 if this
+ * run built the DAG, 0 if it reused an earlier run's, [6] host waits the run made, [7] launches it enqueued.  [0] - [4] are equal
+ * between the two paths; [7] counts kernel launches and clears (the read-back copies are not in it).  A CSR of more than 2^30
+ * entries is refused with MGX_E_FRONTIER_OVERFLOW at the first run (the sort's merge passes keep run widths in ints; m_dag <= m, so
+ * m_dag < 2^31 always holds), no memory is MGX_E_HIP.  Every run starts afresh, on the
+ * context's stream. */
+MGX_API int mgx_tc_create(mgx_graph_t g, mgx_tc_t* out);
+MGX_API int mgx_tc_free(mgx_tc_t p);
+/* the fused path (mgx/tc_fused.hpp): rows binned by oriented length; short rows an entry a lane, longer ones staged in LDS by a
+ * wave or a workgroup while the rows of their entries are streamed; one host wait (the stats) */
+MGX_API int mgx_tc_run(mgx_tc_t p, int symmetric, int64_t* stats);
+/* the operator path (include/gunrock/tc/): one advance over the DAG's entries, a thread intersects the two rows of an entry */
+MGX_API int mgx_tc_enact(mgx_tc_t p, int symmetric, int64_t* stats);
+/* results of the last run of either path (MGX_E_INVALID before any run); the device pointers stay valid until the next run or free */
+MGX_API int mgx_tc_triangles(mgx_tc_t p, int64_t* host_tri);
+MGX_API int mgx_tc_triangles_device(mgx_tc_t p, const int64_t** d_tri);
+MGX_API int mgx_tc_simple_degrees(mgx_tc_t p, int* host_sdeg);
+MGX_API int mgx_tc_simple_degrees_device(mgx_tc_t p, const int** d_sdeg);
+/* which kernel the rows of the last run's DAG go to on the fused path, and the switches in effect (MGX_E_INVALID before any run):
+ * out[7] = rows counted an entry a lane, rows a wave stages, rows a workgroup stages (rows of fewer than two entries are in no
+ * list), entries of a workgroup's stage, entries of a wave's stage, MGX_TC_SHORT_MAX, MGX_TC_WAVE_MAX as read */
+MGX_API int mgx_tc_bins(mgx_tc_t p, int64_t* out);
+/* the last run's DAG: h_ro[n + 1], h_ci[stats[1]]; h_ci may be NULL to fetch the offsets only */
+MGX_API int mgx_tc_dag(mgx_tc_t p, int* h_ro, int* h_ci);
 
 /* ---- PageRank to convergence (mgx/pagerank_fused.hpp, include/gunrock/pagerank/) ----
  * Not mgx_pr_*: that is the reference's pr_enactor_t loop, kept quirk for quirk.  This is PageRank: CSR entry (u, v) is an edge

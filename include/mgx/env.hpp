@@ -54,6 +54,10 @@ inline const env_switch_t* env_switches(int* count) {
     {"MGX_SSSP_DENSE", "0 / N: no sweep for heavy iterations / an iteration is heavy from m / N frontier edges"},
     {"MGX_SSSP_HOT_MIN_EDGES", "smallest iteration that keeps the hubs' distance bounds in LDS (edges)"},
     {"MGX_SSSP_BUILD_LIST", "1: list-based queue build"},
+    // ---- triangle counting (tc_opts_t::from_env: read once per handle)
+    {"MGX_TC_SHORT_MAX", "oriented rows of at most N entries are counted an entry a lane (default 16)"},
+    {"MGX_TC_WAVE_MAX", "longer rows of at most N entries are staged in LDS by a wave, the rest by a workgroup (default 256)"},
+    {"MGX_TC_STAGE", "entries of an LDS stage; a longer row is staged in chunks (default and at most 4096; a wave's: 512)"},
     // ---- neighbour-reduce
     {"MGX_NR_SLICED", "0: the unit blocks instead of the long rows by slice of their destinations"},
     {"MGX_NR_SLICES", "number of hot slices (default: by graph size; at most what the id range holds)"},

@@ -223,6 +223,16 @@ SIGNATURES = {
     "mgx_cc_enact": [_vp, _pi64],
     "mgx_cc_labels": [_vp, _vp],
     "mgx_cc_labels_device": [_vp, _pvp],
+    "mgx_tc_create": [_vp, _pvp],
+    "mgx_tc_free": [_vp],
+    "mgx_tc_run": [_vp, _i, _pi64],
+    "mgx_tc_enact": [_vp, _i, _pi64],
+    "mgx_tc_triangles": [_vp, _vp],
+    "mgx_tc_triangles_device": [_vp, _pvp],
+    "mgx_tc_simple_degrees": [_vp, _vp],
+    "mgx_tc_simple_degrees_device": [_vp, _pvp],
+    "mgx_tc_dag": [_vp, _vp, _vp],
+    "mgx_tc_bins": [_vp, _pi64],
     "mgx_pagerank_create": [_vp, _pvp],
     "mgx_pagerank_free": [_vp],
     "mgx_pagerank_run": [_vp, C.c_double, C.c_double, _i, _i, _pi64, C.POINTER(C.c_double)],

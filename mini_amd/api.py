@@ -4,7 +4,7 @@ Names follow the reference (gunrock/src/*.hxx): Graph ~ graph_device_t, Frontier
 BfsProblem ~ bfs_problem_t + bfs_enactor_t, SsspProblem ~ sssp_problem_t + sssp_enactor_t,
 PrProblem ~ pr_problem_t + pr_enactor_t, KcoreProblem ~ kcore_problem_t + kcore_enactor_t,
 ColorProblem ~ coloring_problem_t + coloring_enactor_t, LsparProblem ~ lspar_problem_t + lspar_enactor_t,
-CcProblem ~ cc_problem_t + cc_enactor_t, PageRankProblem ~ pagerank_problem_t + pagerank_enactor_t.  Every method is one C-ABI call; nothing is computed here.
+CcProblem ~ cc_problem_t + cc_enactor_t, TcProblem ~ tc_problem_t + tc_enactor_t, PageRankProblem ~ pagerank_problem_t + pagerank_enactor_t.  Every method is one C-ABI call; nothing is computed here but TcProblem.clustering() / transitivity(), one numpy division on the counts.
 """
 import ctypes as C
 
@@ -769,6 +769,88 @@ class CcProblem:
     def close(self):
         if self._h:
             lib.mgx_cc_free(self._h)
+            self._h = None
+
+
+class TcProblem:
+    """Triangle counting: tc_problem_t + tc_enactor_t, and the fused path beside them.  triangles(), simple_degrees()
+    and dag() describe the last run of either path, on the underlying simple undirected graph, in original ids."""
+
+    KEYS = ("triangles", "edges", "max_row", "wedges", "rows_sorted", "built", "host_waits", "launches")
+
+    def __init__(self, graph):
+        h = C.c_void_p()
+        check(lib.mgx_tc_create(graph._h, C.byref(h)))
+        self.graph, self._h = graph, h
+
+    def _go(self, fn, symmetric):
+        st = (C.c_int64 * 8)()
+        check(fn(self._h, int(bool(symmetric)), st))
+        return dict(zip(self.KEYS, (int(x) for x in st)))
+
+    def run(self, symmetric=False):
+        """fused path -> {"triangles", "edges", "max_row", "wedges", "rows_sorted", "built", "host_waits", "launches"}.
+        symmetric=True is the caller's word that every entry has its reverse; False is right on any graph."""
+        return self._go(lib.mgx_tc_run, symmetric)
+
+    def enact(self, symmetric=False):
+        """operator path (one advance over the oriented graph, a thread per entry); the same stats"""
+        return self._go(lib.mgx_tc_enact, symmetric)
+
+    def triangles(self):
+        """tri[v]: the triangles that contain v (int64)"""
+        out = np.empty(self.graph.num_nodes, dtype=np.int64)
+        check(lib.mgx_tc_triangles(self._h, _ptr(out)))
+        return out
+
+    def simple_degrees(self):
+        """sdeg[v]: the distinct neighbours of v other than v (int32)"""
+        out = np.empty(self.graph.num_nodes, dtype=np.int32)
+        check(lib.mgx_tc_simple_degrees(self._h, _ptr(out)))
+        return out
+
+    def dag(self):
+        """(row_offsets, col_indices) of the oriented graph the last run counted on"""
+        ro = np.empty(self.graph.num_nodes + 1, dtype=np.int32)
+        check(lib.mgx_tc_dag(self._h, _ptr(ro), None))
+        ci = np.empty(max(int(ro[-1]), 1), dtype=np.int32)
+        check(lib.mgx_tc_dag(self._h, _ptr(ro), _ptr(ci)))
+        return ro, ci[:int(ro[-1])]
+
+    def bins(self):
+        """which kernel the last run's rows go to on the fused path, and the switches in effect"""
+        out = (C.c_int64 * 7)()
+        check(lib.mgx_tc_bins(self._h, out))
+        return dict(zip(("short_rows", "wave_rows", "block_rows", "block_stage", "wave_stage", "short_max", "wave_max"),
+                        (int(x) for x in out)))
+
+    def clustering(self):
+        """local clustering coefficient 2 tri / (sdeg (sdeg - 1)) as float64, 0 where sdeg < 2"""
+        tri, d = self.triangles().astype(np.float64), self.simple_degrees().astype(np.float64)
+        out = np.zeros(len(tri), dtype=np.float64)
+        ok = d >= 2
+        out[ok] = 2.0 * tri[ok] / (d[ok] * (d[ok] - 1.0))
+        return out
+
+    def transitivity(self):
+        """3 triangles / connected triples: sum of tri / sum of sdeg (sdeg - 1) / 2"""
+        tri, d = self.triangles(), self.simple_degrees().astype(np.int64)
+        triples = int((d * (d - 1) // 2).sum())
+        return float(int(tri.sum())) / triples if triples else 0.0
+
+    def triangles_device_ptr(self):
+        p = C.c_void_p()
+        check(lib.mgx_tc_triangles_device(self._h, C.byref(p)))
+        return p.value
+
+    def simple_degrees_device_ptr(self):
+        p = C.c_void_p()
+        check(lib.mgx_tc_simple_degrees_device(self._h, C.byref(p)))
+        return p.value
+
+    def close(self):
+        if self._h:
+            lib.mgx_tc_free(self._h)
             self._h = None
 
 

@@ -16,6 +16,7 @@
 #include "gunrock/pr/pr_enactor.hxx"
 #include "gunrock/kcore/kcore_enactor.hxx"
 #include "gunrock/sssp/sssp_enactor.hxx"
+#include "gunrock/tc/tc_enactor.hxx"
 #include "mgx/bfs_dist.hpp"
 #include "mgx/bfs_dist2.hpp"
 #include "mgx/cc_fused.hpp"
@@ -28,6 +29,7 @@
 #include "mgx/rmat.hpp"
 #include "mgx/sssp_fused.hpp"
 #include "mgx/sssp_preds.hpp"
+#include "mgx/tc_fused.hpp"
 #include "mgx.h"
 
 using namespace gunrock;
@@ -112,6 +114,13 @@ struct mgx_cc_s {
   std::unique_ptr<cc::cc_enactor_t> e;
   std::unique_ptr<mgx::cc_label_stats_t> label_stats;             // lazily: the operator path's stats
   const int* labels = nullptr;                                    // the last run's labels (nullptr: no run yet)
+};
+
+struct mgx_tc_s {
+  mgx_graph_t g = nullptr;
+  std::unique_ptr<mgx::tc_state_t> st;                            // lazily: the DAGs (per `symmetric`), their work lists, tri
+  std::shared_ptr<tc::tc_problem_t> p[2];                         // lazily: the operator path's view of dag[symmetric]
+  std::unique_ptr<tc::tc_enactor_t> e;
 };
 
 struct mgx_pagerank_s {
@@ -2518,6 +2527,129 @@ int mgx_cc_labels_device(mgx_cc_t p, const int** out) {
   MGX_REQUIRE(p && out, "NULL argument");
   MGX_REQUIRE(p->labels, "mgx_cc_labels_device: no run yet");
   *out = p->labels;
+  MGX_CATCH
+}
+
+// ---- triangle counting -------------------------------------------------------------
+int mgx_tc_create(mgx_graph_t g, mgx_tc_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(g && out, "NULL argument");
+  auto* h = new mgx_tc_s();
+  h->g = g;
+  *out = h;
+  MGX_CATCH
+}
+int mgx_tc_free(mgx_tc_t p) {
+  MGX_TRY
+  if (p) { use_device(p->g->c); p->g->c->ctx->synchronize(); delete p; }
+  MGX_CATCH
+}
+static void tc_stats(int64_t* stats, const std::vector<long long>& s) {
+  if (stats) for (int i = 0; i < 8; ++i) stats[i] = s[i];
+}
+static mgx::tc_state_t& tc_state(mgx_tc_t p) {
+  graph_device_t& g = *p->g->g;
+  if (!p->st) p->st.reset(new mgx::tc_state_t(g.num_nodes, g.num_edges, *p->g->c->ctx));
+  return *p->st;
+}
+int mgx_tc_run(mgx_tc_t p, int symmetric, int64_t* stats) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  use_device(p->g->c);
+  standard_context_t& ctx = *p->g->c->ctx;
+  graph_device_t& g = *p->g->g;
+  tc_stats(stats, tc_state(p).run(g.d_row_offsets.data(), g.d_col_indices.data(), symmetric != 0, ctx));
+  MGX_CATCH
+}
+int mgx_tc_enact(mgx_tc_t p, int symmetric, int64_t* stats) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  use_device(p->g->c);
+  standard_context_t& ctx = *p->g->c->ctx;
+  graph_device_t& g = *p->g->g;
+  mgx::tc_state_t& st = tc_state(p);
+  const int sym = symmetric != 0 ? 1 : 0;
+  st.launches = st.waits = 0;
+  st.last = -1;
+  if (st.n <= 0) { tc_stats(stats, {0, 0, 0, 0, sym, 0, 0, 0}); return MGX_OK; }
+  mgx::tc_dag_t& d = st.dag[sym];
+  bool built_now = false;
+  {
+    mgx::tc_build_tmp_t tmp;
+    built_now = st.ensure_dag(sym != 0, g.d_row_offsets.data(), g.d_col_indices.data(), tmp, ctx);
+    if (built_now) st.read_stats(d, true, ctx);        // (the operator needs m_dag on the host; the build's scratch goes behind the wait)
+  }
+  const hipStream_t s = ctx.stream();
+  // the operator's view of the DAG borrows its arrays: a new one whenever they are not the ones it holds (either path may have rebuilt)
+  std::shared_ptr<tc::tc_problem_t>& view = p->p[sym];
+  if (!view || view->gslice->d_row_offsets.data() != d.ro.data() || view->gslice->d_col_indices.data() != d.ci.data()) {
+    view = std::make_shared<tc::tc_problem_t>(d.ro.data(), d.ci.data(), st.n, (int)d.h[mgx::TC_S_MDAG], st.tri.data(), ctx);
+    ++st.waits;                                        // (its data slice goes up with a blocking copy)
+  }
+  if (!p->e) p->e.reset(new tc::tc_enactor_t(ctx, st.n));
+  MGX_HIP(hipMemsetAsync(st.tri.data(), 0, (size_t)st.n * sizeof(mgx::u64), s));
+  MGX_HIP(hipMemsetAsync(d.stat.data() + mgx::TC_S_TOTAL, 0, sizeof(mgx::u64), s));
+  p->e->enact(view, ctx);
+  st.waits += p->e->waits;
+  hipLaunchKernelGGL(mgx::k_tc_sum, dim3(grid_for(st.n, mgx::BLOCK, std::max(ctx.num_cus, 1) * 8)), dim3(mgx::BLOCK), 0, s,
+                     (const mgx::u64*)st.tri.data(), st.n, d.stat.data());
+  MGX_CHECK_LAUNCH("mgx tc enact");
+  // two clears, the degree scan over the n rows (one launch, or three above the look-back's tile limit), the expansion, the sum
+  st.launches += 2 + (mgx::scan_num_tiles(st.n) <= mgx::SCAN_LOOKBACK_MAX_TILES ? 1 : 3) + 1 + 1;
+  st.read_stats(d, false, ctx);
+  st.last = sym;
+  tc_stats(stats, st.result(d, d.h[mgx::TC_S_TOTAL] / 3, built_now));
+  MGX_CATCH
+}
+static mgx::tc_dag_t& tc_last(mgx_tc_t p, const char* who) {
+  MGX_REQUIRE(p->st && p->st->last >= 0, std::string(who) + ": no run yet");
+  return p->st->dag[p->st->last];
+}
+int mgx_tc_triangles(mgx_tc_t p, int64_t* host) {
+  MGX_TRY
+  MGX_REQUIRE(p && host, "NULL argument");
+  tc_last(p, "mgx_tc_triangles");
+  use_device(p->g->c);
+  MGX_HIP(mgx::dtoh((mgx::u64*)host, (const mgx::u64*)p->st->tri.data(), (size_t)p->st->n));
+  MGX_CATCH
+}
+int mgx_tc_triangles_device(mgx_tc_t p, const int64_t** out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  tc_last(p, "mgx_tc_triangles_device");
+  *out = (const int64_t*)p->st->tri.data();
+  MGX_CATCH
+}
+int mgx_tc_simple_degrees(mgx_tc_t p, int* host) {
+  MGX_TRY
+  MGX_REQUIRE(p && host, "NULL argument");
+  mgx::tc_dag_t& d = tc_last(p, "mgx_tc_simple_degrees");
+  use_device(p->g->c);
+  MGX_HIP(mgx::dtoh(host, (const int*)d.sdeg.data(), (size_t)p->st->n));
+  MGX_CATCH
+}
+int mgx_tc_simple_degrees_device(mgx_tc_t p, const int** out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  *out = tc_last(p, "mgx_tc_simple_degrees_device").sdeg.data();
+  MGX_CATCH
+}
+int mgx_tc_bins(mgx_tc_t p, int64_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  tc_last(p, "mgx_tc_bins");
+  use_device(p->g->c);
+  const std::vector<long long> b = p->st->bins(*p->g->c->ctx);
+  for (int i = 0; i < 7; ++i) out[i] = b[i];
+  MGX_CATCH
+}
+int mgx_tc_dag(mgx_tc_t p, int* h_ro, int* h_ci) {
+  MGX_TRY
+  MGX_REQUIRE(p && h_ro, "NULL argument");
+  mgx::tc_dag_t& d = tc_last(p, "mgx_tc_dag");
+  use_device(p->g->c);
+  MGX_HIP(mgx::dtoh(h_ro, (const int*)d.ro.data(), (size_t)p->st->n + 1));
+  if (h_ci) MGX_HIP(mgx::dtoh(h_ci, (const int*)d.ci.data(), (size_t)d.h[mgx::TC_S_MDAG]));
   MGX_CATCH
 }
 
