@@ -46,6 +46,7 @@ typedef struct mgx_color_s* mgx_color_t;
 typedef struct mgx_lspar_s* mgx_lspar_t;
 typedef struct mgx_cc_s* mgx_cc_t;
 typedef struct mgx_tc_s* mgx_tc_t;
+typedef struct mgx_bc_s* mgx_bc_t;
 typedef struct mgx_pagerank_s* mgx_pagerank_t;
 typedef struct mgx_dbfs_s* mgx_dbfs_t;
 typedef struct mgx_dbfs2_s* mgx_dbfs2_t;
@@ -633,6 +634,47 @@ MGX_API int mgx_tc_simple_degrees_device(mgx_tc_t p, const int** d_sdeg);
 MGX_API int mgx_tc_bins(mgx_tc_t p, int64_t* out);
 /* the last run's DAG: h_ro[n + 1], h_ci[stats[1]]; h_ci may be NULL to fetch the offsets only */
 MGX_API int mgx_tc_dag(mgx_tc_t p, int* h_ro, int* h_ci);
+
+/* ---- betweenness centrality (mgx/bc_fused.hpp, include/gunrock/bc/) ----
+ * Brandes on the unweighted graph: a CSR entry (u, v) is an edge u -> v, every entry counts once (duplicate entries are parallel
+ * edges and distinct shortest paths, as for mgx_pagerank_*), self-loops lie on no shortest path; original ids (an attached hub-first
+ * layout serves the traversal underneath, the centrality kernels ignore it).  For a source s: label = BFS depth (-1 unreached),
+ * sigma[v] = the shortest s -> v entry-paths (sigma[s] = 1), delta[v] = sum over the entries (v, w) with label[w] = label[v] + 1 of
+ * sigma[v] / sigma[w] * (1 + delta[w]), bc[v] = sum over the given sources s != v of delta_s[v] -- networkx.betweenness_centrality(
+ * DiGraph, normalized=False) when there are no duplicate entries and the sources are all vertices.  sigma, delta, bc are double;
+ * sigma is exact below 2^53.  sources == NULL: all n vertices (count is ignored); count < 0 or a source out of range: MGX_E_INVALID
+ * before any device work; count == 0: a valid run that leaves bc all zero.  symmetric != 0 is the caller's word that every entry has
+ * its reverse (the in-entries of v are then row v); symmetric = 0 takes the in-entries from the graph's genuine CSC
+ * (mgx_graph_build_csc, or one uploaded) and is MGX_E_INVALID without one (mgx_bc_run only: the operator path reads out-entries alone).
+ * stats (int64[10], may be NULL): [0] sources run, [1] the deepest traversal in levels, [2] vertices reached summed over the sources,
+ * [3] inexact: some sigma reached 2^53, [4] overflow: some sigma is not finite (neither is an error status), [5] host waits of the
+ * run's own, [6] the traversals' host waits (fused path), [7] launches of the run's own (kernels, clears, a sort as one; fused path),
+ * [8] chain launches, [9] 1 if the in-entries came from the CSC.  Every run starts afresh, on the context's stream. */
+MGX_API int mgx_bc_create(mgx_graph_t g, mgx_bc_t* out);
+MGX_API int mgx_bc_free(mgx_bc_t p);
+/* the fused path: per source the fused BFS (push mode), the level lists by one radix sort, then pull sweeps level by level -- no
+ * atomic, results bit-equal from run to run; ONE host wait of its own, at the end */
+MGX_API int mgx_bc_run(mgx_bc_t p, const int* sources, int count, int symmetric, int64_t* stats);
+/* the operator path: advance + filter per level with a CAS on the label and a double atomicAdd per shortest-path entry, one advance
+ * per level backwards */
+MGX_API int mgx_bc_enact(mgx_bc_t p, const int* sources, int count, int symmetric, int64_t* stats);
+/* results of the last run of either path (MGX_E_INVALID before any run): the centrality summed over the run's sources; sigma, delta
+ * and labels of its LAST source.  The device pointer stays valid until the next run or free */
+MGX_API int mgx_bc_centrality(mgx_bc_t p, double* host_bc);
+MGX_API int mgx_bc_centrality_device(mgx_bc_t p, const double** d_bc);
+MGX_API int mgx_bc_sigma(mgx_bc_t p, double* host_sigma);
+MGX_API int mgx_bc_delta(mgx_bc_t p, double* host_delta);
+MGX_API int mgx_bc_labels(mgx_bc_t p, int* host_labels);
+/* what the fused path did with the graph (MGX_E_INVALID before any run): out[16] = [0..2] vertices whose in-row is folded by a lane /
+ * a wave / in segments, [3..5] the same for the out-rows, [6] [7] segments of the huge in- / out-rows, [8..11] MGX_BC_LANE_MAX,
+ * MGX_BC_HUGE_MIN, MGX_BC_SEG, MGX_BC_CHAIN as read, [12] levels of the last source, [13] its chain launches, [14] [15] the longest
+ * in- / out-row.  [0..7], [14], [15] describe the last fused run's tables (0 before one) */
+MGX_API int mgx_bc_info(mgx_bc_t p, int64_t* out);
+/* measurement (tools/bc_bench.py): with timing on, a fused run puts HIP events around the phases of its first 64 sources (a few
+ * microseconds of stream gap each); mgx_bc_phase_ms then gives out[5] = ms per source of the traversal, the list build (clears, keys,
+ * sort, bounds), the forward launches, the backward launches (with the final sigma launch), and the number of sources timed */
+MGX_API int mgx_bc_set_timing(mgx_bc_t p, int on);
+MGX_API int mgx_bc_phase_ms(mgx_bc_t p, double* out);
 
 /* ---- PageRank to convergence (mgx/pagerank_fused.hpp, include/gunrock/pagerank/) ----
  * Not mgx_pr_*: that is the reference's pr_enactor_t loop, kept quirk for quirk.  This is PageRank: CSR entry (u, v) is an edge

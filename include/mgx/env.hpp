@@ -58,6 +58,11 @@ inline const env_switch_t* env_switches(int* count) {
     {"MGX_TC_SHORT_MAX", "oriented rows of at most N entries are counted an entry a lane (default 16)"},
     {"MGX_TC_WAVE_MAX", "longer rows of at most N entries are staged in LDS by a wave, the rest by a workgroup (default 256)"},
     {"MGX_TC_STAGE", "entries of an LDS stage; a longer row is staged in chunks (default and at most 4096; a wave's: 512)"},
+    // ---- betweenness centrality (bc_opts_t::from_env: read once per handle; all four defaults are unmeasured guesses)
+    {"MGX_BC_LANE_MAX", "rows of at most N entries are folded by one lane (default 16)"},
+    {"MGX_BC_HUGE_MIN", "rows of at least N entries are cut into segments folded by several workgroups, the rest by a wave (default 8192)"},
+    {"MGX_BC_SEG", "entries of a huge row's segment (default 8192)"},
+    {"MGX_BC_CHAIN", "0 / N: no chain / levels of at most N vertices in a row run in one workgroup's launch (default 1024)"},
     // ---- neighbour-reduce
     {"MGX_NR_SLICED", "0: the unit blocks instead of the long rows by slice of their destinations"},
     {"MGX_NR_SLICES", "number of hot slices (default: by graph size; at most what the id range holds)"},

@@ -233,6 +233,18 @@ SIGNATURES = {
     "mgx_tc_simple_degrees_device": [_vp, _pvp],
     "mgx_tc_dag": [_vp, _vp, _vp],
     "mgx_tc_bins": [_vp, _pi64],
+    "mgx_bc_create": [_vp, _pvp],
+    "mgx_bc_free": [_vp],
+    "mgx_bc_run": [_vp, _vp, _i, _i, _pi64],
+    "mgx_bc_enact": [_vp, _vp, _i, _i, _pi64],
+    "mgx_bc_centrality": [_vp, _vp],
+    "mgx_bc_centrality_device": [_vp, _pvp],
+    "mgx_bc_sigma": [_vp, _vp],
+    "mgx_bc_delta": [_vp, _vp],
+    "mgx_bc_labels": [_vp, _vp],
+    "mgx_bc_info": [_vp, _pi64],
+    "mgx_bc_set_timing": [_vp, _i],
+    "mgx_bc_phase_ms": [_vp, C.POINTER(C.c_double)],
     "mgx_pagerank_create": [_vp, _pvp],
     "mgx_pagerank_free": [_vp],
     "mgx_pagerank_run": [_vp, C.c_double, C.c_double, _i, _i, _pi64, C.POINTER(C.c_double)],

@@ -4,7 +4,7 @@ Names follow the reference (gunrock/src/*.hxx): Graph ~ graph_device_t, Frontier
 BfsProblem ~ bfs_problem_t + bfs_enactor_t, SsspProblem ~ sssp_problem_t + sssp_enactor_t,
 PrProblem ~ pr_problem_t + pr_enactor_t, KcoreProblem ~ kcore_problem_t + kcore_enactor_t,
 ColorProblem ~ coloring_problem_t + coloring_enactor_t, LsparProblem ~ lspar_problem_t + lspar_enactor_t,
-CcProblem ~ cc_problem_t + cc_enactor_t, TcProblem ~ tc_problem_t + tc_enactor_t, PageRankProblem ~ pagerank_problem_t + pagerank_enactor_t.  Every method is one C-ABI call; nothing is computed here but TcProblem.clustering() / transitivity(), one numpy division on the counts.
+CcProblem ~ cc_problem_t + cc_enactor_t, TcProblem ~ tc_problem_t + tc_enactor_t, BcProblem ~ bc_problem_t + bc_enactor_t, PageRankProblem ~ pagerank_problem_t + pagerank_enactor_t.  Every method is one C-ABI call; nothing is computed here but TcProblem.clustering() / transitivity(), one numpy division on the counts, and BcProblem.centrality()'s two scalings.
 """
 import ctypes as C
 
@@ -851,6 +851,100 @@ class TcProblem:
     def close(self):
         if self._h:
             lib.mgx_tc_free(self._h)
+            self._h = None
+
+
+class BcProblem:
+    """Betweenness centrality: bc_problem_t + bc_enactor_t, and the fused path beside them.  centrality() is the sum
+    over the last run's sources; sigma(), delta() and labels() describe its LAST source; original ids."""
+
+    KEYS = ("sources", "levels", "reached", "inexact", "overflow", "host_waits", "traversal_waits", "launches", "chain_launches",
+            "used_csc")
+    INFO = ("in_lane", "in_wave", "in_huge", "out_lane", "out_wave", "out_huge", "in_segments", "out_segments", "lane_max", "huge_min",
+            "seg", "chain", "levels", "chain_launches", "longest_in", "longest_out")
+
+    def __init__(self, graph):
+        h = C.c_void_p()
+        check(lib.mgx_bc_create(graph._h, C.byref(h)))
+        self.graph, self._h = graph, h
+        self._all = False
+
+    def _go(self, fn, sources, symmetric):
+        st = (C.c_int64 * 10)()
+        if sources is None:
+            check(fn(self._h, None, 0, int(bool(symmetric)), st))
+        else:
+            src = np.ascontiguousarray(sources, dtype=np.int32)
+            check(fn(self._h, _ptr(src), len(src), int(bool(symmetric)), st))
+        self._all = sources is None
+        return dict(zip(self.KEYS, (int(x) for x in st)))
+
+    def run(self, sources=None, symmetric=False):
+        """fused path -> the stats dict.  sources=None: every vertex.  symmetric=True is the caller's word that every entry has its
+        reverse; False needs the graph's genuine CSC (Graph.build_csc)."""
+        return self._go(lib.mgx_bc_run, sources, symmetric)
+
+    def enact(self, sources=None, symmetric=False):
+        """operator path (advance + filter per level, atomic adds); the same stats"""
+        return self._go(lib.mgx_bc_enact, sources, symmetric)
+
+    def _f64(self, fn):
+        out = np.empty(self.graph.num_nodes, dtype=np.float64)
+        check(fn(self._h, _ptr(out)))
+        return out
+
+    def centrality(self, normalized=False, undirected=False):
+        """bc[v] of the last run (float64).  normalized / undirected: networkx's two scalings for a run over all sources -- 1 / ((n - 1)
+        (n - 2)) and the halving of a graph whose every edge is stored in both directions."""
+        out = self._f64(lib.mgx_bc_centrality)
+        if normalized or undirected:
+            if not self._all:
+                raise ValueError("BcProblem.centrality: the scalings are defined for a run over all sources")
+            n = self.graph.num_nodes
+            if undirected:
+                out *= 0.5
+            if normalized:
+                out *= (2.0 if undirected else 1.0) / ((n - 1) * (n - 2)) if n > 2 else 0.0
+        return out
+
+    def sigma(self):
+        """shortest entry-paths from the last source (float64, 0 where unreached)"""
+        return self._f64(lib.mgx_bc_sigma)
+
+    def delta(self):
+        """the last source's dependencies (float64)"""
+        return self._f64(lib.mgx_bc_delta)
+
+    def labels(self):
+        """BFS depths from the last source (int32, -1 where unreached)"""
+        out = np.empty(self.graph.num_nodes, dtype=np.int32)
+        check(lib.mgx_bc_labels(self._h, _ptr(out)))
+        return out
+
+    def info(self):
+        """row classes, segments, switches as read, levels and chain launches of the last source"""
+        out = (C.c_int64 * 16)()
+        check(lib.mgx_bc_info(self._h, out))
+        return dict(zip(self.INFO, (int(x) for x in out)))
+
+    def set_timing(self, on=True):
+        """HIP events around the phases of the next fused runs (measurement only)"""
+        check(lib.mgx_bc_set_timing(self._h, int(bool(on))))
+
+    def phase_ms(self):
+        """ms per source of the last timed fused run: traversal, list build, forward, backward; and the sources timed"""
+        out = (C.c_double * 5)()
+        check(lib.mgx_bc_phase_ms(self._h, out))
+        return {"traversal": out[0], "lists": out[1], "forward": out[2], "backward": out[3], "sources_timed": int(out[4])}
+
+    def centrality_device_ptr(self):
+        p = C.c_void_p()
+        check(lib.mgx_bc_centrality_device(self._h, C.byref(p)))
+        return p.value
+
+    def close(self):
+        if self._h:
+            lib.mgx_bc_free(self._h)
             self._h = None
 
 

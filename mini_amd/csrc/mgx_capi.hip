@@ -8,6 +8,7 @@
 #include <memory>
 #include <string>
 
+#include "gunrock/bc/bc_enactor.hxx"
 #include "gunrock/bfs/bfs_enactor.hxx"
 #include "gunrock/cc/cc_enactor.hxx"
 #include "gunrock/coloring/coloring_enactor.hxx"
@@ -17,6 +18,7 @@
 #include "gunrock/kcore/kcore_enactor.hxx"
 #include "gunrock/sssp/sssp_enactor.hxx"
 #include "gunrock/tc/tc_enactor.hxx"
+#include "mgx/bc_fused.hpp"
 #include "mgx/bfs_dist.hpp"
 #include "mgx/bfs_dist2.hpp"
 #include "mgx/cc_fused.hpp"
@@ -121,6 +123,17 @@ struct mgx_tc_s {
   std::unique_ptr<mgx::tc_state_t> st;                            // lazily: the DAGs (per `symmetric`), their work lists, tri
   std::shared_ptr<tc::tc_problem_t> p[2];                         // lazily: the operator path's view of dag[symmetric]
   std::unique_ptr<tc::tc_enactor_t> e;
+};
+
+struct mgx_bc_s {
+  mgx_graph_t g = nullptr;
+  std::unique_ptr<mgx::bc_state_t> st;                            // lazily: the row classes, the level lists, P / Q, sigma, delta, bc
+  std::shared_ptr<bfs::bfs_problem_t> bp;                         // lazily: the traversal's labels (both paths write them)
+  std::unique_ptr<bfs::bfs_fused_enactor_t> fe;                   // lazily: the fused path's traversal
+  std::shared_ptr<bc::bc_problem_t> p;                            // lazily: the operator path's view of the same arrays
+  std::unique_ptr<bc::bc_enactor_t> e;
+  int last_sym = -1;                                              // `symmetric` of the last fused run (-1: none yet)
+  int last_levels = 0;                                            // levels of the last source of the last run
 };
 
 struct mgx_pagerank_s {
@@ -2650,6 +2663,206 @@ int mgx_tc_dag(mgx_tc_t p, int* h_ro, int* h_ci) {
   use_device(p->g->c);
   MGX_HIP(mgx::dtoh(h_ro, (const int*)d.ro.data(), (size_t)p->st->n + 1));
   if (h_ci) MGX_HIP(mgx::dtoh(h_ci, (const int*)d.ci.data(), (size_t)d.h[mgx::TC_S_MDAG]));
+  MGX_CATCH
+}
+
+// ---- betweenness centrality --------------------------------------------------------
+int mgx_bc_create(mgx_graph_t g, mgx_bc_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(g && out, "NULL argument");
+  auto* h = new mgx_bc_s();
+  h->g = g;
+  *out = h;
+  MGX_CATCH
+}
+int mgx_bc_free(mgx_bc_t p) {
+  MGX_TRY
+  if (p) { use_device(p->g->c); p->g->c->ctx->synchronize(); delete p; }
+  MGX_CATCH
+}
+// the checks both paths make before any device work; the sources as a list
+static std::vector<int> bc_sources(mgx_bc_t p, const int* sources, int count, const char* who) {
+  MGX_REQUIRE(p, "NULL argument");
+  const int n = p->g->g->num_nodes;
+  MGX_REQUIRE(count >= 0, std::string(who) + ": negative count");
+  std::vector<int> s;
+  if (!sources) {
+    s.resize((size_t)n);
+    for (int i = 0; i < n; ++i) s[(size_t)i] = i;
+  } else {
+    for (int i = 0; i < count; ++i) MGX_REQUIRE(sources[i] >= 0 && sources[i] < n, std::string(who) + ": source out of range");
+    s.assign(sources, sources + count);
+  }
+  return s;
+}
+static mgx::bc_state_t& bc_state(mgx_bc_t p) {
+  standard_context_t& ctx = *p->g->c->ctx;
+  if (!p->st) p->st.reset(new mgx::bc_state_t(p->g->g->num_nodes, ctx));
+  if (!p->bp) p->bp = std::make_shared<bfs::bfs_problem_t>(p->g->g, 0, ctx);
+  return *p->st;
+}
+static void bc_stats(int64_t* stats, const mgx::bc_state_t& st, const mgx::bc_ctrl_t& c, long long traversal_waits) {
+  if (!stats) return;
+  stats[0] = st.sources; stats[1] = c.deepest; stats[2] = st.reached; stats[3] = c.inexact ? 1 : 0; stats[4] = c.overflow ? 1 : 0;
+  stats[5] = st.waits; stats[6] = traversal_waits; stats[7] = st.launches; stats[8] = st.chain_launches; stats[9] = st.used_csc;
+}
+int mgx_bc_run(mgx_bc_t p, const int* sources, int count, int symmetric, int64_t* stats) {
+  MGX_TRY
+  const std::vector<int> srcs = bc_sources(p, sources, count, "mgx_bc_run");
+  MGX_REQUIRE(symmetric || !p->g->g->csc_is_csr, "mgx_bc_run: symmetric = 0 needs the graph's genuine CSC (mgx_graph_build_csc)");
+  use_device(p->g->c);
+  standard_context_t& ctx = *p->g->c->ctx;
+  graph_device_t& G = *p->g->g;
+  mgx::bc_state_t& st = bc_state(p);
+  const bool sym = symmetric != 0;
+  st.ensure_rows(sym, G.d_row_offsets.data(), G.d_col_indices.data(), G.d_col_offsets.data(), G.d_row_indices.data(), ctx);
+  if (!p->fe && G.num_edges > 0) p->fe.reset(new bfs::bfs_fused_enactor_t(ctx, G.num_nodes));
+  st.begin_run(sym, ctx);
+  long long traversal_waits = 0;
+  const std::vector<std::pair<long long, long long>> no_trace;
+  int* const labels = p->bp->d_labels.data();
+  for (size_t i = 0; i < srcs.size(); ++i) {
+    const int src = srcs[i];
+    st.mark(0, ctx.stream());
+    if (G.num_edges > 0) {
+      // the fused BFS in push mode; it waits for the host as it always does (and with that for the launches of the source before)
+      p->bp->src = src;
+      p->fe->fused->time_kernels = 0;
+      p->fe->enact(p->bp, ctx, false, 0.f);
+      traversal_waits += p->fe->fused->batches + (p->fe->last.levels > 64 ? 1 : 0);
+      st.reached += p->fe->last.reached;
+      st.source(labels, src, p->fe->last.levels, p->fe->last.trace, sym, ctx);
+    } else {                                                       // a graph without entries: the source alone
+      MGX_HIP(hipMemsetAsync(labels, 0xFF, (size_t)G.num_nodes * sizeof(int), ctx.stream()));
+      MGX_HIP(hipMemsetAsync(labels + src, 0, sizeof(int), ctx.stream()));
+      st.reached += 1;
+      st.source(labels, src, 0, no_trace, sym, ctx);
+    }
+  }
+  mgx::bc_ctrl_t c = {};
+  if (!srcs.empty()) c = st.end_run(ctx);
+  st.ran = true;
+  st.last_chain_launches = srcs.empty() ? 0 : st.last_chain_launches;
+  p->last_sym = sym ? 1 : 0;
+  p->last_levels = c.last_levels;
+  bc_stats(stats, st, c, traversal_waits);
+  MGX_CATCH
+}
+int mgx_bc_enact(mgx_bc_t p, const int* sources, int count, int symmetric, int64_t* stats) {
+  MGX_TRY
+  const std::vector<int> srcs = bc_sources(p, sources, count, "mgx_bc_enact");
+  (void)symmetric;                                                 // (the operator path reads the out-entries alone)
+  use_device(p->g->c);
+  standard_context_t& ctx = *p->g->c->ctx;
+  graph_device_t& G = *p->g->g;
+  mgx::bc_state_t& st = bc_state(p);
+  const int n = G.num_nodes;
+  if (!p->p) p->p = std::make_shared<bc::bc_problem_t>(p->g->g, p->bp->d_labels.data(), st.sigma.data(), const_cast<double*>(st.delta()), ctx);
+  if (!p->e) p->e.reset(new bc::bc_enactor_t(ctx, n, G.num_edges));
+  st.begin_run(true, ctx);
+  const bool was_timing = st.timing;
+  st.timing = false;                                               // (the phase events belong to the fused path)
+  st.launches = 0;                                                 // (the operators' launches are not counted)
+  p->e->waits = 0;
+  int deepest = 0, levels = 0;
+  double* const bcv = st.bc.data();
+  const double* const delta = st.delta();
+  const double* const sigma = st.sigma.data();
+  mgx::bc_ctrl_t* const dc = st.ctrl.data();
+  for (size_t i = 0; i < srcs.size(); ++i) {
+    levels = p->e->enact(p->p, srcs[i], ctx);
+    deepest = std::max(deepest, levels);
+    st.reached += (long long)p->e->level_off.back();
+    mgx::transform([=] __device__(int v) {
+      bcv[v] += delta[v];
+      const double s = sigma[v];
+      if (s >= mgx::BC_TWO53) dc->inexact = 1u;
+      if (!(s <= 1.7976931348623157e308)) dc->overflow = 1u;
+    }, n, ctx);
+    ++st.sources;
+  }
+  MGX_CHECK_LAUNCH("mgx bc enact");
+  mgx::bc_ctrl_t c = {};
+  if (!srcs.empty()) c = st.end_run(ctx);
+  st.ran = true;
+  st.timing = was_timing;
+  c.deepest = deepest;
+  p->last_levels = levels;
+  st.waits += p->e->waits;
+  bc_stats(stats, st, c, 0);
+  MGX_CATCH
+}
+static mgx::bc_state_t& bc_last(mgx_bc_t p, const char* who) {
+  MGX_REQUIRE(p->st && p->st->ran, std::string(who) + ": no run yet");
+  return *p->st;
+}
+int mgx_bc_centrality(mgx_bc_t p, double* host) {
+  MGX_TRY
+  MGX_REQUIRE(p && host, "NULL argument");
+  mgx::bc_state_t& st = bc_last(p, "mgx_bc_centrality");
+  use_device(p->g->c);
+  MGX_HIP(mgx::dtoh(host, (const double*)st.bc.data(), (size_t)st.n));
+  MGX_CATCH
+}
+int mgx_bc_centrality_device(mgx_bc_t p, const double** out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  *out = bc_last(p, "mgx_bc_centrality_device").bc.data();
+  MGX_CATCH
+}
+int mgx_bc_sigma(mgx_bc_t p, double* host) {
+  MGX_TRY
+  MGX_REQUIRE(p && host, "NULL argument");
+  mgx::bc_state_t& st = bc_last(p, "mgx_bc_sigma");
+  use_device(p->g->c);
+  MGX_HIP(mgx::dtoh(host, (const double*)st.sigma.data(), (size_t)st.n));
+  MGX_CATCH
+}
+int mgx_bc_delta(mgx_bc_t p, double* host) {
+  MGX_TRY
+  MGX_REQUIRE(p && host, "NULL argument");
+  mgx::bc_state_t& st = bc_last(p, "mgx_bc_delta");
+  use_device(p->g->c);
+  MGX_HIP(mgx::dtoh(host, st.delta(), (size_t)st.n));
+  MGX_CATCH
+}
+int mgx_bc_labels(mgx_bc_t p, int* host) {
+  MGX_TRY
+  MGX_REQUIRE(p && host, "NULL argument");
+  mgx::bc_state_t& st = bc_last(p, "mgx_bc_labels");
+  use_device(p->g->c);
+  MGX_HIP(mgx::dtoh(host, (const int*)p->bp->d_labels.data(), (size_t)st.n));
+  MGX_CATCH
+}
+int mgx_bc_set_timing(mgx_bc_t p, int on) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  use_device(p->g->c);
+  bc_state(p).timing = on != 0;
+  MGX_CATCH
+}
+int mgx_bc_phase_ms(mgx_bc_t p, double* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  mgx::bc_state_t& st = bc_last(p, "mgx_bc_phase_ms");
+  for (int k = 0; k < 4; ++k) out[k] = st.timed > 0 ? st.phase_ms[k] / st.timed : 0.0;
+  out[4] = (double)st.timed;
+  MGX_CATCH
+}
+int mgx_bc_info(mgx_bc_t p, int64_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  mgx::bc_state_t& st = bc_last(p, "mgx_bc_info");
+  for (int i = 0; i < mgx::BC_INFO_WORDS; ++i) out[i] = 0;
+  if (p->last_sym >= 0) {
+    const mgx::bc_rows_t& rin = p->last_sym ? st.rows_sym : st.rows[0];
+    const mgx::bc_rows_t& rout = p->last_sym ? st.rows_sym : st.rows[1];
+    for (int k = 0; k < 3; ++k) { out[k] = rin.count[k]; out[3 + k] = rout.count[k]; }
+    out[6] = rin.segments; out[7] = rout.segments;
+    out[14] = rin.longest; out[15] = rout.longest;
+  }
+  out[8] = st.opts.lane_max; out[9] = st.opts.huge_min; out[10] = st.opts.seg; out[11] = st.opts.chain;
+  out[12] = p->last_levels; out[13] = st.last_chain_launches;
   MGX_CATCH
 }
 

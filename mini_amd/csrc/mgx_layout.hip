@@ -893,3 +893,16 @@ extern "C" int mgx_nrs_build_device(const int* ro, const int* ci, int rows, unsi
   *mu = units; *off = offs; *total = (long long)M;
   return 0;
 }
+
+// ---- betweenness centrality: the level lists' sort (mgx/bc_fused.hpp) ---------------------------------------------------------
+// (key, id) pairs over the key bits [0, end_bit), stable, asynchronous on `stream`.  tmp == NULL: *tmp_bytes <- the scratch a sort
+// of n pairs needs (asked with the full key width: what the handle allocates once serves every depth).
+extern "C" int mgx_bc_sort_device(const unsigned* keys_in, unsigned* keys_out, const int* ids_in, int* ids_out, int n, int end_bit,
+                                  void* tmp, size_t* tmp_bytes, hipStream_t stream) {
+  if (!tmp_bytes) return (int)hipErrorInvalidValue;
+  if (n <= 0) { if (!tmp) *tmp_bytes = 0; return 0; }
+  size_t bytes = tmp ? *tmp_bytes : 0;
+  LAY_TRY(rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys_out, ids_in, ids_out, (size_t)n, 0u, (unsigned)end_bit, stream));
+  if (!tmp) *tmp_bytes = bytes;
+  return 0;
+}
