@@ -55,7 +55,12 @@ int neighborhood_kernel(std::shared_ptr<Problem> problem, std::shared_ptr<fronti
   // frontier costs).
   const bool full = frontier_size == (long long)graph.num_nodes;
   const bool subset = !full && frontier_size < (long long)graph.num_nodes && frontier_size * 8 >= (long long)graph.num_nodes && nr_subset_enabled();
-  if constexpr (sizeof(Value) == 4)     // (the kernel keeps 40 000 4-byte values in the 160 KB of LDS: wider values take the general path)
+  // what this call did, for mgx_graph_nr_last_call (host-side bookkeeping: nothing of it reaches a kernel)
+  auto& last = context.nr_last_call;
+  last.valid = true; last.body = 0; last.frontier = full ? 1 : subset ? 2 : 0; last.rejected = 0; last.edges = 0;
+  // (the kernel keeps 40 000 4-byte values in the 160 KB of LDS: wider values take the general path; so does an operator whose neutral
+  //  element is not known -- mgx::op_neutral -- since the layout's kernels fold padding entries and idle lanes)
+  if constexpr (sizeof(Value) == 4 && mgx::op_neutral<reduce_op, Value>::known)
   if (!has_output && is_pure_gather<Functor>::value && (full || subset) && frontier_size > 0 &&
       graph.has_layout && (push || graph.csc_is_csr) && graph.rows.ub.units > 0 && graph.rows.ub_min_degree == graph.rows.vs_long_min && graph.rows.vs_long_min >= 17 && graph.rows.vs_long_min <= 64 &&
       graph.rows.ub.cnt.size() && graph.rows.ub.first.size() && graph.rows.vs_dummy != 0 &&
@@ -108,7 +113,12 @@ int neighborhood_kernel(std::shared_ptr<Problem> problem, std::shared_ptr<fronti
       // (a subset call added its frontier's degrees to the context's counter whatever its verdict: the base follows)
       const unsigned long long before = context.nr_edges_base;
       if (subset) context.nr_edges_base = (unsigned long long)context.mailbox[9];
-      if (context.mailbox[8] == 1) return full ? (int)graph.num_edges : (int)(context.nr_edges_base - before);
+      if (context.mailbox[8] == 1) {
+        last.body = L.nrs_mu ? 2 : 1;
+        last.edges = full ? (long long)graph.num_edges : (long long)(context.nr_edges_base - before);
+        return (int)last.edges;
+      }
+      last.rejected = 1;
     }
   }
 
@@ -118,6 +128,7 @@ int neighborhood_kernel(std::shared_ptr<Problem> problem, std::shared_ptr<fronti
   long long edges = 0;
   mgx::transform_scan([=] __device__(long long i) { return offsets[frontier[i] + 1] - offsets[frontier[i]]; },
                       frontier_size, segment_start, context, &edges);
+  last.edges = edges;
   if (edges == 0) return 0;
   int* out = nullptr;
   if (has_output) {

@@ -169,6 +169,9 @@ MGX_API int mgx_lbs_expand_debug(mgx_graph_t g, mgx_frontier_t in, int64_t total
 MGX_API int mgx_compact_i32(mgx_ctx_t ctx, const int* d_in, int64_t n, int drop_value, int* d_out, int64_t* kept);
 /* neighborhood_kernel (neighborhood.hxx:12-70) with get_value_to_reduce = d_vertex_value[nbr]:
  * d_reduced[seg] = op over the segment's neighbours, identity for empty segments.
+ * The identity contract: a segment WITH neighbours receives the pure fold of their values -- `identity` is never mixed in,
+ * it need not be the operator's neutral element (a sentinel such as -1.0 for "no neighbours" under f32_plus is fine) --
+ * and a segment without neighbours receives `identity` itself.  The answer does not depend on which kernels ran.
  * push != 0 walks the CSR, 0 the CSC slots.                                             */
 MGX_API int mgx_segreduce_f32_plus(mgx_graph_t g, mgx_frontier_t in, int push,
                                    const float* d_vertex_value, float identity, float* d_reduced, int64_t* nonzeros);
@@ -176,6 +179,14 @@ MGX_API int mgx_segreduce_i32_min(mgx_graph_t g, mgx_frontier_t in, int push,
                                   const int* d_vertex_value, int identity, int* d_reduced, int64_t* nonzeros);
 MGX_API int mgx_segreduce_i32_max(mgx_graph_t g, mgx_frontier_t in, int push,
                                   const int* d_vertex_value, int identity, int* d_reduced, int64_t* nonzeros);
+/* What the last neighbourhood reduce on the graph's context did (mgx_segreduce_*, and the operator calls of mgx_pr_enact,
+ * the colouring and lspar enactors); MGX_E_INVALID before any such call.
+ *   out4[0]  body: 0 the general LBS kernel, 1 the layout with its unit blocks, 2 the layout with the sliced long rows
+ *   out4[1]  the frontier as the host classified it: 0 other, 1 full (n ids), 2 subset (n / 8 <= ids < n)
+ *   out4[2]  1 if the layout's kernels were entered but the device's verdict on the frontier (not 0 .. n - 1, not strictly
+ *            ascending) sent the call to the general kernel; out4[0] is then 0
+ *   out4[3]  edges returned                                                              */
+MGX_API int mgx_graph_nr_last_call(mgx_graph_t g, int64_t* out4);
 
 /* ---- BFS: bfs_problem_t / bfs_functor_t / bfs_enactor_t (gunrock/src/bfs/) ---- */
 MGX_API int mgx_bfs_create(mgx_graph_t g, int src, mgx_bfs_t* out);       /* bfs_problem.hxx:34-46 */

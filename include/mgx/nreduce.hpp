@@ -21,6 +21,8 @@
 //                 Short rows: 1 .. 63 entries by degree class as in bfs_fused_vshort.hpp: 16 / 4 / 1 lanes per vertex, one
 //                 unaligned 16-byte load of four entries per lane, fold by shuffles.
 // Results go to reduced[old_of_new[v]] -- the frontier POSITION of vertex v in an iota frontier (neighborhood.hxx:58).
+// The caller's identity reaches k_nr_values only (empty rows); the `identity` parameter of every kernel behind it is given the
+// operator's neutral element (nr_full_frontier), so a result is the pure fold of its row whatever identity the caller names.
 // Float sums are folded in a different order than the general kernel's (both are deterministic; the reference's own
 // order is moderngpu's and unpinned): the tests compare with 2e-5 relative.
 #pragma once
@@ -609,6 +611,12 @@ template <typename V, typename Op, typename GetValue>
 inline long long nr_full_frontier(const nr_layout_t& L_in, GetValue get, V* reduced, V identity, Op op, standard_context_t& ctx, const int* frontier,
                              long long* host_flag, u32* dev_flag, u32 epoch, long long nf = -1, const int* offsets = nullptr, u64* pos = nullptr) {
   static_assert(sizeof(V) == 4, "the full-frontier neighbour-reduce is instantiated for 4-byte values only (neighborhood.hxx gates on it)");
+  static_assert(op_neutral<Op, V>::known, "the layout's kernels fold padding entries and idle lanes: they need the operator's neutral element (runtime.hpp: op_neutral)");
+  // The caller's `identity` is what an EMPTY row receives (k_nr_values / k_nr_values_subset store it; nothing else writes a row without
+  // entries: the short rows' classes end at degree 1, the folds cover the long rows only) and is never folded into a result.  What the
+  // kernels behind take in their `identity` parameter -- padding entries, lanes past a row's end, the accumulators' start -- is the
+  // operator's NEUTRAL element: a kernel argument like before, the same code.
+  const V neutral = op_neutral<Op, V>::value();
   hipStream_t s = ctx.stream();
   ++ctx.scratch_epoch;
   nr_layout_t L = L_in;
@@ -641,24 +649,24 @@ inline long long nr_full_frontier(const nr_layout_t& L_in, GetValue get, V* redu
     if (device_once_t once{seen_s})
       MGX_HIP(hipFuncSetAttribute((const void*)(k_nrs_edges<V, Op, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     hipLaunchKernelGGL((k_nrs_edges<V, Op, 1024>), dim3(ctx.num_cus), dim3(1024), nr_lds_bytes(), s, L, (const V*)vals, partial, reduced,
-                       identity, op, dev_flag, epoch);
+                       neutral, op, dev_flag, epoch);
     const u32 grid = L.nrs_tier[0] + (L.nrs_tier[1] - L.nrs_tier[0] + BLOCK / WAVE - 1) / (BLOCK / WAVE) + (L.nrs_tier[2] - L.nrs_tier[1] + BLOCK / 8 - 1) / (BLOCK / 8) +
                      (L.nrs_rows - L.nrs_tier[2] + BLOCK - 1) / BLOCK;
     if (grid && L.nrs_slices + 1u <= (u32)NRS_FOLD_CHUNK)
-      hipLaunchKernelGGL((k_nrs_fold<V, Op, false>), dim3(grid), dim3(BLOCK), 0, s, L, (const V*)partial, reduced, identity, op, dev_flag, epoch);
+      hipLaunchKernelGGL((k_nrs_fold<V, Op, false>), dim3(grid), dim3(BLOCK), 0, s, L, (const V*)partial, reduced, neutral, op, dev_flag, epoch);
     else if (grid)
-      hipLaunchKernelGGL((k_nrs_fold<V, Op, true>), dim3(grid), dim3(BLOCK), 0, s, L, (const V*)partial, reduced, identity, op, dev_flag, epoch);
+      hipLaunchKernelGGL((k_nrs_fold<V, Op, true>), dim3(grid), dim3(BLOCK), 0, s, L, (const V*)partial, reduced, neutral, op, dev_flag, epoch);
     return seq;
   }
   const u32 long_rows = L.vs_v[0];
   const bool has_long = L.ub_units > 0 && long_rows > 0, has_short = L.vs_v[3] > L.vs_v[0];
   if (has_long || has_short)
     hipLaunchKernelGGL((k_nr_edges<V, Op, 1024>), dim3(ctx.num_cus), dim3(1024), nr_lds_bytes(), s, L, (const V*)vals, partial, reduced,
-                       identity, op, dev_flag, epoch);
+                       neutral, op, dev_flag, epoch);
   if (has_long) {
     const u32 rest = long_rows > L.big_rows ? long_rows - L.big_rows : 0u;
     const u32 grid = L.big_rows + (rest + BLOCK - 1) / BLOCK;
-    if (grid) hipLaunchKernelGGL((k_nr_fold<V, Op>), dim3(grid), dim3(BLOCK), 0, s, L, (const V*)partial, reduced, identity, op, long_rows, dev_flag, epoch);
+    if (grid) hipLaunchKernelGGL((k_nr_fold<V, Op>), dim3(grid), dim3(BLOCK), 0, s, L, (const V*)partial, reduced, neutral, op, long_rows, dev_flag, epoch);
   }
   return seq;
 }

@@ -16,6 +16,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <exception>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -164,6 +165,15 @@ struct standard_context_t : context_t {
   // held before the call in flight)
   unsigned long long* nr_edges() const { return (unsigned long long*)(lookback_ticket + 12); }
   unsigned long long nr_edges_base = 0;
+  // what the last neighborhood_kernel call on this context did (gunrock/neighborhood.hxx writes it on the host, behind its own wait;
+  // mgx_graph_nr_last_call reads it).  body: 0 the general LBS kernel, 1 the layout's unit blocks, 2 the layout's sliced long rows;
+  // frontier: 0 other, 1 full, 2 subset (as the host classified it); rejected: the layout's kernels were enqueued but the device's
+  // verdict on the frontier sent the call to the general kernel (body is then 0); edges: what the call returned
+  struct nr_last_call_t {
+    bool valid = false;
+    int body = 0, frontier = 0, rejected = 0;
+    long long edges = 0;
+  } nr_last_call;
   unsigned next_nr_epoch() {
     if (++nr_epoch == 0u) nr_epoch = 1u;      // (2^32 calls: a stale word could only name the call 2^32 - 1 before this one)
     return nr_epoch;
@@ -372,6 +382,28 @@ inline mem_t<T> fill_function(F f, size_t n, context_t& c) {
 template <typename T> struct plus_t    { __host__ __device__ T operator()(T a, T b) const { return a + b; } };
 template <typename T> struct maximum_t { __host__ __device__ T operator()(T a, T b) const { return a > b ? a : b; } };
 template <typename T> struct minimum_t { __host__ __device__ T operator()(T a, T b) const { return a < b ? a : b; } };
+
+// The NEUTRAL element of an operator: op(x, neutral) == x for every x.  The neighbour-reduce's layout kernels (nreduce.hpp) fill
+// padding entries, idle lanes and accumulators with it; the caller's `identity` is only what an EMPTY segment receives and is never
+// folded into a result.  An operator without a specialisation takes the general kernel (gunrock/neighborhood.hxx).
+// (floating-point plus: -0.0, the one value that leaves +0.0 and -0.0 both as they are)
+template <typename Op, typename V>
+struct op_neutral { static constexpr bool known = false; };
+template <typename T>
+struct op_neutral<plus_t<T>, T> {
+  static constexpr bool known = true;
+  static constexpr T value() { return std::numeric_limits<T>::is_iec559 ? -T(0) : T(0); }
+};
+template <typename T>
+struct op_neutral<minimum_t<T>, T> {
+  static constexpr bool known = true;
+  static constexpr T value() { return std::numeric_limits<T>::has_infinity ? std::numeric_limits<T>::infinity() : std::numeric_limits<T>::max(); }
+};
+template <typename T>
+struct op_neutral<maximum_t<T>, T> {
+  static constexpr bool known = true;
+  static constexpr T value() { return std::numeric_limits<T>::has_infinity ? -std::numeric_limits<T>::infinity() : std::numeric_limits<T>::lowest(); }
+};
 
 template <typename T>
 __device__ __forceinline__ T ldg(const T* p) { return *p; }   // no read-only path on CDNA

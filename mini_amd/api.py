@@ -119,6 +119,14 @@ class Graph:
         keys = ("mini_units", "hot_slices", "long_rows", "multi_lane_fold_rows", "tail_mini_units")
         return dict(zip(keys, (int(x) for x in out)))
 
+    def nr_last_call(self):
+        """what the last neighbourhood reduce on this graph's context did (mgx_graph_nr_last_call; MgxError before any): body 0 the
+        general kernel / 1 the layout's unit blocks / 2 the layout's sliced long rows, frontier 0 other / 1 full / 2 subset, rejected
+        1 if the device's verdict on the frontier sent a layout call to the general kernel, and the edges the call returned"""
+        out = (C.c_int64 * 4)()
+        check(lib.mgx_graph_nr_last_call(self._h, out))
+        return dict(zip(("body", "frontier", "rejected", "edges"), (int(x) for x in out)))
+
     def build_csc(self):
         """Genuine CSC (transpose) built by the library on the device (mgx_graph_build_csc): in-edges for the bottom-up
         levels on directed graphs."""

@@ -718,6 +718,14 @@ int mgx_graph_nr_slices_info(mgx_graph_t g, int64_t* out5) {
   out5[4] = G.nrs_units > 0 ? (int64_t)(G.nrs_first[G.nrs_slices + 1] - G.nrs_first[G.nrs_slices]) : 0;
   MGX_CATCH
 }
+int mgx_graph_nr_last_call(mgx_graph_t g, int64_t* out4) {
+  MGX_TRY
+  MGX_REQUIRE(g && out4, "NULL argument");
+  const auto& last = g->c->ctx->nr_last_call;
+  MGX_REQUIRE(last.valid, "mgx_graph_nr_last_call: no neighbourhood reduce on this context yet");
+  out4[0] = last.body; out4[1] = last.frontier; out4[2] = last.rejected; out4[3] = (int64_t)last.edges;
+  MGX_CATCH
+}
 int mgx_graph_layout_read(mgx_graph_t g, int* h_row_offsets, int* h_col_indices, int* h_new_of_old, int* h_old_of_new,
                           float* h_weights) {
   MGX_TRY

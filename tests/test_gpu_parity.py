@@ -146,12 +146,19 @@ def test_neighbour_reduce_full_frontier_on_the_layout(gpu_ctx, oracle, torch_mod
     short ones, hub values in LDS) -- taken when the frontier is 0 .. n - 1 and the graph carries the library's hub-first
     layout -- against the oracle's serial restatement: exact for int min / max and for float sums of small integers, 2e-5
     relative for real-valued floats (the fold order differs); a permuted frontier of the same size takes the general
-    kernel and is compared the same way; R-MAT 16 has rows of more than 4096 entries (a workgroup per row)"""
+    kernel and is compared the same way; R-MAT 16 has rows of more than 4096 entries (a workgroup per row -- of k_nr_fold, the unit
+    blocks' fold: since the long rows are sliced by destination that kernel runs only under MGX_NR_SLICED=0, which is read once per
+    process; tests/test_gpu_nreduce_paths.py runs it in a child interpreter.  What runs here is asserted below: body 2, the sliced
+    long rows, for the iota on all three graphs, and the device's verdict for the permutation)"""
     import mini_amd
     torch = torch_mod
     n, ro, ci, w = oracle.rmat_csr(scale, ef, 60 + scale)
     g = _graph(gpu_ctx, ro, ci).build_layout()
     rng = np.random.default_rng(scale)
+
+    def on_path(kind):
+        info = g.nr_last_call()
+        assert info == {"body": 2 if kind == "iota" else 0, "frontier": 1, "rejected": 0 if kind == "iota" else 1, "edges": len(ci)}, (kind, info)
     for frontier_kind in ("iota", "permuted"):
         ids = np.arange(n, dtype=np.int32) if frontier_kind == "iota" else rng.permutation(n).astype(np.int32)
         f = mini_amd.Frontier(gpu_ctx, n).load(ids)
@@ -161,6 +168,7 @@ def test_neighbour_reduce_full_frontier_on_the_layout(gpu_ctx, oracle, torch_mod
                 dv = torch.from_numpy(vals).cuda()
                 red = torch.full((n,), -1, dtype=torch.float32, device="cuda")
                 nz = mini_amd.segreduce(g, f, dv, 0.0, red, op)
+                on_path(frontier_kind)
                 want, wnz = oracle.neighbor_reduce_f32_plus(ro, ci, ids, vals, 0.0)
                 assert nz == wnz == len(ci)
                 got = red.cpu().numpy()
@@ -174,6 +182,7 @@ def test_neighbour_reduce_full_frontier_on_the_layout(gpu_ctx, oracle, torch_mod
             ident = 2**31 - 1 if op == "i32_min" else -2**31
             red = torch.full((n,), 12345, dtype=torch.int32, device="cuda")
             nz = mini_amd.segreduce(g, f, dv, ident, red, op)
+            on_path(frontier_kind)
             want, wnz = oracle.neighbor_reduce_i32(ro, ci, ids, vals, ident, op == "i32_max")
             assert nz == wnz
             assert np.array_equal(red.cpu().numpy(), want), frontier_kind
@@ -206,6 +215,15 @@ def test_neighbour_reduce_subset_frontier_on_the_layout(gpu_ctx, oracle, torch_m
     }
     dup = np.sort(rng.permutation(n)[: n // 2]); dup[5] = dup[4]    # a duplicate: not STRICTLY ascending
     kinds["duplicate"] = dup
+
+    def on_path(kind, ids):
+        # the layout's kernels (body 2: the sliced long rows) for an ascending subset of at least n / 8 ids; the general kernel below
+        # that, and after the device's verdict on a frontier out of order or with a duplicate
+        info = g.nr_last_call()
+        big = len(ids) * 8 >= n
+        rejected = int(big and kind in ("shuffled", "duplicate"))
+        want = {"body": 2 if big and not rejected else 0, "frontier": 2 if big else 0, "rejected": rejected, "edges": int(deg[ids].sum())}
+        assert len(ids) < n and info == want, (kind, info, want)
     for kind, ids in kinds.items():
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         f = mini_amd.Frontier(gpu_ctx, n).load(ids)
@@ -215,6 +233,7 @@ def test_neighbour_reduce_subset_frontier_on_the_layout(gpu_ctx, oracle, torch_m
                 dv = torch.from_numpy(vals).cuda()
                 red = torch.full((len(ids),), -1, dtype=torch.float32, device="cuda")
                 nz = mini_amd.segreduce(g, f, dv, 0.0, red, op)
+                on_path(kind, ids)
                 want, wnz = oracle.neighbor_reduce_f32_plus(ro, ci, ids, vals, 0.0)
                 assert nz == wnz, kind
                 got = red.cpu().numpy()
@@ -228,6 +247,7 @@ def test_neighbour_reduce_subset_frontier_on_the_layout(gpu_ctx, oracle, torch_m
             ident = 2**31 - 1 if op == "i32_min" else -2**31
             red = torch.full((len(ids),), 12345, dtype=torch.int32, device="cuda")
             nz = mini_amd.segreduce(g, f, dv, ident, red, op)
+            on_path(kind, ids)
             want, wnz = oracle.neighbor_reduce_i32(ro, ci, ids, vals, ident, op == "i32_max")
             assert nz == wnz, kind
             assert np.array_equal(red.cpu().numpy(), want), kind
