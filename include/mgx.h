@@ -48,6 +48,7 @@ typedef struct mgx_cc_s* mgx_cc_t;
 typedef struct mgx_tc_s* mgx_tc_t;
 typedef struct mgx_bc_s* mgx_bc_t;
 typedef struct mgx_pagerank_s* mgx_pagerank_t;
+typedef struct mgx_mst_s* mgx_mst_t;
 typedef struct mgx_dbfs_s* mgx_dbfs_t;
 typedef struct mgx_dbfs2_s* mgx_dbfs2_t;
 typedef struct mgx_dsssp_s* mgx_dsssp_t;
@@ -714,6 +715,42 @@ MGX_API int mgx_pagerank_ranks(mgx_pagerank_t p, float* host_ranks);
 MGX_API int mgx_pagerank_ranks_device(mgx_pagerank_t p, const float** d_ranks);
 /* e_1 .. of the last run: min(cap, iterations, 65536) values into host_e; *iterations (may be NULL) = iterations run */
 MGX_API int mgx_pagerank_residuals(mgx_pagerank_t p, double* host_e, int cap, int* iterations);
+
+/* ---- minimum spanning forest (include/mgx/mst_fused.hpp, include/gunrock/mst/) ----
+ * Every CSR entry (v, u, w) is the undirected edge {v, u} of the graph's float weight w (1.0f when none were uploaded); self-loops
+ * are ignored, parallel entries are parallel edges, a vertex without entries is a tree of its own.  Weights are ordered by
+ * key(w) = b ^ (b >> 31 ? 0xFFFFFFFF : 0x80000000) of their IEEE bits b, -0.0 read as +0.0 (and reported as +0.0); negative weights
+ * are allowed; a NaN weight makes the run MGX_E_INVALID, found at the run's host wait, and leaves no result.  Edges are ordered by
+ * (key(w), min(v, u), max(v, u)), entries with the same triple are the same edge: the minimum spanning forest is unique and both
+ * paths return the same set of (a, b, w), a < b.  The fused path's list order is a function of the graph alone (ascending position
+ * in its sorted incident arrays), list and total are bit-equal from run to run; the operator path's list order is not specified.
+ * symmetric != 0 is the caller's word that every entry has its reverse with the same weight; symmetric == 0 takes the in-entries
+ * from the graph's genuine CSC (mgx_graph_build_csc, or one uploaded; row values included) and is MGX_E_INVALID without one, on both
+ * paths.  A false word may give a wrong forest; it never hangs or faults.
+ * stats (may be NULL), int64[8]: [0] edges (n - components), [1] components, [2] size of the largest, [3] its label, [4] rounds that
+ * chose something, [5] host waits the run made (fused: counted where the host waits; operator path: one per operator call, each
+ * reads its count back, plus the read-backs at the end), [6] cursor steps summed (fused: entries a lane looked at plus 64-entry steps of a
+ * wave; 0 on the operator path), [7] incident entries after dropping self-loops (both ends' when symmetric == 0).  A graph of more
+ * than 2^29 entries is MGX_E_FRONTIER_OVERFLOW.  Every run starts afresh, on the context's stream; the fused path keeps its sorted
+ * incident arrays per `symmetric` on the handle. */
+MGX_API int mgx_mst_create(mgx_graph_t g, mgx_mst_t* out);
+MGX_API int mgx_mst_free(mgx_mst_t p);
+/* the fused path: Boruvka rounds with a monotone cursor per vertex; one host wait whatever the number of rounds */
+MGX_API int mgx_mst_run(mgx_mst_t p, int symmetric, int64_t* stats);
+/* the operator path: two advances and a hook filter per round over all entries, pointer-jumping filters; the host loops */
+MGX_API int mgx_mst_enact(mgx_mst_t p, int symmetric, int64_t* stats);
+/* results of the last run of either path (MGX_E_INVALID before any run, and after one that failed): stats[0] entries each, any of
+ * the arrays may be NULL; the total weight, summed in double in an order fixed by the list; labels[v] = the smallest vertex id of
+ * v's component.  Device pointers stay valid until the next run or free. */
+MGX_API int mgx_mst_edges(mgx_mst_t p, int* h_a, int* h_b, float* h_w);
+MGX_API int mgx_mst_edges_device(mgx_mst_t p, const int** d_a, const int** d_b, const float** d_w);
+MGX_API int mgx_mst_weight(mgx_mst_t p, double* total);
+MGX_API int mgx_mst_labels(mgx_mst_t p, int* host_labels);
+MGX_API int mgx_mst_labels_device(mgx_mst_t p, const int** d_labels);
+/* the last fused run (MGX_E_INVALID before one): out8 = [0] long-row items processed over all rounds (a wave each), [1] short-row
+ * items (a lane each), [2] MGX_MST_LONG_MIN in effect, [3] MGX_MST_SEG in effect, [4] merge passes of the setup sort, [5] 1 if the
+ * setup was reused, [6] [7] 0 */
+MGX_API int mgx_mst_info(mgx_mst_t p, int64_t* out8);
 
 /* ---- segmented sort (mgpu::segmented_sort, lspar_enactor.hxx:85; mgx/segsort.hpp) ----
  * Sorts d_keys[0, count) (and d_vals with them; NULL: keys only) in place, stably, ascending or descending, within segments:

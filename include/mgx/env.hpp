@@ -63,6 +63,9 @@ inline const env_switch_t* env_switches(int* count) {
     {"MGX_BC_HUGE_MIN", "rows of at least N entries are cut into segments folded by several workgroups, the rest by a wave (default 8192)"},
     {"MGX_BC_SEG", "entries of a huge row's segment (default 8192)"},
     {"MGX_BC_CHAIN", "0 / N: no chain / levels of at most N vertices in a row run in one workgroup's launch (default 1024)"},
+    // ---- minimum spanning forest (mst_opts_t::from_env: read per run; both defaults are unmeasured guesses)
+    {"MGX_MST_LONG_MIN", "rows with at least N entries left behind the cursor are scanned by a wave, 64 entries a step (default 64)"},
+    {"MGX_MST_SEG", "entries of a long row's window, a wave each; rounded up to a multiple of 64 (default 2048)"},
     // ---- neighbour-reduce
     {"MGX_NR_SLICED", "0: the unit blocks instead of the long rows by slice of their destinations"},
     {"MGX_NR_SLICES", "number of hot slices (default: by graph size; at most what the id range holds)"},

@@ -253,6 +253,16 @@ SIGNATURES = {
     "mgx_pagerank_ranks": [_vp, _vp],
     "mgx_pagerank_ranks_device": [_vp, _pvp],
     "mgx_pagerank_residuals": [_vp, C.POINTER(C.c_double), _i, _pi],
+    "mgx_mst_create": [_vp, _pvp],
+    "mgx_mst_free": [_vp],
+    "mgx_mst_run": [_vp, _i, _pi64],
+    "mgx_mst_enact": [_vp, _i, _pi64],
+    "mgx_mst_edges": [_vp, _vp, _vp, _vp],
+    "mgx_mst_edges_device": [_vp, _pvp, _pvp, _pvp],
+    "mgx_mst_weight": [_vp, C.POINTER(C.c_double)],
+    "mgx_mst_labels": [_vp, _vp],
+    "mgx_mst_labels_device": [_vp, _pvp],
+    "mgx_mst_info": [_vp, _pi64],
     "mgx_rmat_edges": [_vp, _i, _i64, _i64, _u64, _i, _vp, _vp, _vp],
 }
 _RESTYPES = {"mgx_comm_library": C.c_char_p, "mgx_strerror": C.c_char_p, "mgx_last_error": C.c_char_p, "mgx_host_free": None}

@@ -4,7 +4,7 @@ Names follow the reference (gunrock/src/*.hxx): Graph ~ graph_device_t, Frontier
 BfsProblem ~ bfs_problem_t + bfs_enactor_t, SsspProblem ~ sssp_problem_t + sssp_enactor_t,
 PrProblem ~ pr_problem_t + pr_enactor_t, KcoreProblem ~ kcore_problem_t + kcore_enactor_t,
 ColorProblem ~ coloring_problem_t + coloring_enactor_t, LsparProblem ~ lspar_problem_t + lspar_enactor_t,
-CcProblem ~ cc_problem_t + cc_enactor_t, TcProblem ~ tc_problem_t + tc_enactor_t, BcProblem ~ bc_problem_t + bc_enactor_t, PageRankProblem ~ pagerank_problem_t + pagerank_enactor_t.  Every method is one C-ABI call; nothing is computed here but TcProblem.clustering() / transitivity(), one numpy division on the counts, and BcProblem.centrality()'s two scalings.
+CcProblem ~ cc_problem_t + cc_enactor_t, TcProblem ~ tc_problem_t + tc_enactor_t, BcProblem ~ bc_problem_t + bc_enactor_t, MstProblem ~ mst_problem_t + mst_enactor_t, PageRankProblem ~ pagerank_problem_t + pagerank_enactor_t.  Every method is one C-ABI call; nothing is computed here but TcProblem.clustering() / transitivity(), one numpy division on the counts, and BcProblem.centrality()'s two scalings.
 """
 import ctypes as C
 
@@ -777,6 +777,78 @@ class CcProblem:
     def close(self):
         if self._h:
             lib.mgx_cc_free(self._h)
+            self._h = None
+
+
+class MstProblem:
+    """Minimum spanning forest: mst_problem_t + mst_enactor_t, and the fused path beside them.  Every CSR entry
+    (v, u, w) is the undirected edge {v, u}; edges are ordered by (key(w), min, max), so the forest is unique.  edges(), weight() and
+    labels() describe the last run of either path."""
+
+    KEYS = ("edges", "components", "largest", "largest_label", "rounds", "host_waits", "cursor_steps", "entries")
+    INFO = ("long_items", "short_items", "long_min", "seg", "merge_passes", "setup_reused")
+
+    def __init__(self, graph):
+        h = C.c_void_p()
+        check(lib.mgx_mst_create(graph._h, C.byref(h)))
+        self.graph, self._h = graph, h
+        self._edges = None
+
+    def _go(self, fn, symmetric):
+        st = (C.c_int64 * 8)()
+        self._edges = None
+        check(fn(self._h, int(bool(symmetric)), st))
+        self._edges = int(st[0])
+        return dict(zip(self.KEYS, (int(x) for x in st)))
+
+    def run(self, symmetric=False):
+        """fused path -> the stats dict.  symmetric=True is the caller's word that every entry has its reverse with the same weight;
+        False needs the graph's genuine CSC (Graph.build_csc)."""
+        return self._go(lib.mgx_mst_run, symmetric)
+
+    def enact(self, symmetric=False):
+        """operator path (two advances and a hook filter per round); the same stats, cursor_steps = 0"""
+        return self._go(lib.mgx_mst_enact, symmetric)
+
+    def edges(self):
+        """(a int32, b int32, w float32) of the forest's edges, a < b"""
+        if self._edges is None:
+            check(lib.mgx_mst_edges(self._h, None, None, None))                # raises: no run yet
+        k = self._edges
+        a, b = (np.empty(max(k, 1), dtype=np.int32) for _ in range(2))
+        w = np.empty(max(k, 1), dtype=np.float32)
+        check(lib.mgx_mst_edges(self._h, _ptr(a), _ptr(b), _ptr(w)))
+        return a[:k], b[:k], w[:k]
+
+    def edges_device_ptrs(self):
+        p = [C.c_void_p() for _ in range(3)]
+        check(lib.mgx_mst_edges_device(self._h, *(C.byref(x) for x in p)))
+        return tuple(x.value for x in p)
+
+    def weight(self):
+        t = C.c_double()
+        check(lib.mgx_mst_weight(self._h, C.byref(t)))
+        return float(t.value)
+
+    def labels(self):
+        out = np.empty(self.graph.num_nodes, dtype=np.int32)
+        check(lib.mgx_mst_labels(self._h, _ptr(out)))
+        return out
+
+    def labels_device_ptr(self):
+        p = C.c_void_p()
+        check(lib.mgx_mst_labels_device(self._h, C.byref(p)))
+        return p.value
+
+    def info(self):
+        """the last fused run: which path its rows took and the switches in effect"""
+        out = (C.c_int64 * 8)()
+        check(lib.mgx_mst_info(self._h, out))
+        return dict(zip(self.INFO, (int(x) for x in out)))
+
+    def close(self):
+        if self._h:
+            lib.mgx_mst_free(self._h)
             self._h = None
 
 

@@ -13,6 +13,7 @@
 #include "gunrock/cc/cc_enactor.hxx"
 #include "gunrock/coloring/coloring_enactor.hxx"
 #include "gunrock/lspar/lspar_enactor.hxx"
+#include "gunrock/mst/mst_enactor.hxx"
 #include "gunrock/pagerank/pagerank_enactor.hxx"
 #include "gunrock/pr/pr_enactor.hxx"
 #include "gunrock/kcore/kcore_enactor.hxx"
@@ -25,6 +26,7 @@
 #include "mgx/kcore_fused.hpp"
 #include "mgx/color_fused.hpp"
 #include "mgx/lspar_fused.hpp"
+#include "mgx/mst_fused.hpp"
 #include "mgx/pagerank_fused.hpp"
 #include "mgx/env.hpp"
 #include "mgx/sssp_dist.hpp"
@@ -140,6 +142,23 @@ struct mgx_pagerank_s {
   mgx_graph_t g = nullptr;
   std::shared_ptr<pagerank::pagerank_problem_t> p;                // lazily: the O(n) state both paths run on
   std::unique_ptr<pagerank::pagerank_enactor_t> e;                // lazily: the operator path's iota frontier
+};
+
+struct mgx_mst_s {
+  mgx_graph_t g = nullptr;
+  std::unique_ptr<mgx::mst_fused_state_t> fused;                  // lazily: the fused path's state and its sorted incident arrays
+  std::shared_ptr<mst::mst_problem_t> p;                          // lazily: the operator path's
+  std::unique_ptr<mst::mst_enactor_t> e;
+  std::unique_ptr<mgx::cc_label_stats_t> label_stats;             // lazily: the operator path's stats
+  mem_t<double> tile_sum;                                         // lazily: the operator path's list total
+  mem_t<mgx::u64> stat;
+  bool ready = false;                                             // a run of either path has left a result
+  const int* labels = nullptr;
+  const int* a = nullptr;
+  const int* b = nullptr;
+  const float* w = nullptr;
+  long long edges = 0;
+  double total = 0.0;
 };
 
 struct mgx_dbfs_s {
@@ -2993,6 +3012,145 @@ int mgx_pagerank_residuals(mgx_pagerank_t p, double* host_e, int cap, int* itera
   const int k = std::min(std::min(cap, s.last_iterations), s.trace_cap);
   p->g->c->ctx->synchronize();
   if (k > 0) MGX_HIP(mgx::dtoh(host_e, (const double*)s.trace.data(), (size_t)k));
+  MGX_CATCH
+}
+
+
+// ---- minimum spanning forest -----------------------------------------------------------
+int mgx_mst_create(mgx_graph_t g, mgx_mst_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(g && out, "NULL argument");
+  auto* h = new mgx_mst_s();
+  h->g = g;
+  *out = h;
+  MGX_CATCH
+}
+int mgx_mst_free(mgx_mst_t p) {
+  MGX_TRY
+  if (p) { use_device(p->g->c); p->g->c->ctx->synchronize(); delete p; }
+  MGX_CATCH
+}
+int mgx_mst_run(mgx_mst_t p, int symmetric, int64_t* stats) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  use_device(p->g->c);
+  standard_context_t& ctx = *p->g->c->ctx;
+  graph_device_t& g = *p->g->g;
+  p->ready = false;
+  const bool csc = !g.csc_is_csr;
+  MGX_REQUIRE(symmetric || csc, "mgx_mst_run: symmetric == 0 needs the graph's genuine CSC (mgx_graph_build_csc)");
+  MGX_REQUIRE(g.d_col_values.size() >= (size_t)g.num_edges && (!csc || g.d_row_values.size() >= (size_t)g.num_edges), "mgx_mst_run: the graph has no weights");
+  if (!p->fused) p->fused.reset(new mgx::mst_fused_state_t(g.num_nodes, g.num_edges, ctx));
+  const std::vector<long long> st = p->fused->run(g.d_row_offsets.data(), g.d_col_indices.data(), g.d_col_values.data(),
+                                                  csc ? g.d_col_offsets.data() : nullptr, csc ? g.d_row_indices.data() : nullptr,
+                                                  csc ? g.d_row_values.data() : nullptr, symmetric != 0, ctx);
+  p->labels = p->fused->comp.data();
+  p->a = p->fused->out_a.data(); p->b = p->fused->out_b.data(); p->w = p->fused->out_w.data();
+  p->edges = st[0];
+  p->total = p->fused->total();
+  p->ready = true;
+  if (stats) for (int i = 0; i < 8; ++i) stats[i] = st[i];
+  MGX_CATCH
+}
+int mgx_mst_enact(mgx_mst_t p, int symmetric, int64_t* stats) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  use_device(p->g->c);
+  standard_context_t& ctx = *p->g->c->ctx;
+  graph_device_t& g = *p->g->g;
+  p->ready = false;
+  MGX_REQUIRE(symmetric || !g.csc_is_csr, "mgx_mst_enact: symmetric == 0 needs the graph's genuine CSC (mgx_graph_build_csc)");
+  MGX_REQUIRE(g.d_col_values.size() >= (size_t)g.num_edges, "mgx_mst_enact: the graph has no weights");
+  const int n = g.num_nodes;
+  if (n <= 0) {
+    p->labels = nullptr; p->a = p->b = nullptr; p->w = nullptr; p->edges = 0; p->total = 0.0;
+    p->ready = true;
+    if (stats) for (int i = 0; i < 8; ++i) stats[i] = 0;
+    return MGX_OK;
+  }
+  if (!p->p) p->p = std::make_shared<mst::mst_problem_t>(p->g->g, ctx);
+  if (!p->e) p->e.reset(new mst::mst_enactor_t(ctx, n, g.num_edges));
+  if (!p->label_stats) p->label_stats.reset(new mgx::cc_label_stats_t(n, ctx));
+  if (!p->stat.size()) {
+    p->stat = mem_t<mgx::u64>(mgx::MST_S_WORDS, ctx);
+    p->tile_sum = mem_t<double>((size_t)n / mgx::MST_SUM_TILE + 2, ctx);
+  }
+  p->e->enact(p->p, symmetric != 0, ctx);
+  const hipStream_t s = ctx.stream();
+  mgx::mst_sum_list(p->p->d_w_out.data(), (const long long*)p->p->d_counters.data(), (long long)n, p->tile_sum.data(), nullptr,
+                    (const mgx::u64*)(p->p->d_counters.data() + 2), nullptr, n, p->stat.data(), s);
+  MGX_CHECK_LAUNCH("mgx mst enact");
+  mgx::u64 h[mgx::MST_S_WORDS];
+  mgx::u64 counters[4];
+  long long waits = p->e->waits;                                  // the operators' read-backs, one a call
+  MGX_HIP(mgx::dtoh(h, (const mgx::u64*)p->stat.data(), (size_t)mgx::MST_S_WORDS, s));
+  ++waits;
+  MGX_HIP(mgx::dtoh(counters, (const mgx::u64*)p->p->d_counters.data(), (size_t)4, s));
+  ++waits;
+  MGX_REQUIRE(h[mgx::MST_S_NAN] == 0, "mgx_mst_enact: a NaN edge weight");
+  const std::vector<long long> ls = p->label_stats->run(p->p->d_root.data(), n, ctx);
+  ++waits;
+  p->labels = p->p->d_root.data();
+  p->a = p->p->d_a.data(); p->b = p->p->d_b.data(); p->w = p->p->d_w_out.data();
+  p->edges = (long long)h[mgx::MST_S_EDGES];
+  std::memcpy(&p->total, &h[mgx::MST_S_TOTAL], sizeof(double));
+  p->ready = true;
+  if (stats) {
+    stats[0] = p->edges; stats[1] = ls[0]; stats[2] = ls[1]; stats[3] = ls[2]; stats[4] = p->e->rounds;
+    stats[5] = waits; stats[6] = 0; stats[7] = (long long)counters[1];
+  }
+  MGX_CATCH
+}
+int mgx_mst_edges(mgx_mst_t p, int* h_a, int* h_b, float* h_w) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  MGX_REQUIRE(p->ready, "mgx_mst_edges: no run yet");
+  use_device(p->g->c);
+  p->g->c->ctx->synchronize();
+  const size_t k = (size_t)p->edges;
+  if (h_a && k) MGX_HIP(mgx::dtoh(h_a, p->a, k));
+  if (h_b && k) MGX_HIP(mgx::dtoh(h_b, p->b, k));
+  if (h_w && k) MGX_HIP(mgx::dtoh(h_w, p->w, k));
+  MGX_CATCH
+}
+int mgx_mst_edges_device(mgx_mst_t p, const int** d_a, const int** d_b, const float** d_w) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  MGX_REQUIRE(p->ready, "mgx_mst_edges_device: no run yet");
+  if (d_a) *d_a = p->a;
+  if (d_b) *d_b = p->b;
+  if (d_w) *d_w = p->w;
+  MGX_CATCH
+}
+int mgx_mst_weight(mgx_mst_t p, double* total) {
+  MGX_TRY
+  MGX_REQUIRE(p && total, "NULL argument");
+  MGX_REQUIRE(p->ready, "mgx_mst_weight: no run yet");
+  *total = p->total;
+  MGX_CATCH
+}
+int mgx_mst_labels(mgx_mst_t p, int* host) {
+  MGX_TRY
+  MGX_REQUIRE(p && host, "NULL argument");
+  MGX_REQUIRE(p->ready, "mgx_mst_labels: no run yet");
+  use_device(p->g->c);
+  p->g->c->ctx->synchronize();
+  if (p->g->g->num_nodes > 0) MGX_HIP(mgx::dtoh(host, p->labels, (size_t)p->g->g->num_nodes));
+  MGX_CATCH
+}
+int mgx_mst_labels_device(mgx_mst_t p, const int** out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  MGX_REQUIRE(p->ready, "mgx_mst_labels_device: no run yet");
+  *out = p->labels;
+  MGX_CATCH
+}
+int mgx_mst_info(mgx_mst_t p, int64_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  MGX_REQUIRE(p->fused, "mgx_mst_info: no fused run yet");
+  const std::vector<long long> v = p->fused->info();
+  for (int i = 0; i < 8; ++i) out[i] = v[i];
   MGX_CATCH
 }
 
