@@ -58,6 +58,145 @@ def check_against_enactor(st, est):
     return st["passes"] == int(est[1]) - int(est[0]) and st["expanded"] == int(est[2]) and st["removed"] == int(est[3])
 
 
+# ---- the launch plan: which kind every launch of mgx_kcore_run is (the switch in k_kcore_step, restated) ----
+# The header's thresholds, by name; tests/test_kcore_cpu.py reads their values out of include/mgx/kcore_fused.hpp.
+MINI_MAX = 2048          # KCORE_MINI_MAX: entries of a front one workgroup peels on its own
+LONG_MIN = 32            # KCORE_LONG_MIN: rows of at least this many entries are long
+SEG = 256                # KCORE_SEG: entries of a (vertex, segment) item
+BATCH_MIN = 64           # KCORE_BATCH_MIN, KCORE_BATCH_MAX: launches per host wait, doubling
+BATCH_MAX = 256
+# the codes of mini_amd.KcoreProblem.STEP_KINDS (kcore_kind_t)
+MIN, LIST, EXPAND, FILTER, IDLE, MINI = 1, 2, 3, 4, 5, 6
+_INIT = 0
+KIND_NAMES = {MIN: "min", LIST: "list", EXPAND: "expand", FILTER: "filter", IDLE: "idle", MINI: "mini"}
+
+
+class Plan:
+    """what launch_plan returns.  kinds: the codes up to and including the first idle launch; fronts: (k, entries, kind that took
+    it) per front, a MINI's inner passes included; lists: (short rows, items) of the same fronts, as a step enlists them"""
+
+    def __init__(self):
+        self.kinds, self.fronts, self.lists = [], [], []
+        self.cores = self.largest = self.degrees = self.stats = None
+
+    def names(self):
+        return " ".join(KIND_NAMES[k] for k in self.kinds)
+
+
+def front_lists(ro, front):
+    """(short rows, (vertex, segment) items) a front of these vertices is enlisted as"""
+    lens = np.asarray(ro, dtype=np.int64)[np.asarray(front, dtype=np.int64) + 1] - np.asarray(ro, dtype=np.int64)[front]
+    long_rows = lens[lens >= LONG_MIN]
+    return int((lens < LONG_MIN).sum()), int(((long_rows + SEG - 1) // SEG).sum())
+
+
+def launch_plan(ro, ci):
+    """-> Plan.  The state a launch leaves is (its kind, its k, the front it made, the candidates it found, the smallest positive
+    degree it saw); the next launch's kind follows from that alone, as on the device.  Fronts and candidates are sets, so the
+    plan is a function of the graph."""
+    ro = np.asarray(ro, dtype=np.int64)
+    ci = np.asarray(ci, dtype=np.int64)
+    n = len(ro) - 1
+    deg = np.diff(ro).astype(np.int64)
+    core = np.zeros(n, dtype=np.int32)
+    st = dict.fromkeys(STAT_NAMES, 0)
+    plan = Plan()
+    nobody = np.zeros(0, dtype=np.int64)
+    largest = -1
+
+    def work_of(front):
+        return int((ro[front + 1] - ro[front]).sum())
+
+    def leave(who, number):
+        core[who] = number
+        deg[who] = 0
+
+    def expand(front, k, kind):
+        """one pass: the front's entries take 1 each; -> the vertices that crossed k"""
+        lens = ro[front + 1] - ro[front]
+        total = int(lens.sum())
+        plan.fronts.append((k, total, kind))
+        plan.lists.append(front_lists(ro, front))
+        st["passes"] += 1
+        st["removed"] += int(front.size)
+        st["expanded"] += total
+        if total == 0:
+            return nobody
+        starts = np.repeat(ro[front] - np.concatenate([[0], np.cumsum(lens)[:-1]]), lens)
+        taken = np.bincount(ci[starts + np.arange(total)], minlength=n)
+        hit = np.nonzero(taken)[0]
+        before = deg[hit]
+        deg[hit] = before - taken[hit]
+        return hit[(before >= k) & (deg[hit] < k)]
+
+    def filtered(cand, k):
+        front = cand[deg[cand] > 0]
+        st["stranded"] += int(cand.size - front.size)
+        leave(front, k - 1)
+        return front
+
+    p_kind, k, front, cand, smallest = _INIT, 0, nobody, nobody, 0
+    while True:
+        take = MINI if work_of(front) <= MINI_MAX else EXPAND
+        new_level = False
+        if p_kind == _INIT:
+            kind = MIN
+        elif p_kind == MIN:
+            new_level = True
+            if front.size:                       # the MIN listed level k + 1 itself
+                k, kind = k + 1, take
+            elif smallest == 0:                  # nobody has a positive degree: level k was the last
+                kind = IDLE
+                if k > 0:
+                    largest = k - 1
+            else:
+                k = smallest + 1
+                kind = IDLE if k > n else LIST
+        elif p_kind == LIST:
+            kind = take
+        elif p_kind == EXPAND:
+            kind = FILTER if cand.size else MIN
+        else:                                    # FILTER, and MINI, which ends where a FILTER ends
+            kind = take if front.size else MIN
+        plan.kinds.append(kind)
+        if new_level and kind != IDLE:
+            st["levels"] += 1
+        if kind == IDLE:
+            break
+        if kind == MIN or kind == LIST:
+            at = k - 1 if kind == LIST else (k if 1 <= k < n else 0)
+            positive = deg[deg > 0]
+            smallest = int(positive.min()) if positive.size else 0
+            front = np.nonzero(deg == at)[0] if at > 0 else nobody
+            leave(front, k if kind == MIN else k - 1)
+        elif kind == EXPAND:
+            cand = expand(front, k, EXPAND)
+            front = nobody
+        elif kind == FILTER:
+            front = filtered(cand, k)
+        else:                                    # MINI: passes of its own until the front is empty or has outgrown it
+            while True:
+                front = filtered(expand(front, k, MINI), k)
+                if front.size == 0 or work_of(front) > MINI_MAX:
+                    break
+            kind = FILTER
+        p_kind = kind
+    plan.cores, plan.largest, plan.degrees, plan.stats = core, largest, deg.astype(np.int32), st
+    return plan
+
+
+def host_waits_and_launches(n_kinds):
+    """(host waits, launches enqueued) of a run whose first idle launch is launch n_kinds - 1: batches of BATCH_MIN, doubling up to
+    BATCH_MAX, one wait behind each; the run ends at the first wait whose batches cover the idle launch"""
+    waits, launches, batch = 0, 0, BATCH_MIN
+    while True:
+        launches += batch
+        waits += 1
+        if launches >= n_kinds:
+            return waits, launches
+        batch = min(batch * 2, BATCH_MAX)
+
+
 # ---- the graphs both suites use ----
 def csr(n, src, dst, symmetric=True):
     src, dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)

@@ -73,6 +73,13 @@ def test_fused_equals_operator_path_and_model(gpu_ctx, oracle, name):
     assert np.array_equal(deg, oper.degrees()) and np.array_equal(deg, mdeg)
     assert {k: st[k] for k in model.STAT_NAMES} == mst
     assert st["passes"] == est["passes"] - est["rounds"] and st["expanded"] == est["expanded"] and st["removed"] == est["removed"]
+    # which launches the run was: the plan's, then idle ones up to the end of the host's last batch
+    plan = model.launch_plan(ro, ci)
+    assert np.array_equal(plan.cores, mcores) and plan.stats == mst
+    kinds = fused.step_kinds()
+    waits, launches = model.host_waits_and_launches(len(plan.kinds))
+    assert kinds[:len(plan.kinds)].tolist() == plan.kinds and (kinds[len(plan.kinds):] == model.IDLE).all()
+    assert len(kinds) == launches and st["host_waits"] == waits
     if name == "rmat18_stranded":
         assert st["stranded"] == 1
     if name == "path3":
@@ -132,6 +139,8 @@ def test_fused_host_waits_do_not_follow_levels_or_passes(gpu_ctx, oracle):
     largest, st = kc.run()
     print("rmat16", st)
     assert st["levels"] == 108 and st["passes"] == 332
-    assert st["host_waits"] < 108
+    waits, launches = model.host_waits_and_launches(len(model.launch_plan(ro, ci).kinds))
+    assert waits < 108
+    assert st["host_waits"] == waits and len(kc.step_kinds()) == launches
     kc.close()
     g.close()
