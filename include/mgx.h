@@ -564,6 +564,12 @@ MGX_API int mgx_color_colors(mgx_color_t p, int* host_colors);
 MGX_API int mgx_color_colors_device(mgx_color_t p, const int** d_colors);
 /* active vertices at the start of each round of the last run: *rounds gets the round count, at most cap are written */
 MGX_API int mgx_color_round_trace(mgx_color_t p, int64_t* active_at_round_start, int cap, int* rounds);
+/* the fused path's row classes (all host-side): consts4 = { long_min: rows of at least this many entries are long, seg: entries of a
+ * long row one wave scans, stage: segments a wave's LDS stage holds -- a surviving row of more goes out on its own --, batch_max:
+ * rounds per host wait at most }; and per round the LAST FUSED run ran, three values at the start of the round: short rows, long
+ * items (segments), long rows still uncoloured (round 0: short rows = vertices of fewer than long_min entries).  *rounds gets the
+ * round count, at most cap triples are written (round_triples may be NULL with cap <= 0).  MGX_E_INVALID before any fused run. */
+MGX_API int mgx_color_info(mgx_color_t p, int64_t* consts4, int64_t* round_triples, int cap, int* rounds);
 
 /* ---- local graph sparsification: lspar_problem_t / lspar_functor.hxx / lspar_enactor_t (gunrock/src/lspar/) ----
  * One definition, rows read as they stand (duplicates and self-loops count):
@@ -588,6 +594,10 @@ MGX_API int mgx_lspar_result(mgx_lspar_t p, int* h_ro, int* h_ci, int* h_eid, in
 MGX_API int mgx_lspar_result_device(mgx_lspar_t p, const int** d_ro, const int** d_ci, const int** d_eid, const int** d_sim);
 /* the last run's minhash table, n x k, vertex-major */
 MGX_API int mgx_lspar_minhashes(mgx_lspar_t p, unsigned* h_minhashes);
+/* the fused path's row classes (all host-side): out5 = { short_max: rows of at most this many entries take the group kernels, seg:
+ * entries of a longer row one wave item covers, k_max, and of the LAST FUSED run: the minhash table's stride (k <= 2: k, else k
+ * rounded up to a multiple of 4) and its items (segments of the rows longer than short_max) }.  MGX_E_INVALID before any fused run. */
+MGX_API int mgx_lspar_info(mgx_lspar_t p, int64_t* out5);
 /* a NEW graph that owns a device copy of the last result (weights: the kept entries' input weights, gathered by eid);
  * free it with mgx_graph_free */
 MGX_API int mgx_lspar_graph(mgx_lspar_t p, mgx_graph_t* out);

@@ -277,6 +277,10 @@ struct color_fused_state_t {
   mem_t<int> max_colour;
   int* h_pinned = nullptr;          // one batch's counts + the largest colour
   long long l_cap = 0;
+  // the last run, per round run: short rows, long items, long rows at the start of the round (mgx_color_info); round 0's short
+  // rows are the vertices of fewer than long_min entries.  has_run: a run has finished.
+  std::vector<long long> round_rows;
+  bool has_run = false;
 
   color_fused_state_t(const color_fused_state_t&) = delete;
   color_fused_state_t& operator=(const color_fused_state_t&) = delete;
@@ -304,6 +308,8 @@ struct color_fused_state_t {
                              std::vector<long long>& trace) {
     const hipStream_t st = ctx.stream();
     trace.clear();
+    round_rows.clear();
+    has_run = false;
     const long long half = ((long long)n + 1) / 2;
     const long long cap = max_iter > 0 ? std::min<long long>(max_iter, half) : half;
     if (cnt.size() < (size_t)(3 * (cap + 2))) {
@@ -314,7 +320,7 @@ struct color_fused_state_t {
     MGX_HIP(hipMemsetAsync(bm.data(), 0, (size_t)words4 * 3 * sizeof(uint4), st));
     MGX_HIP(hipMemsetAsync(max_colour.data(), 0, sizeof(int), st));
     long long waits = 0, rounds = 0, left = n;
-    if (cap == 0) return {0, (long long)n, 0, 0};
+    if (cap == 0) { has_run = true; return {0, (long long)n, 0, 0}; }
 
     const int max_blocks = std::max(ctx.num_cus, 1) * 8;
     auto blocks_for = [&](long long s, long long items) {
@@ -364,6 +370,9 @@ struct color_fused_state_t {
         left = active;
         if (r == b || active == 0) break;
         trace.push_back(active);
+        round_rows.push_back(i + r == 0 ? (long long)n - h_pinned[2] : (long long)h_pinned[3 * r]);
+        round_rows.push_back(h_pinned[3 * r + 1]);
+        round_rows.push_back(h_pinned[3 * r + 2]);
         ++rounds;
       }
       i += b;
@@ -371,6 +380,7 @@ struct color_fused_state_t {
       known_items = h_pinned[3 * b + 1];
       if (left == 0) break;
     }
+    has_run = true;
     return {rounds, left, (long long)h_pinned[3 * (COLOR_BATCH_MAX + 2)], waits};
   }
 };

@@ -87,6 +87,8 @@ inline const env_switch_t* env_switches(int* count) {
     {"MGX_DIST_COLD_REDUCE", "0: the sweep ORs the cold bitmaps itself"},
     {"MGX_DIST_HOT_UNITS", "0: unit blocks with all entries on the ranks"},
     {"MGX_LOOPBACK_TIMEOUT_S", "deadline of every wait of the loopback communicator (seconds, default 120)"},
+    // ---- every context (standard_context_t: read once when the context is created)
+    {"MGX_GRID_CUS", "(tests) N: the context counts min(N, the device's) compute units, at least 1 (a non-number counts as 1): chip-sized grids shrink to N * 8 workgroups"},
   };
   *count = (int)(sizeof(table) / sizeof(table[0]));
   return table;

@@ -338,6 +338,7 @@ struct lspar_fused_state_t {
   mem_t<int2> items;
   mem_t<int> cnt, seg_hist;
   int* h_pinned = nullptr;          // the item count and rows cut
+  long long last_items = -1;        // the last run's item count (mgx_lspar_info; -1: no run yet)
 
   lspar_fused_state_t(const lspar_fused_state_t&) = delete;
   lspar_fused_state_t& operator=(const lspar_fused_state_t&) = delete;
@@ -353,6 +354,7 @@ struct lspar_fused_state_t {
   // returns {kept entries, rows cut, host waits}; the outputs are complete when the stream is
   std::vector<long long> run(const int* ro, const int* ci, unsigned seed, int k, double e, standard_context_t& ctx) {
     const hipStream_t st = ctx.stream();
+    last_items = -1;
     S = lspar_stride(k);
     const size_t cells = (size_t)std::max(n, 1) * S;
     if (mh.size() < cells) mh = mem_t<unsigned>(cells, ctx);
@@ -403,6 +405,7 @@ struct lspar_fused_state_t {
       }
       MGX_CHECK_LAUNCH("mgx lspar select");
     }
+    last_items = nitems;
     return {total, cut, 1};
   }
 };

@@ -9,6 +9,7 @@
 //     allocates 4-5 temporaries per superstep);
 //   * errors are status codes / exceptions, never exit() (frontier.hxx:53-59).
 #pragma once
+#include <algorithm>
 #include <cstdlib>
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -23,6 +24,7 @@
 #include <vector>
 
 #include "../mgx.h"
+#include "env.hpp"
 
 namespace mgx {
 
@@ -185,6 +187,9 @@ struct standard_context_t : context_t {
     hipDeviceProp_t prop;
     MGX_HIP(hipGetDeviceProperties(&prop, device));
     num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    // MGX_GRID_CUS only ever lowers the count: the "chip-sized" grids (num_cus * 8 workgroups) then run their grid-stride loops
+    // several times on a small test graph -- the carry-over of a wave's stage and every kernel's later iterations
+    if (const char* e = env("MGX_GRID_CUS")) num_cus = (int)std::min<long long>(std::max<long long>(std::atoll(e), 1), num_cus);
     if (print_prop) std::printf("%s : %d CUs\n", prop.name, num_cus);
     MGX_HIP(hipHostMalloc((void**)&mailbox, 64 * sizeof(long long), hipHostMallocDefault));
     for (int i = 0; i < 64; ++i) mailbox[i] = 0;

@@ -209,6 +209,7 @@ SIGNATURES = {
     "mgx_color_colors": [_vp, _vp],
     "mgx_color_colors_device": [_vp, _pvp],
     "mgx_color_round_trace": [_vp, _pi64, _i, _pi],
+    "mgx_color_info": [_vp, _pi64, _pi64, _i, _pi],
     "mgx_lspar_create": [_vp, _pvp],
     "mgx_lspar_free": [_vp],
     "mgx_lspar_run": [_vp, C.c_uint, _i, C.c_double, _pi64],
@@ -216,6 +217,7 @@ SIGNATURES = {
     "mgx_lspar_result": [_vp, _vp, _vp, _vp, _vp],
     "mgx_lspar_result_device": [_vp, _pvp, _pvp, _pvp, _pvp],
     "mgx_lspar_minhashes": [_vp, _vp],
+    "mgx_lspar_info": [_vp, _pi64],
     "mgx_lspar_graph": [_vp, _pvp],
     "mgx_segmented_sort_i32": [_vp, _vp, _vp, _i64, _vp, _i, _i],
     "mgx_cc_create": [_vp, _pvp],

@@ -666,6 +666,17 @@ class ColorProblem:
         check(lib.mgx_color_round_trace(self._h, out.ctypes.data_as(C.POINTER(C.c_int64)), rounds.value, C.byref(rounds)))
         return out[:rounds.value]
 
+    def info(self):
+        """the fused path's row classes and the last fused run: {"long_min", "seg", "stage", "batch_max", "rounds": int64 (rounds, 3):
+        short rows, long items, long rows at the start of every round run}"""
+        consts, rounds = (C.c_int64 * 4)(), C.c_int()
+        check(lib.mgx_color_info(self._h, consts, None, 0, C.byref(rounds)))
+        out = np.zeros((max(rounds.value, 1), 3), dtype=np.int64)
+        check(lib.mgx_color_info(self._h, consts, out.ctypes.data_as(C.POINTER(C.c_int64)), rounds.value, C.byref(rounds)))
+        d = dict(zip(("long_min", "seg", "stage", "batch_max"), (int(x) for x in consts)))
+        d["rounds"] = out[:rounds.value]
+        return d
+
     def close(self):
         if self._h:
             lib.mgx_color_free(self._h)
@@ -723,6 +734,12 @@ class LsparProblem:
         out = np.empty((self.source.num_nodes, self._k), dtype=np.uint32)
         check(lib.mgx_lspar_minhashes(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def info(self):
+        """the fused path's row classes and the last fused run: {"short_max", "seg", "k_max", "stride", "items"}"""
+        out = (C.c_int64 * 5)()
+        check(lib.mgx_lspar_info(self._h, out))
+        return dict(zip(("short_max", "seg", "k_max", "stride", "items"), (int(x) for x in out)))
 
     def graph(self):
         """a new Graph owning a device copy of the last result"""

@@ -2343,6 +2343,20 @@ int mgx_color_round_trace(mgx_color_t p, int64_t* active_at_round_start, int cap
   for (int i = 0; i < cap && i < (int)p->trace.size(); ++i) active_at_round_start[i] = p->trace[i];
   MGX_CATCH
 }
+int mgx_color_info(mgx_color_t p, int64_t* consts4, int64_t* round_triples, int cap, int* rounds) {
+  MGX_TRY
+  MGX_REQUIRE(p && consts4 && rounds && (round_triples || cap <= 0), "NULL argument");
+  MGX_REQUIRE(p->fused && p->fused->has_run, "mgx_color_info: no fused run yet");
+  consts4[0] = mgx::COLOR_LONG_MIN;
+  consts4[1] = mgx::COLOR_SEG;
+  consts4[2] = mgx::COLOR_STAGE;
+  consts4[3] = mgx::COLOR_BATCH_MAX;
+  const std::vector<long long>& v = p->fused->round_rows;
+  *rounds = (int)(v.size() / 3);
+  for (int i = 0; i < cap && i < *rounds; ++i)
+    for (int j = 0; j < 3; ++j) round_triples[3 * i + j] = v[3 * (size_t)i + j];
+  MGX_CATCH
+}
 
 
 // ---- local graph sparsification ----------------------------------------------------------------
@@ -2439,6 +2453,17 @@ int mgx_lspar_minhashes(mgx_lspar_t p, unsigned* h) {
   if (n)
     MGX_HIP(hipMemcpy2D(h, (size_t)p->k * sizeof(unsigned), p->mh, (size_t)p->mh_stride * sizeof(unsigned), (size_t)p->k * sizeof(unsigned),
                         n, hipMemcpyDeviceToHost));
+  MGX_CATCH
+}
+int mgx_lspar_info(mgx_lspar_t p, int64_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  MGX_REQUIRE(p->fused && p->fused->last_items >= 0, "mgx_lspar_info: no fused run yet");
+  out[0] = mgx::LSPAR_SHORT_MAX;
+  out[1] = mgx::LSPAR_SEG;
+  out[2] = mgx::LSPAR_K_MAX;
+  out[3] = p->fused->S;
+  out[4] = p->fused->last_items;
   MGX_CATCH
 }
 int mgx_lspar_graph(mgx_lspar_t p, mgx_graph_t* out) {
