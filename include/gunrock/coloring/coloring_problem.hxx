@@ -1,10 +1,10 @@
 // gunrock/coloring/coloring_problem.hxx -- state of the graph colouring the operator path runs (mgx_color_enact).
 // The reference's coloring_problem_t (gunrock/src/coloring/coloring_problem.hxx): the same data-slice fields and constructor
 // (graph, seed, max_iter, context).  What differs: the per-round keys are not moderngpu's fill_random over a
-// host generator but key_i(v) = fmix32(v ^ salt_i) (mgx/color_fused.hpp), stored with bit 31 flipped so that the i32
+// host generator but key_i(v) = fmix32(v ^ salt_i) (mgx/color_hash.hpp), stored with bit 31 flipped so that the i32
 // min / max of the neighbourhood reduce order them as unsigned -- one definition the fused path and the tests' model share.
 #pragma once
-#include "../../mgx/color_fused.hpp"
+#include "../../mgx/color_hash.hpp"
 #include "../problem.hxx"
 
 namespace gunrock {

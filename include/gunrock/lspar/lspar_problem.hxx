@@ -1,11 +1,11 @@
 // gunrock/lspar/lspar_problem.hxx -- state of the local sparsification the operator path runs (mgx_lspar_enact).
 // The reference's lspar_problem_t (gunrock/src/lspar/lspar_problem.hxx): the data-slice fields d_hashs, d_minwise_hashs,
 // d_thresholds, d_sims and the {eid, sim} record sim_edge_t.  What differs: the hashes are not std::rand()
-// but colouring's h_j(v) = fmix32(v ^ salt_j) (mgx/color_fused.hpp), stored with bit 31 flipped so that the i32 minimum of
+// but colouring's h_j(v) = fmix32(v ^ salt_j) (mgx/color_hash.hpp), stored with bit 31 flipped so that the i32 minimum of
 // the neighbourhood reduce orders them as unsigned; k hash functions (1 .. 32) instead of "only k = 1"; the keep count is
 // mgx::lspar_keep (the guarded double pow), not floor(__powf); and the result is written, not left uninitialised.
 #pragma once
-#include "../../mgx/color_fused.hpp"
+#include "../../mgx/color_hash.hpp"
 #include "../../mgx/lspar_fused.hpp"
 #include "../problem.hxx"
 

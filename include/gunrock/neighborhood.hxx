@@ -62,8 +62,7 @@ int neighborhood_kernel(std::shared_ptr<Problem> problem, std::shared_ptr<fronti
   //  element is not known -- mgx::op_neutral -- since the layout's kernels fold padding entries and idle lanes)
   if constexpr (sizeof(Value) == 4 && mgx::op_neutral<reduce_op, Value>::known)
   if (!has_output && is_pure_gather<Functor>::value && (full || subset) && frontier_size > 0 &&
-      graph.has_layout && (push || graph.csc_is_csr) && graph.rows.ub.units > 0 && graph.rows.ub_min_degree == graph.rows.vs_long_min && graph.rows.vs_long_min >= 17 && graph.rows.vs_long_min <= 64 &&
-      graph.rows.ub.cnt.size() && graph.rows.ub.first.size() && graph.rows.vs_dummy != 0 &&
+      (push || graph.csc_is_csr) && mgx::nr_units_valid(graph) &&
       context.scratch_bytes >= mgx::nr_scratch_bytes(graph.num_nodes, graph.rows.ub.units_pad, sizeof(Value))) {
     // the check (inside the first kernel) and the work go out back to back: the kernels behind it look at its verdict themselves (a device
     // word that holds the epoch of the last call whose frontier was NOT the iota); one host wait, behind everything
@@ -71,36 +70,11 @@ int neighborhood_kernel(std::shared_ptr<Problem> problem, std::shared_ptr<fronti
     context.mailbox[9] = (long long)context.nr_edges_base;
     const unsigned epoch = context.next_nr_epoch();
     if (graph.num_edges > 0) {
-      mgx::nr_layout_t L;
-      L.new_of_old = graph.d_new_of_old.data();
-      L.row_offsets = (const mgx::u32*)graph.d_layout_row_offsets.data();
-      L.col_indices = graph.d_layout_col_indices.data();
-      L.old_of_new = graph.d_old_of_new.data();
-      L.ub_col = graph.rows.ub.col.size() ? graph.rows.ub.col.data() : nullptr;      // (round 6: gone when the layout carries the 24-bit copy)
-      L.ub_col24 = graph.rows.ub.col24.size() ? graph.rows.ub.col24.data() : nullptr;     // (the 24-bit copy whenever the layout has one: 0.492 -> 0.477 ms in round 4)
-      L.ub_cnt = graph.rows.ub.cnt.data();
-      L.ub_first = graph.rows.ub.first.data();
-      L.ub_units = (mgx::u32)graph.rows.ub.units; L.ub_units_pad = (mgx::u32)graph.rows.ub.units_pad;
-      for (int i = 0; i < 4; ++i) L.vs_v[i] = graph.rows.vs_v[i];
-      L.vs_dummy = graph.rows.vs_dummy;
-      L.big_rows = graph.nr_big_rows;
-      L.n = graph.num_nodes;
-      {
-        static const unsigned parts = [] { const char* e = mgx::env("MGX_NR_PARTS"); return e ? (unsigned)std::atoi(e) & 3u : 3u; }();
-        L.parts = parts ? parts : 3u;
-      }
-      {
-        // the long rows by slice of their destinations (MGX_NR_SLICED=0: the unit blocks, as before round 5), when the graph carries
-        // them and the scratch arena holds a partial per mini-unit
-        static const bool sliced = [] { const char* e = mgx::env("MGX_NR_SLICED"); return !e || std::atoi(e) != 0; }();
-        if (sliced && graph.nrs_units > 0 && graph.nrs_slices > 0 && graph.nrs_rows == graph.rows.vs_v[0] && graph.d_nrs_mu.size() && graph.d_nrs_off.size() &&
-            context.scratch_bytes >= mgx::nr_scratch_bytes(graph.num_nodes, graph.nrs_units, sizeof(Value))) {
-          L.nrs_mu = (const uint4*)graph.d_nrs_mu.data();
-          L.nrs_off = graph.d_nrs_off.data();
-          for (int i = 0; i < mgx::NRS_MAX_SLICES + 2; ++i) L.nrs_first[i] = graph.nrs_first[i];
-          L.nrs_slices = graph.nrs_slices; L.nrs_rows = graph.nrs_rows; for (int i = 0; i < 3; ++i) L.nrs_tier[i] = graph.nrs_tier[i];
-        }
-      }
+      // the long rows by slice of their destinations when the graph carries them (MGX_NR_SLICED=0: the unit blocks, as before round 5)
+      static const bool sliced = [] { const char* e = mgx::env("MGX_NR_SLICED"); return !e || std::atoi(e) != 0; }();
+      static const unsigned parts = [] { const char* e = mgx::env("MGX_NR_PARTS"); return e ? (unsigned)std::atoi(e) & 3u : 3u; }();
+      mgx::nr_layout_t L = mgx::nr_layout_of(graph, context, sizeof(Value), sliced);
+      L.parts = parts ? parts : 3u;
       if (subset && graph.d_nr_pos.size() < (size_t)graph.num_nodes) {       // (first subset call on this graph: the one allocation of this path)
         context.synchronize();
         graph.d_nr_pos = mem_t<unsigned long long>((size_t)graph.num_nodes, context);

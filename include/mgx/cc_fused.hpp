@@ -32,9 +32,10 @@
 #include <algorithm>
 #include <vector>
 
-#include "color_fused.hpp"
+#include "color_hash.hpp"
 #include "runtime.hpp"
 #include "wave.hpp"
+#include "worklist.hpp"
 
 namespace mgx {
 
@@ -146,36 +147,7 @@ struct cc_list_args_t {
   u64* skipped;
 };
 
-// a wave's short items into its LDS stage, out through one returning add per CC_STAGE of them
-__device__ __forceinline__ void cc_flush(int* stage, int& fill, int* out, int* counter) {
-  if (fill == 0) return;
-  wave_lds_fence();
-  int base = 0;
-  if (lane_id() == 0) base = atomicAdd(counter, fill);
-  base = __shfl(base, 0, WAVE);
-  for (int k = lane_id(); k < fill; k += WAVE) out[base + k] = stage[k];
-  wave_lds_fence();                                          // (read before the stage is filled again)
-  fill = 0;
-}
-__device__ __forceinline__ void cc_keep_short(bool keep, int item, int* stage, int& fill, int* out, int* counter) {
-  const u64 m = __ballot(keep);
-  if (!m) return;
-  const int k = __popcll(m);
-  if (fill + k > CC_STAGE) cc_flush(stage, fill, out, counter);
-  if (keep) stage[fill + rank_in_mask(m)] = item;
-  fill += k;
-}
-// a long row's segments: one add per wave for all its lanes' rows
-__device__ __forceinline__ void cc_keep_long(bool keep, int item, int len, int2* out, int* counter) {
-  if (!__ballot(keep)) return;
-  const int segs = keep ? (len + CC_SEG - 1) / CC_SEG : 0;
-  const int incl = wave_inclusive_sum(segs);
-  int base = 0;
-  if (lane_id() == WAVE - 1) base = atomicAdd(counter, incl);
-  base = __shfl(base, WAVE - 1, WAVE);
-  for (int s = 0; s < segs; ++s) out[base + incl - segs + s] = make_int2(item, s);
-}
-
+// short rows through the wave's LDS stage, long rows' segments behind one add per wave and pass (worklist.hpp)
 __global__ __launch_bounds__(BLOCK) void k_cc_worklist(cc_list_args_t a) {
   const int lane = lane_id();
   const int wave = (int)((blockIdx.x * (unsigned)BLOCK + threadIdx.x) / WAVE);
@@ -193,12 +165,12 @@ __global__ __launch_bounds__(BLOCK) void k_cc_worklist(cc_list_args_t a) {
     const bool skip = has && a.mode != CC_NO_SKIP && a.comp[v] == c;
     skipped += __popcll(__ballot(skip));
     const bool out_go = has && !skip && out_len > 0, in_go = has && !skip && in_len > 0;
-    cc_keep_short(out_go && out_len < CC_LONG_MIN, v, stage, fill, a.s_list, a.cnt);
-    cc_keep_short(in_go && in_len < CC_LONG_MIN, ~v, stage, fill, a.s_list, a.cnt);
-    cc_keep_long(out_go && out_len >= CC_LONG_MIN, v, out_len, a.l_list, a.cnt + 1);
-    cc_keep_long(in_go && in_len >= CC_LONG_MIN, ~v, in_len, a.l_list, a.cnt + 1);
+    wave_stage_push<CC_STAGE>(out_go && out_len < CC_LONG_MIN, v, stage, fill, a.s_list, a.cnt);
+    wave_stage_push<CC_STAGE>(in_go && in_len < CC_LONG_MIN, ~v, stage, fill, a.s_list, a.cnt);
+    wave_append_segments(out_go && out_len >= CC_LONG_MIN, v, out_len, CC_SEG, a.l_list, a.cnt + 1);
+    wave_append_segments(in_go && in_len >= CC_LONG_MIN, ~v, in_len, CC_SEG, a.l_list, a.cnt + 1);
   }
-  cc_flush(stage, fill, a.s_list, a.cnt);
+  wave_stage_flush(stage, fill, a.s_list, a.cnt);
   if (lane == 0 && skipped) atomicAdd(a.skipped, (u64)skipped);
 }
 

@@ -23,8 +23,10 @@
 #include <algorithm>
 #include <vector>
 
+#include "color_hash.hpp"
 #include "runtime.hpp"
 #include "wave.hpp"
+#include "worklist.hpp"
 
 namespace mgx {
 
@@ -32,19 +34,6 @@ constexpr int COLOR_SEG = 2048;          // entries of a long row one wave scans
 constexpr int COLOR_LONG_MIN = 32;       // rows of at least this many entries are long
 constexpr int COLOR_BATCH_MAX = 128;     // rounds per host wait, at most
 constexpr unsigned COLOR_SEED_DEFAULT = 15485863u;
-
-__host__ __device__ __forceinline__ unsigned color_fmix32(unsigned h) {
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h;
-}
-__host__ __device__ __forceinline__ unsigned color_salt(unsigned seed, int round) {
-  return color_fmix32(seed + 0x9E3779B9u * (unsigned)(round + 1));
-}
-__host__ __device__ __forceinline__ unsigned color_key(int v, unsigned salt) { return color_fmix32((unsigned)v ^ salt); }
 
 // the segment tally of a split row: arrivals, segments that saw a key below, above -- 21 bits each
 constexpr int COLOR_TALLY_SHIFT = 21;
@@ -98,35 +87,9 @@ __device__ __forceinline__ int color_short_row(const color_round_args_t& a, int 
   return !below ? a.c_lo : (!above ? a.c_lo + 1 : 0);
 }
 
-// A wave's survivors wait in a wave-private LDS stage and go out COLOR_STAGE at a time behind one returning add: the lists'
-// counters are single words every wave of the device adds to, and adds to one word are serialised (one add per surviving long
-// row cost a uniform RMAT-22 round ~19 ms).
+// a wave's LDS stage of survivors (worklist.hpp): one for the short rows -- they go into the stage (then the next round's list) and
+// into the next round's bitmap -- and one for the long rows' items
 constexpr int COLOR_STAGE = 2 * WAVE;
-
-template <typename T>
-__device__ __forceinline__ void color_flush(T* stage, int& fill, T* out, int* counter) {
-  if (fill == 0) return;
-  wave_lds_fence();
-  int base = 0;
-  if (lane_id() == 0) base = atomicAdd(counter, fill);
-  base = __shfl(base, 0, WAVE);
-  for (int k = lane_id(); k < fill; k += WAVE) out[base + k] = stage[k];
-  wave_lds_fence();                                        // (read before the stage is filled again)
-  fill = 0;
-}
-
-// survivors of a wave's short rows into the stage (then the next round's list) and the next round's bitmap
-__device__ __forceinline__ void color_keep_short(const color_round_args_t& a, bool keep, int v, int* stage, int& fill) {
-  const u64 m = __ballot(keep);
-  if (!m) return;
-  const int k = __popcll(m);
-  if (fill + k > COLOR_STAGE) color_flush(stage, fill, a.s_out, a.cnt_out);
-  if (keep) {
-    stage[fill + rank_in_mask(m)] = v;
-    atomicOr(a.bm_next + (v >> 5), 1u << (v & 31));
-  }
-  fill += k;
-}
 
 // Round 0, before the round kernel: vertices 0 .. n - 1 -- short rows decided (every neighbour is uncoloured), long rows'
 // segments listed into l_out / cnt_out[1], [2] (the round kernel of round 0 reads them with cnt_out[0] == 0).
@@ -147,20 +110,14 @@ __global__ __launch_bounds__(BLOCK) void k_color_first(color_round_args_t a, int
     if (in && !is_long) c = color_short_row<true>(a, v);
     if (c) a.colour[v] = c;
     top = max(top, c);
-    color_keep_short(a, in && !is_long && c == 0, v, stage, fill);
+    const bool keep = in && !is_long && c == 0;
+    wave_stage_push<COLOR_STAGE>(keep, v, stage, fill, a.s_out, a.cnt_out);
+    if (keep) atomicOr(a.bm_next + (v >> 5), 1u << (v & 31));
     // long rows: their segments into round 0's item list (one add per wave and pass)
-    const u64 lm = __ballot(is_long);
-    if (lm) {
-      const int segs = is_long ? (deg + COLOR_SEG - 1) / COLOR_SEG : 0;
-      const int incl = wave_inclusive_sum(segs);
-      int base_i = 0;
-      if (lane == WAVE - 1) base_i = atomicAdd(cnt0 + 1, incl);
-      base_i = __shfl(base_i, WAVE - 1, WAVE);
-      for (int s = 0; s < segs; ++s) l0[base_i + incl - segs + s] = make_int2(v, s);
-      long_rows += __popcll(lm);
-    }
+    wave_append_segments(is_long, v, deg, COLOR_SEG, l0, cnt0 + 1);
+    long_rows += __popcll(__ballot(is_long));
   }
-  color_flush(stage, fill, a.s_out, a.cnt_out);
+  wave_stage_flush(stage, fill, a.s_out, a.cnt_out);
   if (lane == 0 && long_rows) atomicAdd(cnt0 + 2, long_rows);
   color_note_max(a.max_colour, top);
 }
@@ -236,7 +193,7 @@ __global__ __launch_bounds__(BLOCK) void k_color_round(color_round_args_t a) {
     } else {
       if (lane == 0) atomicOr(a.bm_next + (v >> 5), 1u << (v & 31));
       ++long_rows;
-      if (segs > COLOR_STAGE - l_fill) color_flush(l_stage, l_fill, a.l_out, a.cnt_out + 1);
+      if (segs > COLOR_STAGE - l_fill) wave_stage_flush(l_stage, l_fill, a.l_out, a.cnt_out + 1);
       if (segs > COLOR_STAGE) {                            // (a row of more than COLOR_STAGE segments goes out on its own)
         int base_i = 0;
         if (lane == 0) base_i = atomicAdd(a.cnt_out + 1, segs);
@@ -248,7 +205,7 @@ __global__ __launch_bounds__(BLOCK) void k_color_round(color_round_args_t a) {
       }
     }
   }
-  color_flush(l_stage, l_fill, a.l_out, a.cnt_out + 1);
+  wave_stage_flush(l_stage, l_fill, a.l_out, a.cnt_out + 1);
   if (lane == 0 && long_rows) atomicAdd(a.cnt_out + 2, long_rows);
 
   for (long long base = (long long)wave * WAVE; base < ns; base += (long long)waves * WAVE) {
@@ -258,9 +215,11 @@ __global__ __launch_bounds__(BLOCK) void k_color_round(color_round_args_t a) {
     const int c = in ? color_short_row<ALL>(a, v) : 0;
     if (c) a.colour[v] = c;
     top = max(top, c);
-    color_keep_short(a, in && c == 0, v, s_stage, s_fill);
+    const bool keep = in && c == 0;
+    wave_stage_push<COLOR_STAGE>(keep, v, s_stage, s_fill, a.s_out, a.cnt_out);
+    if (keep) atomicOr(a.bm_next + (v >> 5), 1u << (v & 31));
   }
-  color_flush(s_stage, s_fill, a.s_out, a.cnt_out);
+  wave_stage_flush(s_stage, s_fill, a.s_out, a.cnt_out);
   color_note_max(a.max_colour, top);
 }
 

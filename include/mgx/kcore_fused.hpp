@@ -38,6 +38,7 @@
 
 #include "runtime.hpp"
 #include "wave.hpp"
+#include "worklist.hpp"
 
 namespace mgx {
 
@@ -88,26 +89,6 @@ struct kcore_step_args_t {
   int n;
   __device__ __forceinline__ int* f_short() const { return cand + max(n, 1); }
 };
-
-__device__ __forceinline__ void kcore_flush(int* stage, int& fill, int* out, int* counter) {
-  if (fill == 0) return;
-  wave_lds_fence();
-  int base = 0;
-  if (lane_id() == 0) base = atomicAdd(counter, fill);
-  base = __shfl(base, 0, WAVE);
-  for (int j = lane_id(); j < fill; j += WAVE) out[base + j] = stage[j];
-  wave_lds_fence();                                          // (read before the stage is filled again)
-  fill = 0;
-}
-// all lanes of the wave call it together; those with `take` append `item`
-__device__ __forceinline__ void kcore_push(bool take, int item, int* stage, int& fill, int* out, int* counter) {
-  const u64 m = __ballot(take);
-  if (!m) return;
-  const int c = __popcll(m);
-  if (fill + c > KCORE_STAGE) kcore_flush(stage, fill, out, counter);
-  if (take) stage[fill + rank_in_mask(m)] = item;
-  fill += c;
-}
 
 // A wave's share of the front being made: short rows wait in `rows`, long rows in `hubs`, each going out behind ONE returning add
 // that also carries their entries (upper half of the word); a long row goes out as its segments' items.
@@ -183,7 +164,7 @@ __device__ __forceinline__ void kcore_take(const kcore_step_args_t& a, kcore_wor
 #pragma unroll
   for (int j = 0; j < KCORE_UNROLL; ++j) old[j] = u[j] >= 0 ? atomicAdd(a.deg + u[j], -1) : 0;
 #pragma unroll
-  for (int j = 0; j < KCORE_UNROLL; ++j) kcore_push(u[j] >= 0 && old[j] == k, u[j], stage, fill, a.cand, &next->n_cand);
+  for (int j = 0; j < KCORE_UNROLL; ++j) wave_stage_push<KCORE_STAGE>(u[j] >= 0 && old[j] == k, u[j], stage, fill, a.cand, &next->n_cand);
 }
 
 // What MINI keeps in LDS: the front (vertex, running sum of the row lengths before it), the candidates, and two counters --
@@ -432,7 +413,7 @@ __global__ __launch_bounds__(BLOCK) void k_kcore_step(kcore_step_args_t a, unsig
     for (int d = WAVE / 2; d > 0; d >>= 1) longest = max(longest, __shfl_xor(longest, d, WAVE));
     for (int j = 0; j < longest; j += KCORE_UNROLL) kcore_take(a, next, beg + j, 1, beg + len, k, stage, fill);
   }
-  kcore_flush(stage, fill, a.cand, &next->n_cand);
+  wave_stage_flush(stage, fill, a.cand, &next->n_cand);
 }
 
 // The scratch of a graph's fused k-core (the core numbers and degrees are the problem's), and the run (host side)

@@ -24,10 +24,11 @@
 #include <cmath>
 #include <vector>
 
-#include "color_fused.hpp"
+#include "color_hash.hpp"
 #include "runtime.hpp"
 #include "scan.hpp"
 #include "wave.hpp"
+#include "worklist.hpp"
 
 namespace mgx {
 
@@ -88,15 +89,7 @@ __global__ __launch_bounds__(BLOCK) void k_lspar_classify(lspar_args_t a) {
     const int v = (int)base + lane;
     const int d = v < a.n ? a.ro[v + 1] - a.ro[v] : 0;
     cut += (d > 0 && lspar_keep(d, a.e) < d) ? 1 : 0;
-    const bool is_long = d > LSPAR_SHORT_MAX;
-    if (__ballot(is_long)) {
-      const int segs = is_long ? (d + LSPAR_SEG - 1) / LSPAR_SEG : 0;
-      const int incl = wave_inclusive_sum(segs);
-      int at = 0;
-      if (lane == WAVE - 1) at = atomicAdd(a.cnt, incl);
-      at = __shfl(at, WAVE - 1, WAVE);
-      for (int s = 0; s < segs; ++s) a.items[at + incl - segs + s] = make_int2(v, s);
-    }
+    wave_append_segments(d > LSPAR_SHORT_MAX, v, d, LSPAR_SEG, a.items, a.cnt);
   }
   cut = wave_sum(cut);
   if (lane == 0 && cut) atomicAdd(a.cnt + 1, cut);

@@ -17,7 +17,7 @@
 //                         vertex only ever moves forward.
 // A round (each step a launch; rt is the snapshot of the roots the last compress left, read-only all round):
 //   work list   live vertices (cursor not at the end): rows with at least MST_LONG_MIN entries left are long, an item per MST_SEG
-//               entries from the cursor on; the others short, compacted through a wave-private LDS stage (k_cc_worklist's)
+//               entries from the cursor on; the others short, compacted through a wave-private LDS stage (worklist.hpp)
 //   scan        a short row a lane: walk from the cursor to the first entry with rt[nbr] != rt[v].  A long item a wave: 64 entries a
 //               step, a __ballot finds the first that leaves; the windows of one row meet in an atomicMin on the row's position
 //               word (a window behind a position already found gives up: an optimisation, never needed for the result)
@@ -68,12 +68,14 @@
 #include "scan.hpp"
 #include "segsort.hpp"
 #include "wave.hpp"
+#include "worklist.hpp"
 
 namespace mgx {
 
 constexpr int MST_LONG_MIN_DEFAULT = 64;   // rows with at least this many entries left go to the wave path (unmeasured guess)
 constexpr int MST_SEG_DEFAULT = 2048;      // entries of a long row's window (unmeasured guess; CC_SEG's value)
 constexpr u32 MST_NONE = 0x7FFFFFFFu;      // no position
+constexpr int MST_LIST_STAGE = 2 * WAVE;   // a wave's LDS stage of short-row items
 constexpr int MST_SUM_TILE = 2048;         // list entries one workgroup sums
 
 // stat words of a run, as read back
@@ -196,17 +198,7 @@ __global__ __launch_bounds__(BLOCK) void k_mst_sort_classify(segsort_args_t<u64,
   for (long long base = (long long)blockIdx.x * BLOCK; base < n; base += (long long)gridDim.x * BLOCK) {
     const int v = (int)base + (int)threadIdx.x;
     const int len = v < n ? off[v + 1] - off[v] : 0;
-    segsort_append(len >= 2 && len <= SEGSORT_WAVE_MAX, v, s.short_list, s.cnt + 0);
-    segsort_append(len > SEGSORT_WAVE_MAX && len <= SEGSORT_TILE, v, s.mid_list, s.cnt + 1);
-    const bool is_long = len > SEGSORT_TILE;
-    if (__ballot(is_long)) {
-      const int tiles = is_long ? (len + SEGSORT_TILE - 1) / SEGSORT_TILE : 0;
-      const int incl = wave_inclusive_sum(tiles);
-      int at = 0;
-      if (lane_id() == WAVE - 1) at = atomicAdd(s.cnt + 2, incl);
-      at = __shfl(at, WAVE - 1, WAVE);
-      for (int t = 0; t < tiles; ++t) s.tile_list[at + incl - tiles + t] = make_int2(v, t);
-    }
+    segsort_classify_one(s, v, len);
   }
 }
 
@@ -238,23 +230,12 @@ __global__ __launch_bounds__(BLOCK) void k_mst_init(int* comp, int* rt, int* cur
   }
 }
 
-// a long row's windows: one add per wave for all its lanes' rows
-__device__ __forceinline__ void mst_keep_long(bool keep, int v, int len, int seg, int2* out, int* counter) {
-  if (!__ballot(keep)) return;
-  const int segs = keep ? (len + seg - 1) / seg : 0;
-  const int incl = wave_inclusive_sum(segs);
-  int base = 0;
-  if (lane_id() == WAVE - 1) base = atomicAdd(counter, incl);
-  base = __shfl(base, WAVE - 1, WAVE);
-  for (int s = 0; s < segs; ++s) out[base + incl - segs + s] = make_int2(v, s);
-}
-
 __global__ __launch_bounds__(BLOCK) void k_mst_worklist(mst_round_args_t a) {
   if (a.words[MST_W_DONE]) return;
   const int lane = lane_id();
   const int wave = (int)((blockIdx.x * (unsigned)BLOCK + threadIdx.x) / WAVE);
   const int waves = (int)(gridDim.x * (BLOCK / WAVE));
-  __shared__ int s_stage[WAVES_PER_BLOCK][CC_STAGE];
+  __shared__ int s_stage[WAVES_PER_BLOCK][MST_LIST_STAGE];
   int* const stage = s_stage[threadIdx.x / WAVE];
   int fill = 0;
   for (long long base = (long long)wave * WAVE; base < a.n; base += (long long)waves * WAVE) {
@@ -266,10 +247,11 @@ __global__ __launch_bounds__(BLOCK) void k_mst_worklist(mst_round_args_t a) {
       a.cw[v] = 0xFFFFFFFFu;
       a.cp[v] = ~0ull;
     }
-    cc_keep_short(rem > 0 && rem < a.long_min, v, stage, fill, a.s_list, a.words + MST_W_SHORT);
-    mst_keep_long(rem >= a.long_min && rem > 0, v, rem, a.seg, a.l_list, a.words + MST_W_LONG);
+    // short rows through the wave's LDS stage, long rows' windows behind one add per wave and pass (worklist.hpp)
+    wave_stage_push<MST_LIST_STAGE>(rem > 0 && rem < a.long_min, v, stage, fill, a.s_list, a.words + MST_W_SHORT);
+    wave_append_segments(rem >= a.long_min && rem > 0, v, rem, a.seg, a.l_list, a.words + MST_W_LONG);
   }
-  cc_flush(stage, fill, a.s_list, a.words + MST_W_SHORT);
+  wave_stage_flush(stage, fill, a.s_list, a.words + MST_W_SHORT);
 }
 
 // long items a wave each, then short rows a lane each; the grid is sized to the chip, the counts come from the device

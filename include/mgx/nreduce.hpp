@@ -600,6 +600,44 @@ inline size_t nr_scratch_bytes(long long n, long long units_pad, size_t value_si
   return (((size_t)n + 64) * value_size + 255) / 256 * 256 + ((size_t)units_pad + 64) * value_size;
 }
 
+// A graph's side of the fast path (Graph: gunrock's graph_device_t; Context: anything with scratch_bytes).
+// nr_units_valid: the graph carries what the kernels read -- the hub-first layout the library built (degree classes, the dummy
+// entries) with the unit blocks of its rows from the long-row threshold on; the slices are built for such graphs only.
+template <typename Graph>
+bool nr_units_valid(const Graph& g) {
+  return g.has_layout && g.rows.ub.units > 0 && g.rows.ub_min_degree == g.rows.vs_long_min && g.rows.vs_long_min >= 17 &&
+         g.rows.vs_long_min <= 64 && g.rows.ub.cnt.size() && g.rows.ub.first.size() && g.rows.vs_dummy != 0;
+}
+// The view of such a graph for values of value_size bytes: the unit blocks (the caller sees to the scratch for units_pad partials),
+// and with `slices` the long rows by slice (nrs_mu != NULL) when the graph carries them and the scratch arena holds a partial per
+// mini-unit.  parts, pos and pos_epoch are the call's: left at their defaults.
+template <typename Graph, typename Context>
+nr_layout_t nr_layout_of(const Graph& g, const Context& ctx, size_t value_size, bool slices) {
+  nr_layout_t L;
+  L.new_of_old = g.d_new_of_old.data();
+  L.row_offsets = (const u32*)g.d_layout_row_offsets.data();
+  L.col_indices = g.d_layout_col_indices.data();
+  L.old_of_new = g.d_old_of_new.data();
+  L.ub_col = g.rows.ub.col.size() ? g.rows.ub.col.data() : nullptr;          // (gone when the layout carries the 24-bit copy)
+  L.ub_col24 = g.rows.ub.col24.size() ? g.rows.ub.col24.data() : nullptr;    // (the 24-bit copy whenever the layout has one: 0.492 -> 0.477 ms)
+  L.ub_cnt = g.rows.ub.cnt.data();
+  L.ub_first = g.rows.ub.first.data();
+  L.ub_units = (u32)g.rows.ub.units; L.ub_units_pad = (u32)g.rows.ub.units_pad;
+  for (int i = 0; i < 4; ++i) L.vs_v[i] = g.rows.vs_v[i];
+  L.vs_dummy = g.rows.vs_dummy;
+  L.big_rows = g.nr_big_rows;
+  L.n = g.num_nodes;
+  if (slices && g.nrs_units > 0 && g.nrs_slices > 0 && g.nrs_rows == g.rows.vs_v[0] && g.d_nrs_mu.size() && g.d_nrs_off.size() &&
+      ctx.scratch_bytes >= nr_scratch_bytes(g.num_nodes, g.nrs_units, value_size)) {
+    L.nrs_mu = (const uint4*)g.d_nrs_mu.data();
+    L.nrs_off = g.d_nrs_off.data();
+    for (int i = 0; i < NRS_MAX_SLICES + 2; ++i) L.nrs_first[i] = g.nrs_first[i];
+    L.nrs_slices = g.nrs_slices; L.nrs_rows = g.nrs_rows;
+    for (int i = 0; i < 3; ++i) L.nrs_tier[i] = g.nrs_tier[i];
+  }
+  return L;
+}
+
 // The whole fast path.  get(old_id) -> V; reduced: n entries; frontier: n ids (checked to be 0 .. n - 1 by the first kernel).
 // Everything is enqueued on the context's stream; the kernels behind the first return at once if *dev_flag == epoch.
 // nf == n: the frontier must be 0 .. n - 1 (results by original id).  nf < n (round 6): a strictly ascending subset -- results by frontier

@@ -21,6 +21,7 @@
 
 #include "runtime.hpp"
 #include "wave.hpp"
+#include "worklist.hpp"
 
 namespace mgx {
 
@@ -50,14 +51,13 @@ __device__ __forceinline__ void segsort_bounds(const int* heads, int ns, int cou
   e = s == ns ? count : heads[s];
 }
 
-// one wave-aggregated append of `take` (this lane's item) to list / counter
-__device__ __forceinline__ void segsort_append(bool take, int item, int* list, int* counter) {
-  const u64 m = __ballot(take);
-  if (!m) return;
-  int base = 0;
-  if (lane_id() == 0) base = atomicAdd(counter, __popcll(m));
-  base = __shfl(base, 0, WAVE);
-  if (take) list[base + rank_in_mask(m)] = item;
+// segment s of len items (0: no segment in this lane) into the list of its band; a longer one a (segment, tile) item per tile.
+// All lanes of the wave call it.
+template <typename K, typename V>
+__device__ __forceinline__ void segsort_classify_one(const segsort_args_t<K, V>& a, int s, int len) {
+  wave_append(len >= 2 && len <= SEGSORT_WAVE_MAX, s, a.short_list, a.cnt + 0);
+  wave_append(len > SEGSORT_WAVE_MAX && len <= SEGSORT_TILE, s, a.mid_list, a.cnt + 1);
+  wave_append_segments(len > SEGSORT_TILE, s, len, SEGSORT_TILE, a.tile_list, a.cnt + 2);
 }
 
 template <typename K, typename V>
@@ -71,18 +71,8 @@ __global__ __launch_bounds__(BLOCK) void k_segsort_classify(segsort_args_t<K, V>
       segsort_bounds(a.heads, a.num_segments, a.count, s, b, e);
       len = e - b;
     }
-    segsort_append(len >= 2 && len <= SEGSORT_WAVE_MAX, s, a.short_list, a.cnt + 0);
-    segsort_append(len > SEGSORT_WAVE_MAX && len <= SEGSORT_TILE, s, a.mid_list, a.cnt + 1);
-    const bool is_long = len > SEGSORT_TILE;
-    if (__ballot(is_long)) {
-      const int tiles = is_long ? (len + SEGSORT_TILE - 1) / SEGSORT_TILE : 0;
-      const int incl = wave_inclusive_sum(tiles);
-      int at = 0;
-      if (lane_id() == WAVE - 1) at = atomicAdd(a.cnt + 2, incl);
-      at = __shfl(at, WAVE - 1, WAVE);
-      for (int t = 0; t < tiles; ++t) a.tile_list[at + incl - tiles + t] = make_int2(s, t);
-      if (is_long) atomicMax(a.cnt + 3, len);
-    }
+    segsort_classify_one(a, s, len);
+    if (len > SEGSORT_TILE) atomicMax(a.cnt + 3, len);
   }
 }
 

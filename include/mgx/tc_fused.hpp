@@ -18,7 +18,7 @@
 //                count admits (a pass over a row that is sorted already copies it)
 //   dedup        count -> scan -> fill once more, dropping adjacent duplicates
 //   dag stats    sdeg[v] = d+(v) + DAG entries that name v; m_dag, the longest row, the wedges
-//   work list    vertices with d+ >= 2 by d+ into three lists, compacted through LDS as k_cc_worklist does
+//   work list    vertices with d+ >= 2 by d+ into three lists, compacted through wave-private LDS stages (worklist.hpp)
 // Sizes: the arrays hold m entries (m_dag <= m < 2^31 by construction; a CSR of more than 2^30 entries is refused at the first
 // run), every scan's total is checked on the device against them before anything is written behind it; a failed check and a
 // failed allocation are statuses (MGX_E_FRONTIER_OVERFLOW, MGX_E_HIP).
@@ -39,17 +39,18 @@
 #include <algorithm>
 #include <vector>
 
-#include "cc_fused.hpp"
 #include "env.hpp"
 #include "runtime.hpp"
 #include "scan.hpp"
 #include "segsort.hpp"
 #include "wave.hpp"
+#include "worklist.hpp"
 
 namespace mgx {
 
 constexpr int TC_SHORT_MAX_DEFAULT = 16;     // rows of at most this many oriented entries: k_tc_short
 constexpr int TC_WAVE_MAX_DEFAULT = 256;     // ... : k_tc_wave; longer: k_tc_block
+constexpr int TC_LIST_STAGE = 2 * WAVE;      // a wave's LDS stage of work-list items, per list
 constexpr int TC_WAVE_STAGE = 512;           // entries of a wave's LDS stage
 constexpr int TC_BLOCK_STAGE = 4096;         // entries of a workgroup's
 constexpr int TC_GROUP = 16;                 // lanes that stream one row b
@@ -206,17 +207,7 @@ __global__ __launch_bounds__(BLOCK) void k_tc_sort_classify(segsort_args_t<int, 
   for (long long base = (long long)blockIdx.x * BLOCK; base < n; base += (long long)gridDim.x * BLOCK) {
     const int v = (int)base + (int)threadIdx.x;
     const int len = v < n ? ro[v + 1] - ro[v] : 0;
-    segsort_append(len >= 2 && len <= SEGSORT_WAVE_MAX, v, s.short_list, s.cnt + 0);
-    segsort_append(len > SEGSORT_WAVE_MAX && len <= SEGSORT_TILE, v, s.mid_list, s.cnt + 1);
-    const bool is_long = len > SEGSORT_TILE;
-    if (__ballot(is_long)) {
-      const int tiles = is_long ? (len + SEGSORT_TILE - 1) / SEGSORT_TILE : 0;
-      const int incl = wave_inclusive_sum(tiles);
-      int at = 0;
-      if (lane_id() == WAVE - 1) at = atomicAdd(s.cnt + 2, incl);
-      at = __shfl(at, WAVE - 1, WAVE);
-      for (int t = 0; t < tiles; ++t) s.tile_list[at + incl - tiles + t] = make_int2(v, t);
-    }
+    segsort_classify_one(s, v, len);
   }
 }
 
@@ -266,7 +257,7 @@ __global__ __launch_bounds__(BLOCK) void k_tc_worklist(tc_list_args_t a) {
   const int lane = lane_id();
   const int wave = (int)((blockIdx.x * (unsigned)BLOCK + threadIdx.x) / WAVE);
   const int waves = (int)(gridDim.x * (BLOCK / WAVE));
-  __shared__ int s_stage[WAVES_PER_BLOCK][3][CC_STAGE];
+  __shared__ int s_stage[WAVES_PER_BLOCK][3][TC_LIST_STAGE];
   int* const st0 = s_stage[threadIdx.x / WAVE][0];
   int* const st1 = s_stage[threadIdx.x / WAVE][1];
   int* const st2 = s_stage[threadIdx.x / WAVE][2];
@@ -274,13 +265,13 @@ __global__ __launch_bounds__(BLOCK) void k_tc_worklist(tc_list_args_t a) {
   for (long long base = (long long)wave * WAVE; base < a.n; base += (long long)waves * WAVE) {
     const int v = (int)base + lane;
     const int d = v < a.n ? a.ro[v + 1] - a.ro[v] : 0;
-    cc_keep_short(d >= 2 && d <= a.short_max, v, st0, f0, a.s_list, a.cnt + 0);
-    cc_keep_short(d >= 2 && d > a.short_max && d <= a.wave_max, v, st1, f1, a.m_list, a.cnt + 1);
-    cc_keep_short(d >= 2 && d > a.short_max && d > a.wave_max, v, st2, f2, a.l_list, a.cnt + 2);
+    wave_stage_push<TC_LIST_STAGE>(d >= 2 && d <= a.short_max, v, st0, f0, a.s_list, a.cnt + 0);
+    wave_stage_push<TC_LIST_STAGE>(d >= 2 && d > a.short_max && d <= a.wave_max, v, st1, f1, a.m_list, a.cnt + 1);
+    wave_stage_push<TC_LIST_STAGE>(d >= 2 && d > a.short_max && d > a.wave_max, v, st2, f2, a.l_list, a.cnt + 2);
   }
-  cc_flush(st0, f0, a.s_list, a.cnt + 0);
-  cc_flush(st1, f1, a.m_list, a.cnt + 1);
-  cc_flush(st2, f2, a.l_list, a.cnt + 2);
+  wave_stage_flush(st0, f0, a.s_list, a.cnt + 0);
+  wave_stage_flush(st1, f1, a.m_list, a.cnt + 1);
+  wave_stage_flush(st2, f2, a.l_list, a.cnt + 2);
 }
 
 struct tc_count_args_t {

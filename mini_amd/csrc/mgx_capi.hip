@@ -1,6 +1,9 @@
 // mgx_capi.hip -- implementation of the C-ABI declared in include/mgx.h.
-// Pre-instantiates the operator templates of include/gunrock/*.hxx for the in-scope functors
-// (BFS, SSSP, PR) and exposes the building blocks.  Built with
+// Pre-instantiates the operator templates of include/gunrock/*.hxx for the in-scope functors (BFS, SSSP, PR, k-core, colouring,
+// lspar, CC, TC, BC, PageRank, MST), exposes the building blocks and runs the fused paths of include/mgx/*_fused.hpp.
+// Every algorithm's handle is an mgx_problem_s (its graph) plus what its two paths keep; the entry points share enter() (device
+// and stream current, context and graph), create_handle / free_handle, require_run ("no run yet"), read_back (a result to the
+// host) and put_stats.  Built with
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Iinclude
 // into mini_amd/libmgx.so (see __graft_entry__.build()).
 #include <cstdlib>
@@ -55,8 +58,14 @@ struct mgx_frontier_s {
   mgx_ctx_s* c;
   std::shared_ptr<frontier_t<int>> f;
 };
-struct mgx_bfs_s {
-  mgx_graph_s* g;
+// what every algorithm's handle starts with: the graph it was made for
+struct mgx_problem_s {
+  mgx_graph_s* g = nullptr;
+  standard_context_t& ctx() const { return *g->c->ctx; }
+  graph_device_t& graph() const { return *g->g; }
+  size_t n() const { return (size_t)g->g->num_nodes; }
+};
+struct mgx_bfs_s : mgx_problem_s {
   std::shared_ptr<bfs::bfs_problem_t> p;
   std::unique_ptr<bfs::bfs_enactor_t> e;              // lazily: holds two m-capacity buffers
   std::unique_ptr<bfs::bfs_fused_enactor_t> fe;       // lazily: O(n)
@@ -64,8 +73,7 @@ struct mgx_bfs_s {
   mem_t<unsigned> visited_mask;                       // lazily: the idempotent mode's bitmask ((n + 31) / 32 words)
   int time_kernels = -1;                              // -1: environment default
 };
-struct mgx_sssp_s {
-  mgx_graph_s* g;
+struct mgx_sssp_s : mgx_problem_s {
   std::shared_ptr<sssp::sssp_problem_t> p;
   std::unique_ptr<sssp::sssp_enactor_t> e;
   float e_sizing = 0.f;
@@ -75,20 +83,17 @@ struct mgx_sssp_s {
   bool preds_stale = false;
   int preds_src = 0;
 };
-struct mgx_pr_s {
-  mgx_graph_s* g;
+struct mgx_pr_s : mgx_problem_s {
   std::shared_ptr<pr::pr_problem_t> p;
   std::unique_ptr<pr::pr_enactor_t> e;
 };
-struct mgx_kcore_s {
-  mgx_graph_t g = nullptr;
+struct mgx_kcore_s : mgx_problem_s {
   std::shared_ptr<kcore::kcore_problem_t> p;
   std::unique_ptr<kcore::kcore_enactor_t> e;
   std::unique_ptr<mgx::kcore_fused_state_t> fused;                // lazily: the fused path's worklists and state words
 };
 
-struct mgx_color_s {
-  mgx_graph_t g = nullptr;
+struct mgx_color_s : mgx_problem_s {
   std::unique_ptr<mgx::color_fused_state_t> fused;                // lazily: the fused path's O(n) state
   std::shared_ptr<coloring::coloring_problem_t> p;                // lazily: the operator path's
   std::unique_ptr<coloring::coloring_enactor_t> e;
@@ -96,8 +101,7 @@ struct mgx_color_s {
   std::vector<long long> trace;                                   // its active vertices per round
 };
 
-struct mgx_lspar_s {
-  mgx_graph_t g = nullptr;
+struct mgx_lspar_s : mgx_problem_s {
   std::unique_ptr<mgx::lspar_fused_state_t> fused;                // lazily: the fused path's state
   std::shared_ptr<lspar::lspar_problem_t> p;                      // lazily: the operator path's
   std::unique_ptr<lspar::lspar_enactor_t> e;
@@ -111,8 +115,7 @@ struct mgx_lspar_s {
   long long kept = 0;
 };
 
-struct mgx_cc_s {
-  mgx_graph_t g = nullptr;
+struct mgx_cc_s : mgx_problem_s {
   std::unique_ptr<mgx::cc_fused_state_t> fused;                   // lazily: the fused path's O(n + m / 32) state
   std::shared_ptr<cc::cc_problem_t> p;                            // lazily: the operator path's
   std::unique_ptr<cc::cc_enactor_t> e;
@@ -120,15 +123,13 @@ struct mgx_cc_s {
   const int* labels = nullptr;                                    // the last run's labels (nullptr: no run yet)
 };
 
-struct mgx_tc_s {
-  mgx_graph_t g = nullptr;
+struct mgx_tc_s : mgx_problem_s {
   std::unique_ptr<mgx::tc_state_t> st;                            // lazily: the DAGs (per `symmetric`), their work lists, tri
   std::shared_ptr<tc::tc_problem_t> p[2];                         // lazily: the operator path's view of dag[symmetric]
   std::unique_ptr<tc::tc_enactor_t> e;
 };
 
-struct mgx_bc_s {
-  mgx_graph_t g = nullptr;
+struct mgx_bc_s : mgx_problem_s {
   std::unique_ptr<mgx::bc_state_t> st;                            // lazily: the row classes, the level lists, P / Q, sigma, delta, bc
   std::shared_ptr<bfs::bfs_problem_t> bp;                         // lazily: the traversal's labels (both paths write them)
   std::unique_ptr<bfs::bfs_fused_enactor_t> fe;                   // lazily: the fused path's traversal
@@ -138,14 +139,12 @@ struct mgx_bc_s {
   int last_levels = 0;                                            // levels of the last source of the last run
 };
 
-struct mgx_pagerank_s {
-  mgx_graph_t g = nullptr;
+struct mgx_pagerank_s : mgx_problem_s {
   std::shared_ptr<pagerank::pagerank_problem_t> p;                // lazily: the O(n) state both paths run on
   std::unique_ptr<pagerank::pagerank_enactor_t> e;                // lazily: the operator path's iota frontier
 };
 
-struct mgx_mst_s {
-  mgx_graph_t g = nullptr;
+struct mgx_mst_s : mgx_problem_s {
   std::unique_ptr<mgx::mst_fused_state_t> fused;                  // lazily: the fused path's state and its sorted incident arrays
   std::shared_ptr<mst::mst_problem_t> p;                          // lazily: the operator path's
   std::unique_ptr<mst::mst_enactor_t> e;
@@ -210,6 +209,51 @@ static thread_local std::string g_last_error;
 // every entry point: the handle's device, and its stream as the one the context-less copies are ordered on
 static inline void use_device(mgx_ctx_s* c) { MGX_HIP(hipSetDevice(c->device)); c->ctx->make_current(); }
 
+// ---- what the algorithms' entry points share (the handles are mgx_problem_s) ----
+// An entry point's prologue: the handle checked, its device and stream current; `auto [ctx, g] = enter(p);`
+struct entered_t {
+  standard_context_t& ctx;
+  graph_device_t& g;
+};
+static entered_t enter(const mgx_problem_s* p) {
+  MGX_REQUIRE(p, "NULL argument");
+  use_device(p->g->c);
+  return {p->ctx(), p->graph()};
+}
+template <typename H>
+static int create_handle(mgx_graph_t g, H** out) {
+  MGX_TRY
+  MGX_REQUIRE(g && out, "NULL argument");
+  auto* h = new H();
+  h->g = g;
+  *out = h;
+  MGX_CATCH
+}
+// Whatever the handle's last run enqueued on the context's stream is over before its memory goes.
+template <typename H>
+static int free_handle(H* p) {
+  MGX_TRY
+  if (p) { use_device(p->g->c); p->ctx().synchronize(); delete p; }
+  MGX_CATCH
+}
+static void require_run(bool ran, const char* who) {
+  if (!ran) throw mgx::mgx_error(MGX_E_INVALID, std::string(who) + ": no run yet");
+}
+// `count` values of a result to the host, behind a wait for the context's stream (the copy alone is ordered on that stream as
+// well; of the two things the getters did the wait is the stricter one, and every getter does it now)
+template <typename T>
+static void read_back(const mgx_problem_s* p, T* host, const T* src, size_t count) {
+  use_device(p->g->c);
+  p->ctx().synchronize();
+  if (count) MGX_HIP(mgx::dtoh(host, src, count));
+}
+// the `count` words an entry point's header promises, when the caller wants them (a run that returns another number of them
+// is refused, not written past the caller's array)
+static void put_stats(int64_t* stats, size_t count, const std::vector<long long>& v) {
+  MGX_REQUIRE(v.size() == count, "internal: a run's stats do not have the size the header states");
+  if (stats) std::copy(v.begin(), v.end(), stats);
+}
+
 // neighbourhood reduce with a plain per-vertex gather as the functor
 namespace {
 template <typename V>
@@ -242,8 +286,7 @@ static void ensure_nr_slices(mgx_graph_s* g) {
   if (G.nrs_tried) return;
   G.nrs_tried = true;
   if (const char* e = mgx::env("MGX_NR_SLICED")) if (atoi(e) == 0) return;
-  if (!G.has_layout || G.rows.ub.units <= 0 || !G.rows.ub.first.size() || G.rows.vs_long_min != G.rows.ub_min_degree || G.rows.vs_long_min < 17 || G.rows.vs_long_min > 64 ||
-      G.rows.vs_v[0] == 0 || G.rows.vs_dummy == 0) return;
+  if (!mgx::nr_units_valid(G) || G.rows.vs_v[0] == 0) return;                  // (no fast path on this graph, or no long rows)
   standard_context_t& ctx = *g->c->ctx;
   const unsigned S = (unsigned)mgx::NR_HOTV;
   const long long n = G.num_nodes;
@@ -1042,17 +1085,13 @@ int mgx_bfs_free(mgx_bfs_t p) {
 int mgx_bfs_labels(mgx_bfs_t p, int* host) {
   MGX_TRY
   MGX_REQUIRE(p && host, "NULL argument");
-  use_device(p->g->c);
-  p->g->c->ctx->synchronize();
-  MGX_HIP(mgx::dtoh(host, p->p->d_labels.data(), (size_t)p->g->g->num_nodes));
+  read_back(p, host, p->p->d_labels.data(), p->n());
   MGX_CATCH
 }
 int mgx_bfs_preds(mgx_bfs_t p, int* host) {
   MGX_TRY
   MGX_REQUIRE(p && host, "NULL argument");
-  use_device(p->g->c);
-  p->g->c->ctx->synchronize();
-  MGX_HIP(mgx::dtoh(host, p->p->d_preds.data(), (size_t)p->g->g->num_nodes));
+  read_back(p, host, p->p->d_preds.data(), p->n());
   MGX_CATCH
 }
 int mgx_bfs_labels_device(mgx_bfs_t p, int** d) {
@@ -1944,9 +1983,7 @@ int mgx_sssp_free(mgx_sssp_t p) {
 int mgx_sssp_distances(mgx_sssp_t p, float* host) {
   MGX_TRY
   MGX_REQUIRE(p && host, "NULL argument");
-  use_device(p->g->c);
-  p->g->c->ctx->synchronize();
-  MGX_HIP(mgx::dtoh(host, p->p->d_labels.data(), (size_t)p->g->g->num_nodes));
+  read_back(p, host, p->p->d_labels.data(), p->n());
   MGX_CATCH
 }
 // the fused loop keeps no predecessors (sssp_fused.hpp); they are built from its distances the first time they are asked for
@@ -1970,8 +2007,7 @@ int mgx_sssp_preds(mgx_sssp_t p, int* host) {
   MGX_REQUIRE(p && host, "NULL argument");
   use_device(p->g->c);
   sssp_preds_if_stale(p);
-  p->g->c->ctx->synchronize();
-  MGX_HIP(mgx::dtoh(host, p->p->d_preds.data(), (size_t)p->g->g->num_nodes));
+  read_back(p, host, p->p->d_preds.data(), p->n());
   MGX_CATCH
 }
 int mgx_sssp_distances_device(mgx_sssp_t p, float** d) {
@@ -2175,9 +2211,7 @@ int mgx_pr_enact(mgx_pr_t p, int64_t* lens, int* iterations) {
 int mgx_pr_ranks(mgx_pr_t p, float* host) {
   MGX_TRY
   MGX_REQUIRE(p && host, "NULL argument");
-  use_device(p->g->c);
-  p->g->c->ctx->synchronize();
-  MGX_HIP(mgx::dtoh(host, p->p->d_current_ranks.data(), (size_t)p->g->g->num_nodes));
+  read_back(p, host, p->p->d_current_ranks.data(), p->n());
   MGX_CATCH
 }
 
@@ -2195,39 +2229,26 @@ int mgx_kcore_create(mgx_graph_t g, mgx_kcore_t* out) {
 }
 int mgx_kcore_reset(mgx_kcore_t p) {
   MGX_TRY
-  MGX_REQUIRE(p, "NULL argument");
-  use_device(p->g->c);
-  p->p->reset(*p->g->c->ctx);
+  standard_context_t& ctx = enter(p).ctx;
+  p->p->reset(ctx);
   MGX_CATCH
 }
-int mgx_kcore_free(mgx_kcore_t p) {
-  MGX_TRY
-  if (p) { use_device(p->g->c); delete p; }
-  MGX_CATCH
-}
+int mgx_kcore_free(mgx_kcore_t p) { return free_handle(p); }
 int mgx_kcore_enact(mgx_kcore_t p, int* largest_k_core, int64_t* stats) {
   MGX_TRY
   MGX_REQUIRE(p && largest_k_core, "NULL argument");
-  use_device(p->g->c);
-  standard_context_t& ctx = *p->g->c->ctx;
-  if (!p->e) p->e.reset(new kcore::kcore_enactor_t(ctx, p->g->g->num_nodes, p->g->g->num_edges));
+  auto [ctx, g] = enter(p);
+  if (!p->e) p->e.reset(new kcore::kcore_enactor_t(ctx, g.num_nodes, g.num_edges));
   p->e->enact(p->p, ctx);
   ctx.synchronize();
   *largest_k_core = p->p->largest_k_core;
-  if (stats) {
-    stats[0] = p->e->rounds;
-    stats[1] = p->e->passes;
-    stats[2] = p->e->expanded;
-    stats[3] = p->e->removed;
-  }
+  put_stats(stats, 4, {p->e->rounds, p->e->passes, p->e->expanded, p->e->removed});
   MGX_CATCH
 }
 int mgx_kcore_run(mgx_kcore_t p, int* largest_k_core, int64_t* stats) {
   MGX_TRY
   MGX_REQUIRE(p && largest_k_core, "NULL argument");
-  use_device(p->g->c);
-  standard_context_t& ctx = *p->g->c->ctx;
-  graph_device_t& g = *p->g->g;
+  auto [ctx, g] = enter(p);
   if (!p->fused) p->fused.reset(new mgx::kcore_fused_state_t(g.num_nodes, g.num_edges, ctx));
   p->p->reset(ctx);                               // every run starts afresh: core numbers 0, degrees = row lengths
   int largest = -1;
@@ -2235,8 +2256,7 @@ int mgx_kcore_run(mgx_kcore_t p, int* largest_k_core, int64_t* stats) {
                                                   p->p->d_num_cores.data(), ctx, largest);
   p->p->largest_k_core = largest;
   *largest_k_core = largest;
-  if (stats)
-    for (int j = 0; j < 6; ++j) stats[j] = st[(size_t)j];
+  put_stats(stats, 6, st);
   MGX_CATCH
 }
 int mgx_kcore_step_kinds(mgx_kcore_t p, int* host_kinds, int cap, int64_t* launches) {
@@ -2253,61 +2273,33 @@ int mgx_kcore_step_kinds(mgx_kcore_t p, int* host_kinds, int cap, int64_t* launc
 int mgx_kcore_num_cores(mgx_kcore_t p, int* host) {
   MGX_TRY
   MGX_REQUIRE(p && host, "NULL argument");
-  use_device(p->g->c);
-  p->g->c->ctx->synchronize();
-  MGX_HIP(mgx::dtoh(host, p->p->d_num_cores.data(), (size_t)p->g->g->num_nodes));
+  read_back(p, host, p->p->d_num_cores.data(), p->n());
   MGX_CATCH
 }
 int mgx_kcore_degrees(mgx_kcore_t p, int* host) {
   MGX_TRY
   MGX_REQUIRE(p && host, "NULL argument");
-  use_device(p->g->c);
-  p->g->c->ctx->synchronize();
-  MGX_HIP(mgx::dtoh(host, p->p->d_degrees.data(), (size_t)p->g->g->num_nodes));
+  read_back(p, host, p->p->d_degrees.data(), p->n());
   MGX_CATCH
 }
 
 
 // ---- graph colouring -------------------------------------------------------------------------
-int mgx_color_create(mgx_graph_t g, mgx_color_t* out) {
-  MGX_TRY
-  MGX_REQUIRE(g && out, "NULL argument");
-  auto* h = new mgx_color_s();
-  h->g = g;
-  *out = h;
-  MGX_CATCH
-}
-int mgx_color_free(mgx_color_t p) {
-  MGX_TRY
-  if (p) { use_device(p->g->c); delete p; }
-  MGX_CATCH
-}
-static void color_stats(int64_t* stats, long long rounds, long long left, long long largest, long long waits) {
-  if (!stats) return;
-  stats[0] = rounds;
-  stats[1] = left;
-  stats[2] = largest;
-  stats[3] = waits;
-}
+int mgx_color_create(mgx_graph_t g, mgx_color_t* out) { return create_handle(g, out); }
+int mgx_color_free(mgx_color_t p) { return free_handle(p); }
 int mgx_color_run(mgx_color_t p, unsigned seed, int max_iter, int64_t* stats) {
   MGX_TRY
-  MGX_REQUIRE(p, "NULL argument");
-  use_device(p->g->c);
-  standard_context_t& ctx = *p->g->c->ctx;
-  graph_device_t& g = *p->g->g;
+  auto [ctx, g] = enter(p);
   if (!p->fused) p->fused.reset(new mgx::color_fused_state_t(g.num_nodes, g.num_edges, ctx));
   p->colors = nullptr;
   const std::vector<long long> st = p->fused->run(g.d_row_offsets.data(), g.d_col_indices.data(), seed, max_iter, ctx, p->trace);
   p->colors = p->fused->colour.data();
-  color_stats(stats, st[0], st[1], st[2], st[3]);
+  put_stats(stats, 4, st);
   MGX_CATCH
 }
 int mgx_color_enact(mgx_color_t p, unsigned seed, int max_iter, int64_t* stats) {
   MGX_TRY
-  MGX_REQUIRE(p, "NULL argument");
-  use_device(p->g->c);
-  standard_context_t& ctx = *p->g->c->ctx;
-  graph_device_t& g = *p->g->g;
+  auto [ctx, g] = enter(p);
   if (!p->p) p->p = std::make_shared<coloring::coloring_problem_t>(p->g->g, seed, max_iter, ctx);
   if (!p->e) p->e.reset(new coloring::coloring_enactor_t(ctx, g.num_nodes, g.num_edges));
   p->p->seed = seed;
@@ -2317,22 +2309,20 @@ int mgx_color_enact(mgx_color_t p, unsigned seed, int max_iter, int64_t* stats) 
   ctx.synchronize();
   p->colors = p->p->d_colors.data();
   p->trace = p->e->trace;
-  color_stats(stats, p->e->rounds, p->e->left, p->e->largest, p->e->waits);
+  put_stats(stats, 4, {p->e->rounds, p->e->left, p->e->largest, p->e->waits});
   MGX_CATCH
 }
 int mgx_color_colors(mgx_color_t p, int* host) {
   MGX_TRY
   MGX_REQUIRE(p && host, "NULL argument");
-  MGX_REQUIRE(p->colors, "mgx_color_colors: no run yet");
-  use_device(p->g->c);
-  p->g->c->ctx->synchronize();
-  MGX_HIP(mgx::dtoh(host, p->colors, (size_t)p->g->g->num_nodes));
+  require_run(p->colors, "mgx_color_colors");
+  read_back(p, host, p->colors, p->n());
   MGX_CATCH
 }
 int mgx_color_colors_device(mgx_color_t p, const int** out) {
   MGX_TRY
   MGX_REQUIRE(p && out, "NULL argument");
-  MGX_REQUIRE(p->colors, "mgx_color_colors_device: no run yet");
+  require_run(p->colors, "mgx_color_colors_device");
   *out = p->colors;
   MGX_CATCH
 }
@@ -2360,52 +2350,31 @@ int mgx_color_info(mgx_color_t p, int64_t* consts4, int64_t* round_triples, int 
 
 
 // ---- local graph sparsification ----------------------------------------------------------------
-int mgx_lspar_create(mgx_graph_t g, mgx_lspar_t* out) {
-  MGX_TRY
-  MGX_REQUIRE(g && out, "NULL argument");
-  auto* h = new mgx_lspar_s();
-  h->g = g;
-  *out = h;
-  MGX_CATCH
-}
-int mgx_lspar_free(mgx_lspar_t p) {
-  MGX_TRY
-  if (p) { use_device(p->g->c); delete p; }
-  MGX_CATCH
-}
+int mgx_lspar_create(mgx_graph_t g, mgx_lspar_t* out) { return create_handle(g, out); }
+int mgx_lspar_free(mgx_lspar_t p) { return free_handle(p); }
 static void lspar_check_params(int k, double e) {
   MGX_REQUIRE(k >= 1 && k <= mgx::LSPAR_K_MAX, "lspar: k must be 1 .. 32");
   MGX_REQUIRE(std::isfinite(e) && e >= 0.0, "lspar: e must be finite and >= 0");
-}
-static void lspar_stats(int64_t* stats, long long kept, long long cut, long long waits) {
-  if (!stats) return;
-  stats[0] = kept;
-  stats[1] = cut;
-  stats[2] = waits;
 }
 int mgx_lspar_run(mgx_lspar_t p, unsigned seed, int k, double e, int64_t* stats) {
   MGX_TRY
   MGX_REQUIRE(p, "NULL argument");
   lspar_check_params(k, e);
-  use_device(p->g->c);
-  standard_context_t& ctx = *p->g->c->ctx;
-  graph_device_t& g = *p->g->g;
+  auto [ctx, g] = enter(p);
   if (!p->fused) p->fused.reset(new mgx::lspar_fused_state_t(g.num_nodes, g.num_edges, ctx));
   p->ro = nullptr;
   const std::vector<long long> st = p->fused->run(g.d_row_offsets.data(), g.d_col_indices.data(), seed, k, e, ctx);
   mgx::lspar_fused_state_t& f = *p->fused;
   p->ro = f.oro.data(); p->ci = f.oci.data(); p->eid = f.oeid.data(); p->sim = f.osim.data();
   p->mh = f.mh.data(); p->mh_stride = f.S; p->k = k; p->kept = st[0];
-  lspar_stats(stats, st[0], st[1], st[2]);
+  put_stats(stats, 3, st);
   MGX_CATCH
 }
 int mgx_lspar_enact(mgx_lspar_t p, unsigned seed, int k, double e, int64_t* stats) {
   MGX_TRY
   MGX_REQUIRE(p, "NULL argument");
   lspar_check_params(k, e);
-  use_device(p->g->c);
-  standard_context_t& ctx = *p->g->c->ctx;
-  graph_device_t& g = *p->g->g;
+  auto [ctx, g] = enter(p);
   if (!p->p) p->p = std::make_shared<lspar::lspar_problem_t>(p->g->g, seed, k, e, ctx);
   else p->p->reset(seed, k, e, ctx);
   if (!p->e) p->e.reset(new lspar::lspar_enactor_t(ctx, g.num_nodes, g.num_edges));
@@ -2415,17 +2384,16 @@ int mgx_lspar_enact(mgx_lspar_t p, unsigned seed, int k, double e, int64_t* stat
   lspar::lspar_enactor_t& E = *p->e;
   p->ro = E.d_out_ro.data(); p->ci = E.d_out_ci.data(); p->eid = E.d_out_eid.data(); p->sim = E.d_out_sim.data();
   p->mh = p->p->d_minwise_hashs.data(); p->mh_stride = k; p->k = k; p->kept = E.kept;
-  lspar_stats(stats, E.kept, E.cut, E.waits);
+  put_stats(stats, 3, {E.kept, E.cut, E.waits});
   MGX_CATCH
 }
 int mgx_lspar_result(mgx_lspar_t p, int* h_ro, int* h_ci, int* h_eid, int* h_sim) {
   MGX_TRY
   MGX_REQUIRE(p, "NULL argument");
-  MGX_REQUIRE(p->ro, "mgx_lspar_result: no run yet");
-  use_device(p->g->c);
-  p->g->c->ctx->synchronize();
-  const size_t n = (size_t)p->g->g->num_nodes, m = (size_t)p->kept;
-  if (h_ro) MGX_HIP(mgx::dtoh(h_ro, p->ro, n + 1));
+  require_run(p->ro, "mgx_lspar_result");
+  enter(p).ctx.synchronize();
+  const size_t m = (size_t)p->kept;
+  if (h_ro) MGX_HIP(mgx::dtoh(h_ro, p->ro, p->n() + 1));
   if (m) {
     if (h_ci) MGX_HIP(mgx::dtoh(h_ci, p->ci, m));
     if (h_eid) MGX_HIP(mgx::dtoh(h_eid, p->eid, m));
@@ -2436,7 +2404,7 @@ int mgx_lspar_result(mgx_lspar_t p, int* h_ro, int* h_ci, int* h_eid, int* h_sim
 int mgx_lspar_result_device(mgx_lspar_t p, const int** d_ro, const int** d_ci, const int** d_eid, const int** d_sim) {
   MGX_TRY
   MGX_REQUIRE(p, "NULL argument");
-  MGX_REQUIRE(p->ro, "mgx_lspar_result_device: no run yet");
+  require_run(p->ro, "mgx_lspar_result_device");
   if (d_ro) *d_ro = p->ro;
   if (d_ci) *d_ci = p->ci;
   if (d_eid) *d_eid = p->eid;
@@ -2446,10 +2414,9 @@ int mgx_lspar_result_device(mgx_lspar_t p, const int** d_ro, const int** d_ci, c
 int mgx_lspar_minhashes(mgx_lspar_t p, unsigned* h) {
   MGX_TRY
   MGX_REQUIRE(p && h, "NULL argument");
-  MGX_REQUIRE(p->ro, "mgx_lspar_minhashes: no run yet");
-  use_device(p->g->c);
-  p->g->c->ctx->synchronize();
-  const size_t n = (size_t)p->g->g->num_nodes;
+  require_run(p->ro, "mgx_lspar_minhashes");
+  enter(p).ctx.synchronize();
+  const size_t n = p->n();
   if (n)
     MGX_HIP(hipMemcpy2D(h, (size_t)p->k * sizeof(unsigned), p->mh, (size_t)p->mh_stride * sizeof(unsigned), (size_t)p->k * sizeof(unsigned),
                         n, hipMemcpyDeviceToHost));
@@ -2469,7 +2436,7 @@ int mgx_lspar_info(mgx_lspar_t p, int64_t* out) {
 int mgx_lspar_graph(mgx_lspar_t p, mgx_graph_t* out) {
   MGX_TRY
   MGX_REQUIRE(p && out, "NULL argument");
-  MGX_REQUIRE(p->ro, "mgx_lspar_graph: no run yet");
+  require_run(p->ro, "mgx_lspar_graph");
   mgx_ctx_s* const c = p->g->c;
   use_device(c);
   standard_context_t& ctx = *c->ctx;
@@ -2526,48 +2493,23 @@ int mgx_segmented_sort_i32(mgx_ctx_t c, int* d_keys, int* d_vals, int64_t count,
 
 
 // ---- connected components ----------------------------------------------------------------------
-int mgx_cc_create(mgx_graph_t g, mgx_cc_t* out) {
-  MGX_TRY
-  MGX_REQUIRE(g && out, "NULL argument");
-  auto* h = new mgx_cc_s();
-  h->g = g;
-  *out = h;
-  MGX_CATCH
-}
-int mgx_cc_free(mgx_cc_t p) {
-  MGX_TRY
-  if (p) { use_device(p->g->c); delete p; }
-  MGX_CATCH
-}
-static void cc_stats(int64_t* stats, const std::vector<long long>& s, long long skipped, long long waits) {
-  if (!stats) return;
-  stats[0] = s[0];
-  stats[1] = s[1];
-  stats[2] = s[2];
-  stats[3] = skipped;
-  stats[4] = waits;
-}
+int mgx_cc_create(mgx_graph_t g, mgx_cc_t* out) { return create_handle(g, out); }
+int mgx_cc_free(mgx_cc_t p) { return free_handle(p); }
 int mgx_cc_run(mgx_cc_t p, int symmetric, unsigned seed, int64_t* stats) {
   MGX_TRY
-  MGX_REQUIRE(p, "NULL argument");
-  use_device(p->g->c);
-  standard_context_t& ctx = *p->g->c->ctx;
-  graph_device_t& g = *p->g->g;
+  auto [ctx, g] = enter(p);
   if (!p->fused) p->fused.reset(new mgx::cc_fused_state_t(g.num_nodes, g.num_edges, ctx));
   p->labels = nullptr;
   const bool csc = !g.csc_is_csr;
   const std::vector<long long> st = p->fused->run(g.d_row_offsets.data(), g.d_col_indices.data(), csc ? g.d_col_offsets.data() : nullptr,
                                                   csc ? g.d_row_indices.data() : nullptr, symmetric != 0, seed, ctx);
   p->labels = p->fused->comp.data();
-  cc_stats(stats, st, st[3], st[4]);
+  put_stats(stats, 5, st);
   MGX_CATCH
 }
 int mgx_cc_enact(mgx_cc_t p, int64_t* stats) {
   MGX_TRY
-  MGX_REQUIRE(p, "NULL argument");
-  use_device(p->g->c);
-  standard_context_t& ctx = *p->g->c->ctx;
-  graph_device_t& g = *p->g->g;
+  auto [ctx, g] = enter(p);
   if (!p->p) p->p = std::make_shared<cc::cc_problem_t>(p->g->g, ctx);
   if (!p->e) p->e.reset(new cc::cc_enactor_t(ctx, g.num_nodes, g.num_edges));
   if (!p->label_stats) p->label_stats.reset(new mgx::cc_label_stats_t(g.num_nodes, ctx));
@@ -2575,68 +2517,45 @@ int mgx_cc_enact(mgx_cc_t p, int64_t* stats) {
   p->e->enact(p->p, ctx);
   const std::vector<long long> st = p->label_stats->run(p->p->d_comp.data(), g.num_nodes, ctx);
   p->labels = p->p->d_comp.data();
-  cc_stats(stats, st, 0, p->e->waits + 1);
+  put_stats(stats, 5, {st[0], st[1], st[2], 0, p->e->waits + 1});
   MGX_CATCH
 }
 int mgx_cc_labels(mgx_cc_t p, int* host) {
   MGX_TRY
   MGX_REQUIRE(p && host, "NULL argument");
-  MGX_REQUIRE(p->labels, "mgx_cc_labels: no run yet");
-  use_device(p->g->c);
-  p->g->c->ctx->synchronize();
-  MGX_HIP(mgx::dtoh(host, p->labels, (size_t)p->g->g->num_nodes));
+  require_run(p->labels, "mgx_cc_labels");
+  read_back(p, host, p->labels, p->n());
   MGX_CATCH
 }
 int mgx_cc_labels_device(mgx_cc_t p, const int** out) {
   MGX_TRY
   MGX_REQUIRE(p && out, "NULL argument");
-  MGX_REQUIRE(p->labels, "mgx_cc_labels_device: no run yet");
+  require_run(p->labels, "mgx_cc_labels_device");
   *out = p->labels;
   MGX_CATCH
 }
 
 // ---- triangle counting -------------------------------------------------------------
-int mgx_tc_create(mgx_graph_t g, mgx_tc_t* out) {
-  MGX_TRY
-  MGX_REQUIRE(g && out, "NULL argument");
-  auto* h = new mgx_tc_s();
-  h->g = g;
-  *out = h;
-  MGX_CATCH
-}
-int mgx_tc_free(mgx_tc_t p) {
-  MGX_TRY
-  if (p) { use_device(p->g->c); p->g->c->ctx->synchronize(); delete p; }
-  MGX_CATCH
-}
-static void tc_stats(int64_t* stats, const std::vector<long long>& s) {
-  if (stats) for (int i = 0; i < 8; ++i) stats[i] = s[i];
-}
+int mgx_tc_create(mgx_graph_t g, mgx_tc_t* out) { return create_handle(g, out); }
+int mgx_tc_free(mgx_tc_t p) { return free_handle(p); }
 static mgx::tc_state_t& tc_state(mgx_tc_t p) {
-  graph_device_t& g = *p->g->g;
-  if (!p->st) p->st.reset(new mgx::tc_state_t(g.num_nodes, g.num_edges, *p->g->c->ctx));
+  if (!p->st) p->st.reset(new mgx::tc_state_t(p->graph().num_nodes, p->graph().num_edges, p->ctx()));
   return *p->st;
 }
 int mgx_tc_run(mgx_tc_t p, int symmetric, int64_t* stats) {
   MGX_TRY
-  MGX_REQUIRE(p, "NULL argument");
-  use_device(p->g->c);
-  standard_context_t& ctx = *p->g->c->ctx;
-  graph_device_t& g = *p->g->g;
-  tc_stats(stats, tc_state(p).run(g.d_row_offsets.data(), g.d_col_indices.data(), symmetric != 0, ctx));
+  auto [ctx, g] = enter(p);
+  put_stats(stats, 8, tc_state(p).run(g.d_row_offsets.data(), g.d_col_indices.data(), symmetric != 0, ctx));
   MGX_CATCH
 }
 int mgx_tc_enact(mgx_tc_t p, int symmetric, int64_t* stats) {
   MGX_TRY
-  MGX_REQUIRE(p, "NULL argument");
-  use_device(p->g->c);
-  standard_context_t& ctx = *p->g->c->ctx;
-  graph_device_t& g = *p->g->g;
+  auto [ctx, g] = enter(p);
   mgx::tc_state_t& st = tc_state(p);
   const int sym = symmetric != 0 ? 1 : 0;
   st.launches = st.waits = 0;
   st.last = -1;
-  if (st.n <= 0) { tc_stats(stats, {0, 0, 0, 0, sym, 0, 0, 0}); return MGX_OK; }
+  if (st.n <= 0) { put_stats(stats, 8, {0, 0, 0, 0, sym, 0, 0, 0}); return MGX_OK; }
   mgx::tc_dag_t& d = st.dag[sym];
   bool built_now = false;
   {
@@ -2663,19 +2582,18 @@ int mgx_tc_enact(mgx_tc_t p, int symmetric, int64_t* stats) {
   st.launches += 2 + (mgx::scan_num_tiles(st.n) <= mgx::SCAN_LOOKBACK_MAX_TILES ? 1 : 3) + 1 + 1;
   st.read_stats(d, false, ctx);
   st.last = sym;
-  tc_stats(stats, st.result(d, d.h[mgx::TC_S_TOTAL] / 3, built_now));
+  put_stats(stats, 8, st.result(d, d.h[mgx::TC_S_TOTAL] / 3, built_now));
   MGX_CATCH
 }
 static mgx::tc_dag_t& tc_last(mgx_tc_t p, const char* who) {
-  MGX_REQUIRE(p->st && p->st->last >= 0, std::string(who) + ": no run yet");
+  require_run(p->st && p->st->last >= 0, who);
   return p->st->dag[p->st->last];
 }
 int mgx_tc_triangles(mgx_tc_t p, int64_t* host) {
   MGX_TRY
   MGX_REQUIRE(p && host, "NULL argument");
   tc_last(p, "mgx_tc_triangles");
-  use_device(p->g->c);
-  MGX_HIP(mgx::dtoh((mgx::u64*)host, (const mgx::u64*)p->st->tri.data(), (size_t)p->st->n));
+  read_back(p, (mgx::u64*)host, (const mgx::u64*)p->st->tri.data(), (size_t)p->st->n);
   MGX_CATCH
 }
 int mgx_tc_triangles_device(mgx_tc_t p, const int64_t** out) {
@@ -2688,9 +2606,7 @@ int mgx_tc_triangles_device(mgx_tc_t p, const int64_t** out) {
 int mgx_tc_simple_degrees(mgx_tc_t p, int* host) {
   MGX_TRY
   MGX_REQUIRE(p && host, "NULL argument");
-  mgx::tc_dag_t& d = tc_last(p, "mgx_tc_simple_degrees");
-  use_device(p->g->c);
-  MGX_HIP(mgx::dtoh(host, (const int*)d.sdeg.data(), (size_t)p->st->n));
+  read_back(p, host, (const int*)tc_last(p, "mgx_tc_simple_degrees").sdeg.data(), (size_t)p->st->n);
   MGX_CATCH
 }
 int mgx_tc_simple_degrees_device(mgx_tc_t p, const int** out) {
@@ -2703,35 +2619,21 @@ int mgx_tc_bins(mgx_tc_t p, int64_t* out) {
   MGX_TRY
   MGX_REQUIRE(p && out, "NULL argument");
   tc_last(p, "mgx_tc_bins");
-  use_device(p->g->c);
-  const std::vector<long long> b = p->st->bins(*p->g->c->ctx);
-  for (int i = 0; i < 7; ++i) out[i] = b[i];
+  put_stats(out, 7, p->st->bins(enter(p).ctx));
   MGX_CATCH
 }
 int mgx_tc_dag(mgx_tc_t p, int* h_ro, int* h_ci) {
   MGX_TRY
   MGX_REQUIRE(p && h_ro, "NULL argument");
   mgx::tc_dag_t& d = tc_last(p, "mgx_tc_dag");
-  use_device(p->g->c);
-  MGX_HIP(mgx::dtoh(h_ro, (const int*)d.ro.data(), (size_t)p->st->n + 1));
-  if (h_ci) MGX_HIP(mgx::dtoh(h_ci, (const int*)d.ci.data(), (size_t)d.h[mgx::TC_S_MDAG]));
+  read_back(p, h_ro, (const int*)d.ro.data(), (size_t)p->st->n + 1);
+  if (h_ci) read_back(p, h_ci, (const int*)d.ci.data(), (size_t)d.h[mgx::TC_S_MDAG]);
   MGX_CATCH
 }
 
 // ---- betweenness centrality --------------------------------------------------------
-int mgx_bc_create(mgx_graph_t g, mgx_bc_t* out) {
-  MGX_TRY
-  MGX_REQUIRE(g && out, "NULL argument");
-  auto* h = new mgx_bc_s();
-  h->g = g;
-  *out = h;
-  MGX_CATCH
-}
-int mgx_bc_free(mgx_bc_t p) {
-  MGX_TRY
-  if (p) { use_device(p->g->c); p->g->c->ctx->synchronize(); delete p; }
-  MGX_CATCH
-}
+int mgx_bc_create(mgx_graph_t g, mgx_bc_t* out) { return create_handle(g, out); }
+int mgx_bc_free(mgx_bc_t p) { return free_handle(p); }
 // the checks both paths make before any device work; the sources as a list
 static std::vector<int> bc_sources(mgx_bc_t p, const int* sources, int count, const char* who) {
   MGX_REQUIRE(p, "NULL argument");
@@ -2748,23 +2650,19 @@ static std::vector<int> bc_sources(mgx_bc_t p, const int* sources, int count, co
   return s;
 }
 static mgx::bc_state_t& bc_state(mgx_bc_t p) {
-  standard_context_t& ctx = *p->g->c->ctx;
-  if (!p->st) p->st.reset(new mgx::bc_state_t(p->g->g->num_nodes, ctx));
-  if (!p->bp) p->bp = std::make_shared<bfs::bfs_problem_t>(p->g->g, 0, ctx);
+  if (!p->st) p->st.reset(new mgx::bc_state_t(p->graph().num_nodes, p->ctx()));
+  if (!p->bp) p->bp = std::make_shared<bfs::bfs_problem_t>(p->g->g, 0, p->ctx());
   return *p->st;
 }
 static void bc_stats(int64_t* stats, const mgx::bc_state_t& st, const mgx::bc_ctrl_t& c, long long traversal_waits) {
-  if (!stats) return;
-  stats[0] = st.sources; stats[1] = c.deepest; stats[2] = st.reached; stats[3] = c.inexact ? 1 : 0; stats[4] = c.overflow ? 1 : 0;
-  stats[5] = st.waits; stats[6] = traversal_waits; stats[7] = st.launches; stats[8] = st.chain_launches; stats[9] = st.used_csc;
+  put_stats(stats, 10, {st.sources, c.deepest, st.reached, c.inexact ? 1 : 0, c.overflow ? 1 : 0, st.waits, traversal_waits, st.launches,
+                    st.chain_launches, st.used_csc});
 }
 int mgx_bc_run(mgx_bc_t p, const int* sources, int count, int symmetric, int64_t* stats) {
   MGX_TRY
   const std::vector<int> srcs = bc_sources(p, sources, count, "mgx_bc_run");
   MGX_REQUIRE(symmetric || !p->g->g->csc_is_csr, "mgx_bc_run: symmetric = 0 needs the graph's genuine CSC (mgx_graph_build_csc)");
-  use_device(p->g->c);
-  standard_context_t& ctx = *p->g->c->ctx;
-  graph_device_t& G = *p->g->g;
+  auto [ctx, G] = enter(p);
   mgx::bc_state_t& st = bc_state(p);
   const bool sym = symmetric != 0;
   st.ensure_rows(sym, G.d_row_offsets.data(), G.d_col_indices.data(), G.d_col_offsets.data(), G.d_row_indices.data(), ctx);
@@ -2804,9 +2702,7 @@ int mgx_bc_enact(mgx_bc_t p, const int* sources, int count, int symmetric, int64
   MGX_TRY
   const std::vector<int> srcs = bc_sources(p, sources, count, "mgx_bc_enact");
   (void)symmetric;                                                 // (the operator path reads the out-entries alone)
-  use_device(p->g->c);
-  standard_context_t& ctx = *p->g->c->ctx;
-  graph_device_t& G = *p->g->g;
+  auto [ctx, G] = enter(p);
   mgx::bc_state_t& st = bc_state(p);
   const int n = G.num_nodes;
   if (!p->p) p->p = std::make_shared<bc::bc_problem_t>(p->g->g, p->bp->d_labels.data(), st.sigma.data(), const_cast<double*>(st.delta()), ctx);
@@ -2845,15 +2741,14 @@ int mgx_bc_enact(mgx_bc_t p, const int* sources, int count, int symmetric, int64
   MGX_CATCH
 }
 static mgx::bc_state_t& bc_last(mgx_bc_t p, const char* who) {
-  MGX_REQUIRE(p->st && p->st->ran, std::string(who) + ": no run yet");
+  require_run(p->st && p->st->ran, who);
   return *p->st;
 }
 int mgx_bc_centrality(mgx_bc_t p, double* host) {
   MGX_TRY
   MGX_REQUIRE(p && host, "NULL argument");
   mgx::bc_state_t& st = bc_last(p, "mgx_bc_centrality");
-  use_device(p->g->c);
-  MGX_HIP(mgx::dtoh(host, (const double*)st.bc.data(), (size_t)st.n));
+  read_back(p, host, (const double*)st.bc.data(), (size_t)st.n);
   MGX_CATCH
 }
 int mgx_bc_centrality_device(mgx_bc_t p, const double** out) {
@@ -2866,30 +2761,26 @@ int mgx_bc_sigma(mgx_bc_t p, double* host) {
   MGX_TRY
   MGX_REQUIRE(p && host, "NULL argument");
   mgx::bc_state_t& st = bc_last(p, "mgx_bc_sigma");
-  use_device(p->g->c);
-  MGX_HIP(mgx::dtoh(host, (const double*)st.sigma.data(), (size_t)st.n));
+  read_back(p, host, (const double*)st.sigma.data(), (size_t)st.n);
   MGX_CATCH
 }
 int mgx_bc_delta(mgx_bc_t p, double* host) {
   MGX_TRY
   MGX_REQUIRE(p && host, "NULL argument");
   mgx::bc_state_t& st = bc_last(p, "mgx_bc_delta");
-  use_device(p->g->c);
-  MGX_HIP(mgx::dtoh(host, st.delta(), (size_t)st.n));
+  read_back(p, host, (const double*)st.delta(), (size_t)st.n);
   MGX_CATCH
 }
 int mgx_bc_labels(mgx_bc_t p, int* host) {
   MGX_TRY
   MGX_REQUIRE(p && host, "NULL argument");
   mgx::bc_state_t& st = bc_last(p, "mgx_bc_labels");
-  use_device(p->g->c);
-  MGX_HIP(mgx::dtoh(host, (const int*)p->bp->d_labels.data(), (size_t)st.n));
+  read_back(p, host, (const int*)p->bp->d_labels.data(), (size_t)st.n);
   MGX_CATCH
 }
 int mgx_bc_set_timing(mgx_bc_t p, int on) {
   MGX_TRY
-  MGX_REQUIRE(p, "NULL argument");
-  use_device(p->g->c);
+  enter(p);
   bc_state(p).timing = on != 0;
   MGX_CATCH
 }
@@ -2919,19 +2810,8 @@ int mgx_bc_info(mgx_bc_t p, int64_t* out) {
 }
 
 // ---- PageRank to convergence --------------------------------------------------------
-int mgx_pagerank_create(mgx_graph_t g, mgx_pagerank_t* out) {
-  MGX_TRY
-  MGX_REQUIRE(g && out, "NULL argument");
-  auto* h = new mgx_pagerank_s();
-  h->g = g;
-  *out = h;
-  MGX_CATCH
-}
-int mgx_pagerank_free(mgx_pagerank_t p) {
-  MGX_TRY
-  if (p) { use_device(p->g->c); delete p; }
-  MGX_CATCH
-}
+int mgx_pagerank_create(mgx_graph_t g, mgx_pagerank_t* out) { return create_handle(g, out); }
+int mgx_pagerank_free(mgx_pagerank_t p) { return free_handle(p); }
 // the arguments both paths refuse before any device work
 static void pagerank_check(mgx_pagerank_t p, double alpha, double tol, int max_iter, int symmetric, const char* who) {
   MGX_REQUIRE(p, "NULL argument");
@@ -2943,48 +2823,13 @@ static void pagerank_check(mgx_pagerank_t p, double alpha, double tol, int max_i
                                  "pass symmetric = 1 only if every entry has its reverse");
 }
 static void pagerank_stats(int64_t* stats, double* residual, const mgx::pagerank_stats_t& s) {
-  if (stats) {
-    stats[0] = s.iterations; stats[1] = s.converged; stats[2] = s.dangling; stats[3] = s.layout_path; stats[4] = s.waits; stats[5] = s.launches;
-  }
+  put_stats(stats, 6, {s.iterations, s.converged, s.dangling, s.layout_path, s.waits, s.launches});
   if (residual) *residual = s.residual;
-}
-// the layout reduce's view of the graph (the conditions of neighborhood.hxx:59-62, 91-92); false: the general reduce serves
-static bool pagerank_layout(mgx_graph_s* g, mgx::nr_layout_t& L) {
-  graph_device_t& G = *g->g;
-  if (!G.has_layout || G.num_edges <= 0) return false;
-  ensure_nr_slices(g);
-  standard_context_t& ctx = *g->c->ctx;
-  if (!(G.rows.ub.units > 0 && G.rows.ub_min_degree == G.rows.vs_long_min && G.rows.vs_long_min >= 17 && G.rows.vs_long_min <= 64 &&
-        G.rows.ub.cnt.size() && G.rows.ub.first.size() && G.rows.vs_dummy != 0)) return false;
-  if (!(G.nrs_units > 0 && G.nrs_slices > 0 && G.nrs_rows == G.rows.vs_v[0] && G.d_nrs_mu.size() && G.d_nrs_off.size() &&
-        ctx.scratch_bytes >= mgx::nr_scratch_bytes(G.num_nodes, G.nrs_units, sizeof(float)))) return false;
-  L = mgx::nr_layout_t();
-  L.new_of_old = G.d_new_of_old.data();
-  L.row_offsets = (const mgx::u32*)G.d_layout_row_offsets.data();
-  L.col_indices = G.d_layout_col_indices.data();
-  L.old_of_new = G.d_old_of_new.data();
-  L.ub_col = G.rows.ub.col.size() ? G.rows.ub.col.data() : nullptr;
-  L.ub_col24 = G.rows.ub.col24.size() ? G.rows.ub.col24.data() : nullptr;
-  L.ub_cnt = G.rows.ub.cnt.data();
-  L.ub_first = G.rows.ub.first.data();
-  L.ub_units = (mgx::u32)G.rows.ub.units; L.ub_units_pad = (mgx::u32)G.rows.ub.units_pad;
-  for (int i = 0; i < 4; ++i) L.vs_v[i] = G.rows.vs_v[i];
-  L.vs_dummy = G.rows.vs_dummy;
-  L.big_rows = G.nr_big_rows;
-  L.n = G.num_nodes;
-  L.nrs_mu = (const uint4*)G.d_nrs_mu.data();
-  L.nrs_off = G.d_nrs_off.data();
-  for (int i = 0; i < mgx::NRS_MAX_SLICES + 2; ++i) L.nrs_first[i] = G.nrs_first[i];
-  L.nrs_slices = G.nrs_slices; L.nrs_rows = G.nrs_rows;
-  for (int i = 0; i < 3; ++i) L.nrs_tier[i] = G.nrs_tier[i];
-  return true;
 }
 int mgx_pagerank_run(mgx_pagerank_t p, double alpha, double tol, int max_iter, int symmetric, int64_t* stats, double* residual) {
   MGX_TRY
   pagerank_check(p, alpha, tol, max_iter, symmetric, "mgx_pagerank_run");
-  use_device(p->g->c);
-  standard_context_t& ctx = *p->g->c->ctx;
-  graph_device_t& G = *p->g->g;
+  auto [ctx, G] = enter(p);
   if (!p->p) p->p = std::make_shared<pagerank::pagerank_problem_t>(p->g->g, ctx);
   mgx::pagerank_graph_t pg;
   mgx::nr_layout_t L;
@@ -2992,9 +2837,14 @@ int mgx_pagerank_run(mgx_pagerank_t p, double alpha, double tol, int max_iter, i
   pg.in_off = symmetric ? G.d_row_offsets.data() : G.d_col_offsets.data();
   pg.in_idx = symmetric ? G.d_col_indices.data() : G.d_row_indices.data();
   pg.in_entries = G.num_edges;
-  if (symmetric && pagerank_layout(p->g, L)) {
-    pg.layout = &L;
-    pg.old_of_new = G.d_old_of_new.data();
+  // the layout reduce only with the long rows by slice (and 4-byte values); otherwise the general reduce serves
+  if (symmetric && G.has_layout && G.num_edges > 0) {
+    ensure_nr_slices(p->g);
+    if (mgx::nr_units_valid(G)) L = mgx::nr_layout_of(G, ctx, sizeof(float), true);
+    if (L.nrs_mu) {
+      pg.layout = &L;
+      pg.old_of_new = G.d_old_of_new.data();
+    }
   }
   pagerank_stats(stats, residual, p->p->state.run(pg, alpha, tol, max_iter, ctx));
   MGX_CATCH
@@ -3002,9 +2852,7 @@ int mgx_pagerank_run(mgx_pagerank_t p, double alpha, double tol, int max_iter, i
 int mgx_pagerank_enact(mgx_pagerank_t p, double alpha, double tol, int max_iter, int symmetric, int64_t* stats, double* residual) {
   MGX_TRY
   pagerank_check(p, alpha, tol, max_iter, symmetric, "mgx_pagerank_enact");
-  use_device(p->g->c);
-  standard_context_t& ctx = *p->g->c->ctx;
-  graph_device_t& G = *p->g->g;
+  auto [ctx, G] = enter(p);
   if (!p->p) p->p = std::make_shared<pagerank::pagerank_problem_t>(p->g->g, ctx);
   if (!p->e) p->e.reset(new pagerank::pagerank_enactor_t(ctx, G.num_nodes, G.num_edges));
   if (G.has_layout && G.csc_is_csr) ensure_nr_slices(p->g);      // (the operator's full-frontier reduce may take them)
@@ -3014,53 +2862,34 @@ int mgx_pagerank_enact(mgx_pagerank_t p, double alpha, double tol, int max_iter,
 int mgx_pagerank_ranks(mgx_pagerank_t p, float* host) {
   MGX_TRY
   MGX_REQUIRE(p && host, "NULL argument");
-  MGX_REQUIRE(p->p && p->p->state.result, "mgx_pagerank_ranks: no run yet");
-  use_device(p->g->c);
-  p->g->c->ctx->synchronize();
-  MGX_HIP(mgx::dtoh(host, p->p->state.result, (size_t)p->g->g->num_nodes));
+  require_run(p->p && p->p->state.result, "mgx_pagerank_ranks");
+  read_back(p, host, (const float*)p->p->state.result, p->n());
   MGX_CATCH
 }
 int mgx_pagerank_ranks_device(mgx_pagerank_t p, const float** out) {
   MGX_TRY
   MGX_REQUIRE(p && out, "NULL argument");
-  MGX_REQUIRE(p->p && p->p->state.result, "mgx_pagerank_ranks_device: no run yet");
+  require_run(p->p && p->p->state.result, "mgx_pagerank_ranks_device");
   *out = p->p->state.result;
   MGX_CATCH
 }
 int mgx_pagerank_residuals(mgx_pagerank_t p, double* host_e, int cap, int* iterations) {
   MGX_TRY
   MGX_REQUIRE(p && cap >= 0 && (host_e || cap == 0), "bad argument");
-  MGX_REQUIRE(p->p && p->p->state.result, "mgx_pagerank_residuals: no run yet");
-  use_device(p->g->c);
+  require_run(p->p && p->p->state.result, "mgx_pagerank_residuals");
   mgx::pagerank_state_t& s = p->p->state;
   if (iterations) *iterations = s.last_iterations;
-  const int k = std::min(std::min(cap, s.last_iterations), s.trace_cap);
-  p->g->c->ctx->synchronize();
-  if (k > 0) MGX_HIP(mgx::dtoh(host_e, (const double*)s.trace.data(), (size_t)k));
+  read_back(p, host_e, (const double*)s.trace.data(), (size_t)std::max(std::min(std::min(cap, s.last_iterations), s.trace_cap), 0));
   MGX_CATCH
 }
 
 
 // ---- minimum spanning forest -----------------------------------------------------------
-int mgx_mst_create(mgx_graph_t g, mgx_mst_t* out) {
-  MGX_TRY
-  MGX_REQUIRE(g && out, "NULL argument");
-  auto* h = new mgx_mst_s();
-  h->g = g;
-  *out = h;
-  MGX_CATCH
-}
-int mgx_mst_free(mgx_mst_t p) {
-  MGX_TRY
-  if (p) { use_device(p->g->c); p->g->c->ctx->synchronize(); delete p; }
-  MGX_CATCH
-}
+int mgx_mst_create(mgx_graph_t g, mgx_mst_t* out) { return create_handle(g, out); }
+int mgx_mst_free(mgx_mst_t p) { return free_handle(p); }
 int mgx_mst_run(mgx_mst_t p, int symmetric, int64_t* stats) {
   MGX_TRY
-  MGX_REQUIRE(p, "NULL argument");
-  use_device(p->g->c);
-  standard_context_t& ctx = *p->g->c->ctx;
-  graph_device_t& g = *p->g->g;
+  auto [ctx, g] = enter(p);
   p->ready = false;
   const bool csc = !g.csc_is_csr;
   MGX_REQUIRE(symmetric || csc, "mgx_mst_run: symmetric == 0 needs the graph's genuine CSC (mgx_graph_build_csc)");
@@ -3074,15 +2903,12 @@ int mgx_mst_run(mgx_mst_t p, int symmetric, int64_t* stats) {
   p->edges = st[0];
   p->total = p->fused->total();
   p->ready = true;
-  if (stats) for (int i = 0; i < 8; ++i) stats[i] = st[i];
+  put_stats(stats, 8, st);
   MGX_CATCH
 }
 int mgx_mst_enact(mgx_mst_t p, int symmetric, int64_t* stats) {
   MGX_TRY
-  MGX_REQUIRE(p, "NULL argument");
-  use_device(p->g->c);
-  standard_context_t& ctx = *p->g->c->ctx;
-  graph_device_t& g = *p->g->g;
+  auto [ctx, g] = enter(p);
   p->ready = false;
   MGX_REQUIRE(symmetric || !g.csc_is_csr, "mgx_mst_enact: symmetric == 0 needs the graph's genuine CSC (mgx_graph_build_csc)");
   MGX_REQUIRE(g.d_col_values.size() >= (size_t)g.num_edges, "mgx_mst_enact: the graph has no weights");
@@ -3090,7 +2916,7 @@ int mgx_mst_enact(mgx_mst_t p, int symmetric, int64_t* stats) {
   if (n <= 0) {
     p->labels = nullptr; p->a = p->b = nullptr; p->w = nullptr; p->edges = 0; p->total = 0.0;
     p->ready = true;
-    if (stats) for (int i = 0; i < 8; ++i) stats[i] = 0;
+    put_stats(stats, 8, {0, 0, 0, 0, 0, 0, 0, 0});
     return MGX_OK;
   }
   if (!p->p) p->p = std::make_shared<mst::mst_problem_t>(p->g->g, ctx);
@@ -3120,18 +2946,14 @@ int mgx_mst_enact(mgx_mst_t p, int symmetric, int64_t* stats) {
   p->edges = (long long)h[mgx::MST_S_EDGES];
   std::memcpy(&p->total, &h[mgx::MST_S_TOTAL], sizeof(double));
   p->ready = true;
-  if (stats) {
-    stats[0] = p->edges; stats[1] = ls[0]; stats[2] = ls[1]; stats[3] = ls[2]; stats[4] = p->e->rounds;
-    stats[5] = waits; stats[6] = 0; stats[7] = (long long)counters[1];
-  }
+  put_stats(stats, 8, {p->edges, ls[0], ls[1], ls[2], p->e->rounds, waits, 0, (long long)counters[1]});
   MGX_CATCH
 }
 int mgx_mst_edges(mgx_mst_t p, int* h_a, int* h_b, float* h_w) {
   MGX_TRY
   MGX_REQUIRE(p, "NULL argument");
-  MGX_REQUIRE(p->ready, "mgx_mst_edges: no run yet");
-  use_device(p->g->c);
-  p->g->c->ctx->synchronize();
+  require_run(p->ready, "mgx_mst_edges");
+  enter(p).ctx.synchronize();
   const size_t k = (size_t)p->edges;
   if (h_a && k) MGX_HIP(mgx::dtoh(h_a, p->a, k));
   if (h_b && k) MGX_HIP(mgx::dtoh(h_b, p->b, k));
@@ -3141,7 +2963,7 @@ int mgx_mst_edges(mgx_mst_t p, int* h_a, int* h_b, float* h_w) {
 int mgx_mst_edges_device(mgx_mst_t p, const int** d_a, const int** d_b, const float** d_w) {
   MGX_TRY
   MGX_REQUIRE(p, "NULL argument");
-  MGX_REQUIRE(p->ready, "mgx_mst_edges_device: no run yet");
+  require_run(p->ready, "mgx_mst_edges_device");
   if (d_a) *d_a = p->a;
   if (d_b) *d_b = p->b;
   if (d_w) *d_w = p->w;
@@ -3150,23 +2972,21 @@ int mgx_mst_edges_device(mgx_mst_t p, const int** d_a, const int** d_b, const fl
 int mgx_mst_weight(mgx_mst_t p, double* total) {
   MGX_TRY
   MGX_REQUIRE(p && total, "NULL argument");
-  MGX_REQUIRE(p->ready, "mgx_mst_weight: no run yet");
+  require_run(p->ready, "mgx_mst_weight");
   *total = p->total;
   MGX_CATCH
 }
 int mgx_mst_labels(mgx_mst_t p, int* host) {
   MGX_TRY
   MGX_REQUIRE(p && host, "NULL argument");
-  MGX_REQUIRE(p->ready, "mgx_mst_labels: no run yet");
-  use_device(p->g->c);
-  p->g->c->ctx->synchronize();
-  if (p->g->g->num_nodes > 0) MGX_HIP(mgx::dtoh(host, p->labels, (size_t)p->g->g->num_nodes));
+  require_run(p->ready, "mgx_mst_labels");
+  read_back(p, host, p->labels, (size_t)std::max(p->graph().num_nodes, 0));
   MGX_CATCH
 }
 int mgx_mst_labels_device(mgx_mst_t p, const int** out) {
   MGX_TRY
   MGX_REQUIRE(p && out, "NULL argument");
-  MGX_REQUIRE(p->ready, "mgx_mst_labels_device: no run yet");
+  require_run(p->ready, "mgx_mst_labels_device");
   *out = p->labels;
   MGX_CATCH
 }
@@ -3174,8 +2994,7 @@ int mgx_mst_info(mgx_mst_t p, int64_t* out) {
   MGX_TRY
   MGX_REQUIRE(p && out, "NULL argument");
   MGX_REQUIRE(p->fused, "mgx_mst_info: no fused run yet");
-  const std::vector<long long> v = p->fused->info();
-  for (int i = 0; i < 8; ++i) out[i] = v[i];
+  put_stats(out, 8, p->fused->info());
   MGX_CATCH
 }
 

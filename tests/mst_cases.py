@@ -122,6 +122,33 @@ def small_components(symmetric, count=10000, seed=10):
     return wcsr(n, s, d, w, symmetric=symmetric) + (symmetric,)
 
 
+def work_list_edges(seg=2048, seed=12):
+    """k_mst_worklist at its edges (include/mgx/mst_fused.hpp; MST_SEG_DEFAULT entries a window, a wave's stage holds 128 rows):
+    three rings of 2049 + 2048 + 2048 = 3 * 2048 + 1 vertices, every one a short row in round one (2 - 4 entries), and four hubs
+    behind them.  Hubs 0 and 1 have exactly seg entries each and hubs 2 and 3 seg + 1; the heaviest entry of each -- the last of
+    its sorted row, for hubs 2 and 3 a window of its own -- is the edge to its partner hub, the only edge between their rings:
+    ring 0 (hubs 0 and 2) -- ring 1 (hub 1), ring 0 -- ring 2 (hub 3).  The forest is a tree only if both edges are found."""
+    rng = np.random.default_rng(seed)
+    sizes = [seg + 1, seg, seg]
+    starts = np.concatenate([[0], np.cumsum(sizes)])
+    hub = int(starts[-1]) + np.arange(4)
+    s, d = [], []
+    for k, sz in enumerate(sizes):
+        v = starts[k] + np.arange(sz)
+        s.append(v)
+        d.append(starts[k] + (np.arange(sz) + 1) % sz)
+    spokes = [(hub[0], 0, seg - 1), (hub[1], 1, seg - 1), (hub[2], 0, seg), (hub[3], 2, seg)]    # (hub, its ring, spokes)
+    for h, k, count in spokes:
+        s.append(np.full(count, h))
+        d.append(starts[k] + np.arange(count))
+    s, d = np.concatenate(s), np.concatenate(d)
+    w = rng.permutation(len(s)).astype(np.float32) + 1.0               # distinct integers: the totals are exact
+    s = np.concatenate([s, [hub[0], hub[2]]])
+    d = np.concatenate([d, [hub[1], hub[3]]])
+    w = np.concatenate([w, [1e6, 2e6]]).astype(np.float32)
+    return wcsr(int(hub[-1]) + 1, s, d, w) + (True,)
+
+
 # name -> builder of the cases both suites run (the R-MAT inputs and the fixtures come from the oracle: see the suites)
 CASES = {
     "no_entries_1": lambda: no_entries(1),
@@ -142,6 +169,7 @@ CASES = {
     "special_weights": special_weights,
     "small_components_symmetric": lambda: small_components(True),
     "small_components_directed": lambda: small_components(False),
+    "work_list_edges": work_list_edges,
 }
 
 RMAT_SYMMETRIC = [(10, 1), (11, 2), (12, 4), (13, 8), (14, 16), (15, 1), (16, 16)]

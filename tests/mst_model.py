@@ -115,7 +115,8 @@ def kruskal(ro, ci, w=None):
 
 
 def boruvka(ro, ci, w=None, symmetric=True):
-    """-> {"edges": (a, b, w) canonical, "total", "labels", "rounds": stats[4], "entries": stats[7]}.  The incident array of v
+    """-> {"edges": (a, b, w) canonical, "total", "labels", "rounds": stats[4], "entries": stats[7], "left": per round that makes
+    a work list (the one that chooses nothing included) every row's entries from its cursor on}.  The incident array of v
     holds its out-entries -- and, symmetric False, its in-entries -- as (key, neighbour) ascending; a cursor per vertex stands
     at its first entry that may still leave its component."""
     n = len(ro) - 1
@@ -133,7 +134,9 @@ def boruvka(ro, ci, w=None, symmetric=True):
     chosen = []
     rounds = 0
     rows = np.nonzero(np.diff(off) > 0)[0]
+    left = []
     while True:
+        left.append(off[1:] - cur)
         leaves = lab[v] != lab[u]
         first = np.full(n, big, dtype=np.int64)
         if len(rows):
@@ -171,7 +174,7 @@ def boruvka(ro, ci, w=None, symmetric=True):
         ea, eb, ka = np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.uint32)
     edges = canonical(ea, eb, weight_of_key(ka))
     return {"edges": edges, "total": float(np.sum(edges[2].astype(np.float64))), "labels": lab.astype(np.int32), "rounds": rounds,
-            "entries": int(len(v))}
+            "entries": int(len(v)), "left": left}
 
 
 def total_bound(w):

@@ -9,6 +9,7 @@ import pytest
 
 from tests import cc_model as model
 from tests import coloring_model as cm
+from tests.grid_cus import one_cu_context
 
 pytestmark = pytest.mark.gpu
 
@@ -108,6 +109,30 @@ def test_star_long_row(gpu_ctx, centre):
     ro, ci = cm.csr(n, np.full(len(leaves), centre), leaves, symmetric=False)   # only the centre's row
     for csc in (False, True):
         _check(gpu_ctx, ro, ci, False, csc=csc)
+
+
+def test_work_list_stage_and_segment_edges(gpu_ctx, torch_mod, monkeypatch):
+    """k_cc_worklist at its edges, on a one-unit context (8 workgroups: a pass covers 2048 vertices): 3 * 2048 + 1 short rows, all
+    listed (directed, no CSC: nothing is skipped), so every wave's stage of 128 goes out inside the loop in its third pass and
+    again behind it; a row of exactly CC_SEG entries left to link whose last one is the only entry into the second group, and a
+    row of CC_SEG + 1 whose last one -- a segment of its own -- is the only entry into the third."""
+    seg, rounds = 2048, 2                                                 # CC_SEG, CC_NEIGHBOR_ROUNDS (include/mgx/cc_fused.hpp)
+    groups = [np.arange(0, 2100), np.arange(2100, 4200), np.arange(4200, 3 * 2048 + 1)]
+    s = np.concatenate([np.repeat(g, 3) for g in groups])
+    d = np.concatenate([g[(np.arange(len(g))[:, None] + [1, 2, 3]) % len(g)].ravel() for g in groups])
+    hub_a, hub_b = 3 * 2048 + 1, 3 * 2048 + 2
+    row_a = np.concatenate([np.arange(rounds + seg - 1), [groups[1][-1]]])      # rows are sorted: the far group's vertex comes last
+    row_b = np.concatenate([np.arange(rounds + seg), [groups[2][-1]]])
+    s = np.concatenate([s, np.full(len(row_a), hub_a), np.full(len(row_b), hub_b)])
+    d = np.concatenate([d, row_a, row_b])
+    n = hub_b + 1
+    ro, ci = cm.csr(n, s, d, symmetric=False)
+    left = np.diff(ro) - rounds
+    assert left[hub_a] == seg and left[hub_b] == seg + 1 and ci[ro[hub_a + 1] - 1] == 4199 and ci[ro[hub_b + 1] - 1] == 3 * 2048
+    assert ((left[:hub_a] >= 1) & (left[:hub_a] < 32)).all()              # CC_LONG_MIN
+    with one_cu_context(monkeypatch, torch_mod) as one_cu:
+        for ctx in (one_cu, gpu_ctx):
+            assert (_check(ctx, ro, ci, False) == 0).all()
 
 
 def test_shuffled_path(gpu_ctx):

@@ -54,6 +54,28 @@ def test_case_runs_the_planned_launches(gpu_ctx, name):
     g.close()
 
 
+def test_candidate_stage_on_one_unit(gpu_ctx, torch_mod, monkeypatch):
+    """4096 disjoint paths a - b - c.  Level 2's front is the 8192 ends, short rows all (8192 entries: an EXPAND of the device);
+    every b is decremented twice and becomes a candidate once.  On a one-unit context the step is 4 workgroups -- 16 waves, which
+    share the 4096 candidates, so one of them at least holds 256: its stage of 128 goes out inside the loop and again behind it
+    (on the session context no wave sees more than 64 rows).  The candidates are then stranded at degree 0."""
+    import mini_amd
+    from tests.grid_cus import one_cu_context
+    paths = 4096
+    a, b, c = np.arange(paths), paths + np.arange(paths), 2 * paths + np.arange(paths)
+    ro, ci = cases._symmetric(3 * paths, np.concatenate([a, b]), np.concatenate([b, c]))
+    plan = model.launch_plan(ro, ci)
+    assert plan.kinds[:4] == [model.MIN, model.LIST, model.EXPAND, model.FILTER] and plan.stats["stranded"] == paths
+    with one_cu_context(monkeypatch, torch_mod) as one_cu:
+        for ctx in (one_cu, gpu_ctx):
+            g = _graph(ctx, ro, ci)
+            kc = mini_amd.KcoreProblem(g)
+            largest, st = kc.run()
+            check_run(kc, largest, st, plan)
+            kc.close()
+            g.close()
+
+
 def _uniform16(ctx, oracle):
     from mini_amd import rmat
     d = rmat.uniform_csr(ctx, 16, 16)

@@ -13,6 +13,7 @@ import pytest
 from tests import cc_model
 from tests import mst_cases as cases
 from tests import mst_model as model
+from tests.grid_cus import one_cu_context
 
 pytestmark = pytest.mark.gpu
 
@@ -133,6 +134,25 @@ def test_hand_made_cases(gpu_ctx, name):
         assert (1, 4, 2.0) in set(zip(a.tolist(), b.tolist(), x.tolist()))
     if name.startswith("small_components"):
         assert sf["components"] == 10000
+
+
+def test_work_list_edges_on_one_unit(gpu_ctx, torch_mod, monkeypatch):
+    """cases.work_list_edges where a pass of k_mst_worklist covers 2048 vertices (8 workgroups): every wave's stage goes out inside
+    the loop in its third pass and again behind it; the hubs' rows are one window of exactly MST_SEG entries and two windows, the
+    second of one entry (test_hand_made_cases runs the same graph on the session context)"""
+    ro, ci, w, symmetric = cases.work_list_edges()
+    d = np.diff(ro)
+    assert sorted(d[-4:].tolist()) == [2048, 2048, 2049, 2049] and ((d[:-4] >= 1) & (d[:-4] < 64)).all() and len(d) - 4 == 3 * 2048 + 1
+    left = model.boruvka(ro, ci, w)["left"]
+    assert sorted(left[0][-4:].tolist()) == [2048, 2048, 2049, 2049] and sorted(left[1][-4:].tolist()) == [2048, 2048, 2049, 2049]
+    with one_cu_context(monkeypatch, torch_mod) as one_cu:
+        for ctx in (one_cu, gpu_ctx):
+            sf, info = _check(ctx, ro, ci, w, symmetric)
+            assert info["long_min"] == 64 and info["seg"] == 2048
+            assert sf["edges"] == len(d) - 1 and sf["components"] == 1
+            # the work lists of all rounds: a short row an item, a long one an item per window of what is left of it
+            assert info["short_items"] == sum(int(((x > 0) & (x < 64)).sum()) for x in left), info
+            assert info["long_items"] == sum(int(((x[x >= 64] + 2047) // 2048).sum()) for x in left), info
 
 
 def test_nan_is_invalid(gpu_ctx):

@@ -10,6 +10,7 @@ import pytest
 
 from tests import coloring_model as cm
 from tests import tc_model as model
+from tests.grid_cus import one_cu_context
 
 pytestmark = pytest.mark.gpu
 
@@ -133,6 +134,26 @@ def test_tripled_pairs_and_self_loops_equal_the_simple_graph(gpu_ctx):
         w = _check(gpu_ctx, ro, ci, symmetric)
         assert w["stats"]["triangles"] == simple["stats"]["triangles"] > 0
         assert np.array_equal(w["tri"], simple["tri"]) and np.array_equal(w["sdeg"], simple["sdeg"])
+
+
+def test_work_list_stages_on_one_unit(gpu_ctx, torch_mod, monkeypatch):
+    """k_tc_worklist where a pass covers 2048 vertices (a one-unit context: 8 workgroups): a band graph (v -- v + 1, v + 2) of
+    3 * 2048 + 5 vertices, all but two of them rows of two oriented entries, so every wave's stage of 128 short rows goes out inside
+    the loop in its third pass and again behind it; and the same with all of them in the second and in the third list."""
+    n = 3 * 2048 + 5
+    v = np.arange(n)
+    ro, ci = cm.csr(n, np.concatenate([v[:-1], v[:-2]]), np.concatenate([v[:-1] + 1, v[:-2] + 2]))
+    want = model.count(ro, ci, True)
+    d = np.diff(want["dag_ro"])
+    assert ((d[:3 * 2048 + 1] >= 2) & (d[:3 * 2048 + 1] <= 16)).all() and want["stats"]["triangles"] == n - 2
+    with one_cu_context(monkeypatch, torch_mod) as one_cu:
+        for ctx in (one_cu, gpu_ctx):
+            _check(ctx, ro, ci, True, want=want)
+        for env in (ALL_WAVE, ALL_BLOCK):
+            for k, x in env.items():
+                monkeypatch.setenv(k, x)
+            for ctx in (one_cu, gpu_ctx):
+                _check(ctx, ro, ci, True, want=want, operator=False, expect={"short_max": 0})
 
 
 def test_star_long_row(gpu_ctx):
