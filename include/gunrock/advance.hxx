@@ -89,7 +89,7 @@ int advance_forward_kernel(std::shared_ptr<Problem> problem, std::shared_ptr<fro
     ++context.scratch_epoch;
     mgx::transform_lbs_keep(visit_keep, edges, graph.d_scanned_row_offsets.data(), frontier_size, where.bits, context);
     context.keep.data = out; context.keep.n = edges; context.keep.iteration = iteration;
-    context.keep.functor = &mgx::functor_tag_t<Functor>::id; context.keep.epoch = context.scratch_epoch; context.keep.generation = mgx::frontier_generation(); context.keep.valid = true;
+    context.keep.functor = &mgx::functor_tag_t<Functor>::id; context.keep.epoch = context.scratch_epoch; context.keep.generation = mgx::frontier_generation().load(std::memory_order_relaxed); context.keep.valid = true;
     return (int)edges;
   }
   auto visit = [=] __device__(int slot, int segment, int rank) {
@@ -146,8 +146,7 @@ int advance_filter_fused_kernel(std::shared_ptr<Problem> problem, std::shared_pt
     }
   };
   mgx::transform_lbs(visit_and_keep, edges, graph.d_scanned_row_offsets.data(), frontier_size, context);
-  MGX_HIP(hipMemcpyAsync(context.mailbox, cursor, sizeof(long long), hipMemcpyDeviceToHost, context.stream()));
-  context.synchronize();
+  context.mailbox.fetch((const long long*)cursor, 1, context.stream());
   const long long kept = context.mailbox[0];
   output->resize((size_t)kept);   // throws on overflow; nothing was written past the capacity
   return (int)kept;

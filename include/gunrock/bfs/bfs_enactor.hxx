@@ -165,8 +165,6 @@ struct bfs_fused_enactor_t {
   bfs_fused_enactor_t(standard_context_t& context, int num_nodes) {
     fused.reset(new mgx::bfs_fused_state_t(num_nodes, context));
   }
-  bfs_fused_enactor_t(const bfs_fused_enactor_t&) = delete;
-  bfs_fused_enactor_t& operator=(const bfs_fused_enactor_t&) = delete;
 
   // the graph's hub-first layout (if it has one) as the fused loop takes it
   static mgx::bfs_layout_t layout_of(graph_device_t& g) {
@@ -257,7 +255,7 @@ struct bfs_fused_enactor_t {
                        bfs_problem->src, context, use_layout ? &layout : nullptr, direction_optimizing ? 1 : 0, alpha,
                        g.d_col_offsets.data(), g.d_row_indices.data());
     if (asked) g.src_shape_cache.collect();            // (bfs_fused_run returns behind its last launch: the copy in front of the first has landed)
-    fill_stats(last, fused->host_ctrl, direction_optimizing, true);
+    fill_stats(last, fused->host_ctrl.data(), direction_optimizing, true);
   }
 
   // `count` traversals enqueued back to back, one host wait (mgx::bfs_fused_run_many): out[i] = the counters of source
@@ -268,7 +266,7 @@ struct bfs_fused_enactor_t {
   // behind one wait (a traversal is ~2 * slots + 4 launches).  A chunk of 512 traversals is ~170 ms of device work on
   // RMAT-22: the extra host wait per chunk (~10 us) does not show.
   static constexpr int MANY_CHUNK = 512;
-  char* many_heads = nullptr;       // pinned, MANY_CHUNK heads at most
+  mgx::pinned_t<char> many_heads;   // MANY_CHUNK heads at most
   int many_cap = 0;
   int enact_many(std::shared_ptr<bfs_problem_t> bfs_problem, standard_context_t& context, const int* srcs, int count,
                  std::vector<bfs_run_stats_t>& out, bool direction_optimizing = false, float alpha = 0.f) {
@@ -277,10 +275,7 @@ struct bfs_fused_enactor_t {
     const bool use_layout = g.has_layout && (!direction_optimizing || g.csc_is_csr);
     const int want = count < MANY_CHUNK ? count : MANY_CHUNK;
     if (want > many_cap) {
-      if (many_heads) (void)hipHostFree(many_heads);
-      many_heads = nullptr;
-      many_cap = 0;
-      MGX_HIP(hipHostMalloc((void**)&many_heads, (size_t)want * mgx::bfs_many_head_bytes(), hipHostMallocDefault));
+      many_heads = mgx::pinned_t<char>((size_t)want * mgx::bfs_many_head_bytes());
       many_cap = want;
     }
     out.assign((size_t)(count > 0 ? count : 0), bfs_run_stats_t());
@@ -289,14 +284,13 @@ struct bfs_fused_enactor_t {
       const int part = count - first < MANY_CHUNK ? count - first : MANY_CHUNK;
       if (use_layout) resolve_shapes(g, layout, srcs + first, part, direction_optimizing ? 1 : 0, context);
       reruns += mgx::bfs_fused_run_many(*fused, g.d_row_offsets.data(), g.d_col_indices.data(), bfs_problem->d_labels.data(), srcs + first,
-                                        part, context, many_heads, use_layout ? &layout : nullptr, direction_optimizing ? 1 : 0,
+                                        part, context, many_heads.data(), use_layout ? &layout : nullptr, direction_optimizing ? 1 : 0,
                                         alpha, g.d_col_offsets.data(), g.d_row_indices.data());
-      for (int i = 0; i < part; ++i) fill_stats(out[(size_t)(first + i)], mgx::bfs_many_head(many_heads, i), direction_optimizing, false);
+      for (int i = 0; i < part; ++i) fill_stats(out[(size_t)(first + i)], mgx::bfs_many_head(many_heads.data(), i), direction_optimizing, false);
     }
     if (count > 0) { last = out.back(); bfs_problem->src = srcs[count - 1]; }
     return reruns;
   }
-  ~bfs_fused_enactor_t() { if (many_heads) (void)hipHostFree(many_heads); }
 };
 
 }  // namespace bfs

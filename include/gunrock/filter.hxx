@@ -25,7 +25,7 @@ int filter_kernel(std::shared_ptr<Problem> problem, std::shared_ptr<frontier_t<i
   context.keep.valid = false;
   const bool ready = rec.valid && !input->exposed() && rec.data == (const void*)candidates && rec.n == (long long)input->size() && rec.iteration == iteration &&
                      rec.functor == (const void*)&mgx::functor_tag_t<Functor>::id && rec.epoch == context.scratch_epoch &&
-                     rec.generation == mgx::frontier_generation();     // (nobody has written into a frontier from outside since)
+                     rec.generation == mgx::frontier_generation().load(std::memory_order_relaxed);     // (nobody has written into a frontier from outside since)
   const long long kept = ready ? pass.upsweep_from_bits()
                                : pass.upsweep([=] __device__(long long i) { return Functor::cond_filter(candidates[i], slice, iteration); });
   output->resize((size_t)kept);

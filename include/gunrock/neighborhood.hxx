@@ -81,7 +81,7 @@ int neighborhood_kernel(std::shared_ptr<Problem> problem, std::shared_ptr<fronti
         MGX_HIP(hipMemsetAsync(graph.d_nr_pos.data(), 0, (size_t)graph.num_nodes * sizeof(unsigned long long), context.stream()));
       }
       const long long seq = mgx::nr_full_frontier<Value>(L, [=] __device__(int v) -> Value { return Functor::get_value_to_reduce(v, data, iteration); }, reduced,
-                                   identity, reduce_op(), context, frontier, context.mailbox + 8, context.nr_flag(), epoch,
+                                   identity, reduce_op(), context, frontier, context.mailbox.data() + 8, context.nr_flag(), epoch,
                                    full ? -1 : frontier_size, offsets, subset ? (mgx::u64*)graph.d_nr_pos.data() : nullptr);
       if (seq) context.mailbox_wait(seq); else context.synchronize();
       // (a subset call added its frontier's degrees to the context's counter whatever its verdict: the base follows)

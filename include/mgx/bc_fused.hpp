@@ -335,8 +335,8 @@ struct bc_state_t {
   mem_t<int> ids, list[2], bound[2];
   mem_t<u32> flags;
   mem_t<bc_ctrl_t> ctrl;
-  bc_ctrl_t* h_ctrl = nullptr;       // pinned
-  void* sort_tmp = nullptr;
+  pinned_t<bc_ctrl_t> h_ctrl;
+  mem_t<char> sort_tmp;
   size_t sort_bytes = 0;
   int bound_cap = 0;
   bool ran = false;
@@ -347,12 +347,10 @@ struct bc_state_t {
   // launches of the first BC_TIMED sources of a run -- an event costs a few microseconds of stream gap, so only on request
   static constexpr int BC_TIMED = 64;
   bool timing = false;
-  std::vector<hipEvent_t> ev;        // 5 per timed source
+  std::vector<event_t> ev;           // 5 per timed source
   double phase_ms[4] = {0.0, 0.0, 0.0, 0.0};
   int timed = 0;
 
-  bc_state_t(const bc_state_t&) = delete;
-  bc_state_t& operator=(const bc_state_t&) = delete;
   bc_state_t(int n_, standard_context_t& ctx) : n(n_), opts(bc_opts_t::from_env()) {
     if (n > (1 << 29)) throw mgx_error(MGX_E_INVALID, "mgx bc: more than 2^29 vertices");
     const size_t N = (size_t)std::max(n, 1);
@@ -363,21 +361,16 @@ struct bc_state_t {
     ids = mem_t<int>(N, ctx);
     flags = mem_t<u32>(2, ctx);
     ctrl = mem_t<bc_ctrl_t>(1, ctx);
-    MGX_HIP(hipHostMalloc((void**)&h_ctrl, sizeof(bc_ctrl_t), hipHostMallocDefault));
+    h_ctrl = pinned_t<bc_ctrl_t>(1);
     const int rc = mgx_bc_sort_device(nullptr, nullptr, nullptr, nullptr, std::max(n, 1), 32, nullptr, &sort_bytes, ctx.stream());
     if (rc != 0) throw hip_error((hipError_t)rc, "mgx bc: sort scratch", __FILE__, __LINE__);
-    MGX_HIP(hipMalloc(&sort_tmp, std::max<size_t>(sort_bytes, 16)));
+    sort_tmp = mem_t<char>(std::max<size_t>(sort_bytes, 16), ctx);
     grow_bounds(std::min(n, 1 << 16) + 2, ctx);
-  }
-  ~bc_state_t() {
-    if (h_ctrl) (void)hipHostFree(h_ctrl);
-    if (sort_tmp) (void)hipFree(sort_tmp);
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
   }
   // event k (0: before the traversal, 1: behind it, 2: lists built, 3: forward done, 4: source done) of the source in flight
   void mark(int k, hipStream_t st) {
     if (!timing || sources >= BC_TIMED) return;
-    while (ev.size() < (size_t)(sources + 1) * 5) { hipEvent_t e; MGX_HIP(hipEventCreate(&e)); ev.push_back(e); }
+    while (ev.size() < (size_t)(sources + 1) * 5) ev.emplace_back();
     MGX_HIP(hipEventRecord(ev[(size_t)sources * 5 + (size_t)k], st));
   }
   // room for the list bounds of a traversal of `levels` levels
@@ -452,7 +445,7 @@ struct bc_state_t {
     launches += 3;
     for (int i = 0; i < two; ++i) {
       size_t bytes = sort_bytes;
-      const int rc = mgx_bc_sort_device(keys_in[i].data(), keys_sorted[i].data(), ids.data(), list[i].data(), n, end_bit, sort_tmp, &bytes, st);
+      const int rc = mgx_bc_sort_device(keys_in[i].data(), keys_sorted[i].data(), ids.data(), list[i].data(), n, end_bit, sort_tmp.data(), &bytes, st);
       if (rc != 0) throw hip_error((hipError_t)rc, "mgx bc: sort", __FILE__, __LINE__);
       // (cleared first: a key the traversal's level count did not promise could leave a bound unwritten -- an empty list then, never a stray index)
       MGX_HIP(hipMemsetAsync(bound[i].data(), 0, (size_t)(K + 1) * sizeof(int), st));
@@ -528,8 +521,7 @@ struct bc_state_t {
 
   // the run's ONE wait of its own: the control block
   const bc_ctrl_t& end_run(standard_context_t& ctx) {
-    MGX_HIP(hipMemcpyAsync(h_ctrl, ctrl.data(), sizeof(bc_ctrl_t), hipMemcpyDeviceToHost, ctx.stream()));
-    MGX_HIP(hipStreamSynchronize(ctx.stream()));
+    h_ctrl.fetch(ctrl.data(), 1, ctx.stream());
     ++waits;
     ran = true;
     timed = 0;
@@ -540,7 +532,7 @@ struct bc_state_t {
         MGX_HIP(hipEventElapsedTime(&ms, ev[(size_t)i * 5 + (size_t)k], ev[(size_t)i * 5 + (size_t)k + 1]));
         phase_ms[k] += (double)ms;
       }
-    return *h_ctrl;
+    return h_ctrl[0];
   }
 };
 

@@ -43,12 +43,7 @@ struct dbfs_state_t {
   long long bin_cap = 0;
   long long frontier_size = 0;
   int cur = 0;
-  unsigned long long* host_counters = nullptr;
-
-  dbfs_state_t() {}
-  dbfs_state_t(const dbfs_state_t&) = delete;
-  dbfs_state_t& operator=(const dbfs_state_t&) = delete;
-  ~dbfs_state_t() { if (host_counters) (void)hipHostFree(host_counters); }
+  pinned_t<unsigned long long> host_counters;
 
   void init(standard_context_t& ctx, int n_global_, int v_lo_, int v_hi_, int ranks_, int rank_,
             const int* ro, const int* ci, long long m_local_, int* borrowed_bins, long long borrowed_bin_cap) {
@@ -68,7 +63,7 @@ struct dbfs_state_t {
       bins = mem_t<int>((size_t)ranks * (size_t)bin_cap + 1, ctx);
     }
     counters = mem_t<unsigned long long>((size_t)ranks + 1, ctx);
-    MGX_HIP(hipHostMalloc((void**)&host_counters, (ranks + 1) * sizeof(unsigned long long), hipHostMallocDefault));
+    host_counters = pinned_t<unsigned long long>((size_t)ranks + 1);
     ctx.reserve_scratch(scan_scratch_bytes(n_local) + (1 << 16));
   }
 };
@@ -148,9 +143,7 @@ inline void dbfs_expand(dbfs_state_t& st, standard_context_t& ctx, long long* ed
         },
         front, st.scanned.data(), st.frontier_size, ctx);
   }
-  MGX_HIP(hipMemcpyAsync(st.host_counters, st.counters.data(), (size_t)st.ranks * sizeof(unsigned long long),
-                         hipMemcpyDeviceToHost, s));
-  MGX_HIP(hipStreamSynchronize(s));
+  st.host_counters.fetch(st.counters.data(), (size_t)st.ranks, s);
   if (edges_out) *edges_out = front;
 }
 
@@ -182,7 +175,7 @@ inline void dbfs_receive(dbfs_state_t& st, const int* ids, long long count, int 
 // next frontier becomes current; returns its size
 inline long long dbfs_swap(dbfs_state_t& st, standard_context_t& ctx) {
   hipStream_t s = ctx.stream();
-  MGX_HIP(hipMemcpyAsync(st.host_counters + st.ranks, st.counters.data() + st.ranks, sizeof(unsigned long long),
+  MGX_HIP(hipMemcpyAsync(st.host_counters.data() + st.ranks, st.counters.data() + st.ranks, sizeof(unsigned long long),
                          hipMemcpyDeviceToHost, s));
   MGX_HIP(hipMemsetAsync(st.counters.data() + st.ranks, 0, sizeof(unsigned long long), s));
   MGX_HIP(hipStreamSynchronize(s));

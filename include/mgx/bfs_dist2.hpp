@@ -488,7 +488,7 @@ struct d2_state_t {
   mem_t<u32> slot_marks;              // marks stored by the push workgroups of a level (bfs_body_finish): what k_d2_newbits bases its shape on
   u32 declare_mul = 16;               // a level whose push stored more than this x list_cap marks does not fill its list (MGX_DIST_DECLARE_MUL; 0: always fill)
   int sparse_push = 1;                // levels of at most list_cap edges append to the list themselves (MGX_DIST_SPARSE_PUSH=0: every level sweeps)
-  u64* host_flag = nullptr;           // pinned: what k_d2_lists_apply tells the host
+  pinned_t<u64> host_flag;            // pinned: what k_d2_lists_apply tells the host
   u64 flag_seq = 0;
   // The rank's row layout (mgx/row_layout.hpp; built on request by mgx_dbfs2_build_units, owners in GLOBAL ids, padding units owned
   // by vertex n_global): the unit blocks of its long rows -- or, when it has cold-edge lists, the blocks of the rows' HOT entries alone,
@@ -560,15 +560,9 @@ struct d2_state_t {
     labels = mem_t<int>((size_t)n_local + 1, ctx);
     merged = mem_t<u32>((size_t)nwords + 4, ctx);
     MGX_HIP(hipMemsetAsync(merged.data(), 0, ((size_t)nwords + 4) * sizeof(u32), ctx.stream()));   // (the bit of vertex n_global stays 0)
-    MGX_HIP(hipHostMalloc((void**)&host_flag, 64, hipHostMallocDefault));
+    host_flag = pinned_t<u64>(8);
     host_flag[0] = host_flag[1] = host_flag[2] = 0;
   }
-  ~d2_state_t() {
-    if (host_flag) (void)hipHostFree(host_flag);
-  }
-  d2_state_t() {}
-  d2_state_t(const d2_state_t&) = delete;
-  d2_state_t& operator=(const d2_state_t&) = delete;
   // capacity (ids) of a rank's list: n / (256 ranks), at least 252, so that head + ids is a multiple of 4 words
   static u32 default_list_cap(int n_global, int ranks) {
     long long c = (long long)n_global / (256ll * ranks);
@@ -696,7 +690,7 @@ inline u64 d2_enqueue_apply_lists(d2_state_t& st, int level, const u32* glists, 
   // (does the kernel read the rank's own buffer?  a one-rank run, or an in-place gather)
   const bool own_is_read = st.mylist && glists < st.mylist + st.list_words() && st.mylist < glists + (size_t)nlists * (size_t)stride_words;
   hipLaunchKernelGGL(k_d2_lists_apply<BLOCK>, dim3(256), dim3(BLOCK), 0, s, a, level, glists, nlists, (u32)stride_words, st.list_cap,
-                     st.labels.data(), st.ranks, st.rank, spec ? (u64*)nullptr : st.host_flag, seq, st.newbits, nlists == 1 ? 0 : st.rank,
+                     st.labels.data(), st.ranks, st.rank, spec ? (u64*)nullptr : st.host_flag.data(), seq, st.newbits, nlists == 1 ? 0 : st.rank,
                      (st.mylist && !own_is_read) ? st.mylist : nullptr, spec ? 1 : 0);
   MGX_CHECK_LAUNCH("partitioned BFS: list merge launch");
   // the count of this rank's own list, for the next level's sweep: behind the kernel when the kernel reads that very list (see its header)
@@ -707,7 +701,7 @@ inline void d2_apply_lists(d2_state_t& st, int level, const u32* glists, int nli
                            long long* out3) {
   hipStream_t s = ctx.stream();
   const u64 seq = d2_enqueue_apply_lists(st, level, glists, nlists, stride_words, ctx, false);
-  volatile u64* const flag = st.host_flag;
+  volatile u64* const flag = st.host_flag.data();
   long long spins = 0;
   while (flag[0] != seq) {
     if (++spins > 20000000LL) { MGX_HIP(hipStreamSynchronize(s)); break; }
@@ -763,7 +757,7 @@ inline void d2_merge(d2_state_t& st, int level, const u32* gathered, int maps, l
 // [5] edges of this rank's next queues.
 inline void d2_status(d2_state_t& st, int next_level, standard_context_t& ctx, long long* out) {
   hipStream_t s = ctx.stream();
-  bfs_ctrl_t* hc = st.fs->host_ctrl;
+  bfs_ctrl_t* hc = st.fs->host_ctrl.data();
   MGX_HIP(hipMemcpyAsync(hc, st.fs->ctrl.data(), offsetof(bfs_ctrl_t, trace), hipMemcpyDeviceToHost, s));
   MGX_HIP(hipStreamSynchronize(s));
   const u64 cur = hc->cursor[next_level % 3], lcur = hc->lcursor[next_level % 3];
@@ -912,7 +906,7 @@ inline void d2_run(d2_state_t& st, comm_t& cm, d2_run_bufs_t& bufs, int src, int
       if (o3[1] == 0) {                                     // a source without edges: over
         MGX_CHECK_LAUNCH("partitioned BFS: kernel launch");
         d2_status(st, level, ctx, out6);
-        bufs.learn(st.fs->host_ctrl, (int)out6[1], out6[3], st.list_cap);
+        bufs.learn(st.fs->host_ctrl.data(), (int)out6[1], out6[3], st.list_cap);
         return;
       }
       if (o3[0]) d2_exchange_bitmaps(st, cm, bufs, 0, exchange, xwords, ctx);
@@ -966,7 +960,7 @@ inline void d2_run(d2_state_t& st, comm_t& cm, d2_run_bufs_t& bufs, int src, int
       MGX_CHECK_LAUNCH("partitioned BFS: kernel launch");
       d2_status(st, level, ctx, out6);
     }
-    bufs.learn(st.fs->host_ctrl, (int)out6[1], out6[3], st.list_cap);
+    bufs.learn(st.fs->host_ctrl.data(), (int)out6[1], out6[3], st.list_cap);
     return;
   }
   int batch = bufs.levels_hint;
@@ -1036,7 +1030,7 @@ inline void d2_group_run(d2_state_t** sts, d2_run_bufs_t** bufs, d2_group_bufs_t
       if (o3[1] == 0) {
         MGX_CHECK_LAUNCH("partitioned BFS (group): kernel launch");
         for (int r = 0; r < G; ++r) d2_status(*sts[r], level, ctx, out6 + 6 * r);
-        for (int r = 0; r < G; ++r) bufs[r]->learn(sts[r]->fs->host_ctrl, (int)out6[6 * r + 1], out6[6 * r + 3], sts[r]->list_cap);
+        for (int r = 0; r < G; ++r) bufs[r]->learn(sts[r]->fs->host_ctrl.data(), (int)out6[6 * r + 1], out6[6 * r + 3], sts[r]->list_cap);
         return;
       }
       if (o3[0]) bitmaps(0);
@@ -1074,7 +1068,7 @@ inline void d2_group_run(d2_state_t** sts, d2_run_bufs_t** bufs, d2_group_bufs_t
       MGX_CHECK_LAUNCH("partitioned BFS (group): kernel launch");
       for (int r = 0; r < G; ++r) d2_status(*sts[r], level, ctx, out6 + 6 * r);
     }
-    for (int r = 0; r < G; ++r) bufs[r]->learn(sts[r]->fs->host_ctrl, (int)out6[6 * r + 1], out6[6 * r + 3], sts[r]->list_cap);
+    for (int r = 0; r < G; ++r) bufs[r]->learn(sts[r]->fs->host_ctrl.data(), (int)out6[6 * r + 1], out6[6 * r + 3], sts[r]->list_cap);
     return;
   }
   int batch = bufs[0]->levels_hint;

@@ -1270,8 +1270,8 @@ struct bfs_fused_state_t {
   mem_t<bfs_ctrl_t> ctrl;
   mem_t<u32> flush_buf;              // deferred hot marks: BFS_FLUSH_MAX bitmaps of BFS_FLUSH_WORDS words (allocated on demand)
   unsigned defer_min_marks = 2048;   // a push workgroup with more deferred discoveries flushes a bitmap (MGX_BFS_DEFER: 0 = never defer)
-  bfs_ctrl_t* host_ctrl = nullptr;   // pinned copy for stats
-  u64* host_seq = nullptr;           // pinned: the batch number k_bfs_publish stores when the copy above is complete
+  pinned_t<bfs_ctrl_t> host_ctrl;    // pinned copy for stats
+  pinned_t<u64> host_seq;            // pinned: the batch number k_bfs_publish stores when the copy above is complete
   u64 seq = 0;
   bool spin = true;                  // wait for a batch by spinning on host_seq (false: copy + hipStreamSynchronize)
   int n = 0;
@@ -1307,14 +1307,14 @@ struct bfs_fused_state_t {
                                      // leaves a ~6 us gap on the stream: profiling runs only)
   unsigned hot_min_edges = 65536;    // smaller levels probe the bitmap in L2 instead of copying its hot prefix to LDS
   // timing of the level kernels of the last run (HIP events around each batch of launches)
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  event_t ev0, ev1;
   double level_kernel_ms = 0.0;
   long long level_kernel_launches = 0;
   float batch_ms[256];               // duration of each launch batch of the last run (per level when levels_per_sync == 1)
   int batches = 0;
   // per-launch timing of the two push kernels of a level: events [3i] stream [3i+1] wave [3i+2]
   static constexpr int EV_POOL = 96;
-  hipEvent_t wev[EV_POOL] = {};
+  event_t wev[EV_POOL];
   double wave_kernel_ms = 0.0;       // the short-row part of k_bfs_push (timing mode 1)
   long long wave_kernel_launches = 0;
   double stream_kernel_ms = 0.0;     // the long-row part of k_bfs_push (timing mode 1) or the whole merged launch (mode 2)
@@ -1337,23 +1337,11 @@ struct bfs_fused_state_t {
       lq_off[i] = mem_t<u32>((size_t)num_nodes + 1, ctx);
     }
     ctrl = mem_t<bfs_ctrl_t>(1, ctx);
-    MGX_HIP(hipHostMalloc((void**)&host_ctrl, sizeof(bfs_ctrl_t), hipHostMallocDefault));
-    MGX_HIP(hipHostMalloc((void**)&host_seq, 64, hipHostMallocDefault));
-    *host_seq = 0;
-    MGX_HIP(hipEventCreate(&ev0));
-    MGX_HIP(hipEventCreate(&ev1));
-    for (int i = 0; i < EV_POOL; ++i) MGX_HIP(hipEventCreate(&wev[i]));
+    host_ctrl = pinned_t<bfs_ctrl_t>(1);
+    host_seq = pinned_t<u64>(8);
+    host_seq[0] = 0;
     if (const char* e = mgx::env("MGX_BFS_LONG_MIN")) long_min = atoi(e) > 0 ? atoi(e) : 0;
     if (const char* e = mgx::env("MGX_BFS_HOT_MIN_EDGES")) hot_min_edges = (unsigned)atoll(e);
-  }
-  bfs_fused_state_t(const bfs_fused_state_t&) = delete;
-  bfs_fused_state_t& operator=(const bfs_fused_state_t&) = delete;
-  ~bfs_fused_state_t() {
-    if (host_ctrl) (void)hipHostFree(host_ctrl);
-    if (host_seq) (void)hipHostFree(host_seq);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    for (int i = 0; i < EV_POOL; ++i) if (wev[i]) (void)hipEventDestroy(wev[i]);
   }
   size_t bitmap_words() const { return visited.size(); }
 };

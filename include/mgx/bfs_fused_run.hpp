@@ -813,10 +813,10 @@ inline void bfs_fused_run(bfs_fused_state_t& st, const int* row_offsets, const i
     constexpr size_t head_bytes = offsetof(bfs_ctrl_t, trace) + 64 * sizeof(u64);
     if ((opt.spin >= 0 ? opt.spin != 0 : st.spin) && !batch_events) {
       const u64 seq = ++st.seq;
-      hipLaunchKernelGGL(k_bfs_publish, dim3(1), dim3(256), 0, s, (const bfs_ctrl_t*)st.ctrl.data(), st.host_ctrl, st.host_seq, seq,
+      hipLaunchKernelGGL(k_bfs_publish, dim3(1), dim3(256), 0, s, (const bfs_ctrl_t*)st.ctrl.data(), st.host_ctrl.data(), st.host_seq.data(), seq,
                          (int)(head_bytes / 4));
       MGX_CHECK_LAUNCH("fused BFS: kernel launch");
-      volatile u64* const flag = st.host_seq;
+      volatile u64* const flag = st.host_seq.data();
       long long spins = 0;
       while (*flag != seq) {
         if (++spins > 20000000LL) { MGX_HIP(hipStreamSynchronize(s)); break; }     // (a failed launch: let the runtime report it)
@@ -825,7 +825,7 @@ inline void bfs_fused_run(bfs_fused_state_t& st, const int* row_offsets, const i
       __atomic_thread_fence(__ATOMIC_ACQUIRE);
     } else {
       MGX_CHECK_LAUNCH("fused BFS: kernel launch");
-      MGX_HIP(hipMemcpyAsync(st.host_ctrl, st.ctrl.data(), head_bytes, hipMemcpyDeviceToHost, s));
+      MGX_HIP(hipMemcpyAsync(st.host_ctrl.data(), st.ctrl.data(), head_bytes, hipMemcpyDeviceToHost, s));
       MGX_HIP(hipStreamSynchronize(s));
     }
     float ms = 0.f;
@@ -875,7 +875,7 @@ inline void bfs_fused_run(bfs_fused_state_t& st, const int* row_offsets, const i
     MGX_HIP(hipMemcpyAsync(st.host_ctrl->trace + 64, st.ctrl.data()->trace + 64, (size_t)(lv - 64) * sizeof(u64), hipMemcpyDeviceToHost, s));
     MGX_HIP(hipStreamSynchronize(s));
   }
-  bfs_learn_slots(st, a, st.host_ctrl, mode, BFS_MAX_TRACE, plan.minis, cls);
+  bfs_learn_slots(st, a, st.host_ctrl.data(), mode, BFS_MAX_TRACE, plan.minis, cls);
 }
 
 // COUNT traversals enqueued back to back with ONE host wait at the end (mgx_bfs_run_many): every traversal is complete --
@@ -953,7 +953,7 @@ inline int bfs_fused_run_many(bfs_fused_state_t& st, const int* row_offsets, con
     // slots (round 5: grid2d-22, 79.9 -> 61.7 ms per traversal); the heads are what those calls leave.
     for (int i = 0; i < count; ++i) {
       run_one(i);
-      memcpy(bfs_many_head(heads, i), st.host_ctrl, bfs_head_bytes());
+      memcpy(bfs_many_head(heads, i), st.host_ctrl.data(), bfs_head_bytes());
     }
     return 0;
   }
@@ -1026,12 +1026,12 @@ inline int bfs_fused_run_many(bfs_fused_state_t& st, const int* row_offsets, con
   assert(pending[0] == count - 1);     // the last traversal ran in state 0 (state_of(count - 1) == 0): the caller's labels are its labels
   if (pending[1] >= 0)
     hipLaunchKernelGGL(k_bfs_publish2, dim3(1), dim3(256), 0, s, (const bfs_ctrl_t*)plans[0].a.ctrl, bfs_many_head(heads, pending[0]),
-                       (const bfs_ctrl_t*)plans[1].a.ctrl, bfs_many_head(heads, pending[1]), st.host_seq, seq, head_words);
+                       (const bfs_ctrl_t*)plans[1].a.ctrl, bfs_many_head(heads, pending[1]), st.host_seq.data(), seq, head_words);
   else
-    hipLaunchKernelGGL(k_bfs_publish, dim3(1), dim3(256), 0, s, (const bfs_ctrl_t*)st.ctrl.data(), bfs_many_head(heads, count - 1), st.host_seq, seq, head_words);
+    hipLaunchKernelGGL(k_bfs_publish, dim3(1), dim3(256), 0, s, (const bfs_ctrl_t*)st.ctrl.data(), bfs_many_head(heads, count - 1), st.host_seq.data(), seq, head_words);
   MGX_CHECK_LAUNCH("fused BFS (batch of sources): kernel launch");
   {
-    volatile u64* const flag = st.host_seq;
+    volatile u64* const flag = st.host_seq.data();
     long long spins = 0;
     while (*flag != seq) {
       if (++spins > 20000000LL) { MGX_HIP(hipStreamSynchronize(s)); break; }
@@ -1051,7 +1051,7 @@ inline int bfs_fused_run_many(bfs_fused_state_t& st, const int* row_offsets, con
     }
     if (h->done) { bfs_learn_slots(st, a, h, mode, 64, plan.minis, classes[(size_t)i]); continue; }
     run_one(i);
-    memcpy(h, st.host_ctrl, bfs_head_bytes());
+    memcpy(h, st.host_ctrl.data(), bfs_head_bytes());
     ++reruns;
     if (i != count - 1) redo_last = true;
   }

@@ -305,17 +305,14 @@ struct cc_label_stats_t {
   mem_t<int> sizes;
   mem_t<int> hot;
   mem_t<u64> out;
-  u64* h_pinned = nullptr;
+  pinned_t<u64> h_pinned;
 
-  cc_label_stats_t(const cc_label_stats_t&) = delete;
-  cc_label_stats_t& operator=(const cc_label_stats_t&) = delete;
   cc_label_stats_t(int n, context_t& ctx) {
     sizes = mem_t<int>((size_t)std::max(n, 1), ctx);
     hot = mem_t<int>(1, ctx);
     out = mem_t<u64>(2, ctx);
-    MGX_HIP(hipHostMalloc((void**)&h_pinned, 2 * sizeof(u64), hipHostMallocDefault));
+    h_pinned = pinned_t<u64>(2);
   }
-  ~cc_label_stats_t() { if (h_pinned) (void)hipHostFree(h_pinned); }
 
   // {components, largest, its label} of a label array of n entries on the device
   std::vector<long long> run(const int* label, int n, standard_context_t& ctx) {
@@ -324,10 +321,9 @@ struct cc_label_stats_t {
     const int max_blocks = std::max(ctx.num_cus, 1) * 8;
     hipLaunchKernelGGL(k_cc_sample, dim3(1), dim3(BLOCK), 0, st, label, n, CC_SEED_DEFAULT, hot.data());
     cc_label_stats(label, n, hot.data(), sizes.data(), out.data(), max_blocks, st);
-    MGX_HIP(hipMemcpyAsync(h_pinned, out.data(), 2 * sizeof(u64), hipMemcpyDeviceToHost, st));
-    MGX_HIP(hipStreamSynchronize(st));
+    h_pinned.fetch(out.data(), 2, st);
     long long s[3];
-    cc_unpack_stats(h_pinned, s);
+    cc_unpack_stats(h_pinned.data(), s);
     return {s[0], s[1], s[2]};
   }
 };
@@ -341,11 +337,9 @@ struct cc_fused_state_t {
   mem_t<int2> l_list;
   mem_t<int> words;                 // [0] short count, [1] long items, [2] c
   mem_t<u64> stat;                  // [0] packed largest, [1] components, [2] skipped
-  u64* h_pinned = nullptr;          // the one read-back
+  pinned_t<u64> h_pinned;           // the one read-back
   long long l_cap = 0;
 
-  cc_fused_state_t(const cc_fused_state_t&) = delete;
-  cc_fused_state_t& operator=(const cc_fused_state_t&) = delete;
   cc_fused_state_t(int n_, long long m, context_t& ctx) : n(n_) {
     const size_t N = (size_t)std::max(n, 1);
     comp = mem_t<int>(N, ctx);
@@ -356,9 +350,8 @@ struct cc_fused_state_t {
     l_list = mem_t<int2>((size_t)l_cap, ctx);
     words = mem_t<int>(4, ctx);
     stat = mem_t<u64>(4, ctx);
-    MGX_HIP(hipHostMalloc((void**)&h_pinned, 4 * sizeof(u64), hipHostMallocDefault));
+    h_pinned = pinned_t<u64>(4);
   }
-  ~cc_fused_state_t() { if (h_pinned) (void)hipHostFree(h_pinned); }
 
   // Label the graph (ro, ci: CSR on the device; co, ri: its genuine CSC or nullptr).  symmetric: the caller's word that every
   // entry has its reverse.  Returns {components, largest, its label, skipped, host waits}.
@@ -389,10 +382,9 @@ struct cc_fused_state_t {
     hipLaunchKernelGGL(k_cc_compress, dim3(grid_n), dim3(BLOCK), 0, st, comp.data(), n);
     MGX_CHECK_LAUNCH("mgx cc run");
     cc_label_stats(comp.data(), n, c_word, sizes.data(), stat.data(), max_blocks, st);
-    MGX_HIP(hipMemcpyAsync(h_pinned, stat.data(), 3 * sizeof(u64), hipMemcpyDeviceToHost, st));
-    MGX_HIP(hipStreamSynchronize(st));
+    h_pinned.fetch(stat.data(), 3, st);
     long long s[3];
-    cc_unpack_stats(h_pinned, s);
+    cc_unpack_stats(h_pinned.data(), s);
     return {s[0], s[1], s[2], (long long)h_pinned[2], 1};
   }
 };

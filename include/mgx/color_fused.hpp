@@ -234,15 +234,13 @@ struct color_fused_state_t {
   mem_t<unsigned long long> tally;
   mem_t<int> cnt;                   // 3 per round (+ 3 for the round behind the last)
   mem_t<int> max_colour;
-  int* h_pinned = nullptr;          // one batch's counts + the largest colour
+  pinned_t<int> h_pinned;           // one batch's counts + the largest colour
   long long l_cap = 0;
   // the last run, per round run: short rows, long items, long rows at the start of the round (mgx_color_info); round 0's short
   // rows are the vertices of fewer than long_min entries.  has_run: a run has finished.
   std::vector<long long> round_rows;
   bool has_run = false;
 
-  color_fused_state_t(const color_fused_state_t&) = delete;
-  color_fused_state_t& operator=(const color_fused_state_t&) = delete;
   color_fused_state_t(int n_, long long m, context_t& ctx) : n(n_) {
     const size_t N = (size_t)std::max(n, 1);
     colour = mem_t<int>(N, ctx);
@@ -257,9 +255,8 @@ struct color_fused_state_t {
     tally = mem_t<unsigned long long>(N, ctx);
     MGX_HIP(hipMemsetAsync(tally.data(), 0, N * sizeof(unsigned long long), ctx.stream()));
     max_colour = mem_t<int>(1, ctx);
-    MGX_HIP(hipHostMalloc((void**)&h_pinned, (3 * (COLOR_BATCH_MAX + 2) + 1) * sizeof(int), hipHostMallocDefault));
+    h_pinned = pinned_t<int>(3 * (COLOR_BATCH_MAX + 2) + 1);
   }
-  ~color_fused_state_t() { if (h_pinned) (void)hipHostFree(h_pinned); }
 
   // Colour the graph (ro, ci: CSR on the device) from all-uncoloured.  trace gets the active vertices at the start of every round
   // run; returns {rounds, left uncoloured, largest colour, host waits}.
@@ -320,8 +317,8 @@ struct color_fused_state_t {
         }
       }
       MGX_CHECK_LAUNCH("mgx color round");
-      MGX_HIP(hipMemcpyAsync(h_pinned, cnt.data() + 3 * i, (size_t)(3 * (b + 1)) * sizeof(int), hipMemcpyDeviceToHost, st));
-      MGX_HIP(hipMemcpyAsync(h_pinned + 3 * (COLOR_BATCH_MAX + 2), max_colour.data(), sizeof(int), hipMemcpyDeviceToHost, st));
+      MGX_HIP(hipMemcpyAsync(h_pinned.data(), cnt.data() + 3 * i, (size_t)(3 * (b + 1)) * sizeof(int), hipMemcpyDeviceToHost, st));
+      MGX_HIP(hipMemcpyAsync(h_pinned.data() + 3 * (COLOR_BATCH_MAX + 2), max_colour.data(), sizeof(int), hipMemcpyDeviceToHost, st));
       MGX_HIP(hipStreamSynchronize(st));
       ++waits;
       for (long long r = 0; r <= b; ++r) {

@@ -422,11 +422,9 @@ struct kcore_fused_state_t {
   mem_t<int> lists;                        // candidates | short rows of the front
   mem_t<int2> f_items;
   mem_t<kcore_control_t> ctl;
-  kcore_totals_t* h_totals = nullptr;      // pinned
+  pinned_t<kcore_totals_t> h_totals;
   long long launches = 0;                  // of the last run, the idle ones behind its end included
 
-  kcore_fused_state_t(const kcore_fused_state_t&) = delete;
-  kcore_fused_state_t& operator=(const kcore_fused_state_t&) = delete;
   kcore_fused_state_t(int n_, long long m, context_t& ctx) : n(n_) {
     const size_t N = (size_t)std::max(n, 1);
     lists = mem_t<int>(2 * N, ctx);        // a vertex crosses a k once, and leaves once
@@ -434,9 +432,8 @@ struct kcore_fused_state_t {
     const long long items = std::min<long long>((long long)N, m / KCORE_LONG_MIN + 1) + m / KCORE_SEG + 1;
     f_items = mem_t<int2>((size_t)items, ctx);
     ctl = mem_t<kcore_control_t>(1, ctx);
-    MGX_HIP(hipHostMalloc((void**)&h_totals, sizeof(kcore_totals_t), hipHostMallocDefault));
+    h_totals = pinned_t<kcore_totals_t>(1);
   }
-  ~kcore_fused_state_t() { if (h_totals) (void)hipHostFree(h_totals); }
 
   // Peel the graph (ro, ci: CSR on the device).  deg holds the row lengths and core zeros when the stream gets here; they end
   // as the operator path leaves them.  Returns {levels, removing passes, entries expanded, vertices removed, stranded, host
@@ -445,8 +442,8 @@ struct kcore_fused_state_t {
     const hipStream_t st = ctx.stream();
     kcore_totals_t zero{};
     zero.largest = -1;
-    *h_totals = zero;
-    MGX_HIP(hipMemcpyAsync(&ctl.data()->totals, h_totals, sizeof(kcore_totals_t), hipMemcpyHostToDevice, st));
+    h_totals[0] = zero;
+    MGX_HIP(hipMemcpyAsync(&ctl.data()->totals, h_totals.data(), sizeof(kcore_totals_t), hipMemcpyHostToDevice, st));
     MGX_HIP(hipMemsetAsync(ctl.data()->ring, 0, 4 * sizeof(kcore_word_t), st));
     kcore_step_args_t a;
     a.ro = ro; a.ci = ci; a.deg = deg; a.core = core;
@@ -462,8 +459,7 @@ struct kcore_fused_state_t {
       for (int j = 0; j < batch; ++j, ++launches)
         hipLaunchKernelGGL(k_kcore_step, dim3(blocks), dim3(BLOCK), 0, st, a, (unsigned)(launches & 0xffffffffll));
       MGX_CHECK_LAUNCH("mgx kcore step");
-      MGX_HIP(hipMemcpyAsync(h_totals, &ctl.data()->totals, sizeof(kcore_totals_t), hipMemcpyDeviceToHost, st));
-      MGX_HIP(hipStreamSynchronize(st));
+      h_totals.fetch(&ctl.data()->totals, 1, st);
       ++waits;
       if (h_totals->done) break;
       if (launches > most) throw mgx_error(MGX_E_HIP, "mgx kcore: the run did not end");

@@ -330,19 +330,16 @@ struct lspar_fused_state_t {
   mem_t<int> oro, oci, oeid, osim;
   mem_t<int2> items;
   mem_t<int> cnt, seg_hist;
-  int* h_pinned = nullptr;          // the item count and rows cut
+  pinned_t<int> h_pinned;           // the item count and rows cut
   long long last_items = -1;        // the last run's item count (mgx_lspar_info; -1: no run yet)
 
-  lspar_fused_state_t(const lspar_fused_state_t&) = delete;
-  lspar_fused_state_t& operator=(const lspar_fused_state_t&) = delete;
   lspar_fused_state_t(int n_, long long m_, standard_context_t& ctx) : n(n_), m(m_) {
     oro = mem_t<int>((size_t)n + 1, ctx);
     items = mem_t<int2>((size_t)(m / LSPAR_SHORT_MAX + m / LSPAR_SEG + 2), ctx);
     cnt = mem_t<int>(2, ctx);
     ctx.reserve_scratch(scan_scratch_bytes(std::max(n, 1)));
-    MGX_HIP(hipHostMalloc((void**)&h_pinned, 2 * sizeof(int), hipHostMallocDefault));
+    h_pinned = pinned_t<int>(2);
   }
-  ~lspar_fused_state_t() { if (h_pinned) (void)hipHostFree(h_pinned); }
 
   // returns {kept entries, rows cut, host waits}; the outputs are complete when the stream is
   std::vector<long long> run(const int* ro, const int* ci, unsigned seed, int k, double e, standard_context_t& ctx) {
@@ -360,7 +357,7 @@ struct lspar_fused_state_t {
     const int max_blocks = std::max(ctx.num_cus, 1) * 8;
     if (n > 0) {
       hipLaunchKernelGGL(k_lspar_classify, dim3(grid_for(n, BLOCK, max_blocks)), dim3(BLOCK), 0, st, a);
-      MGX_HIP(hipMemcpyAsync(h_pinned, cnt.data(), 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+      MGX_HIP(hipMemcpyAsync(h_pinned.data(), cnt.data(), 2 * sizeof(int), hipMemcpyDeviceToHost, st));
       const int mh_blocks = grid_for(n, BLOCK / LSPAR_MH_GROUP, max_blocks);
       if (k == 1) {
         hipLaunchKernelGGL(k_lspar_minhash_short<1>, dim3(mh_blocks), dim3(BLOCK), 0, st, a);

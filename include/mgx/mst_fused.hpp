@@ -466,15 +466,13 @@ struct mst_fused_state_t {
   mem_t<int> out_a, out_b;       // the list: n entries of room
   mem_t<float> out_w;
   mem_t<double> tile_sum;
-  u64* h_pinned = nullptr;
+  pinned_t<u64> h_pinned;
   mst_opts_t opts;               // of the last run
   long long h[MST_S_WORDS] = {0};
   int last = -1;                 // the setup of the last run (-1: none, or it failed)
   long long waits = 0;           // host waits of the run in progress: counted where the host waits, not stated
   bool reused = false;
 
-  mst_fused_state_t(const mst_fused_state_t&) = delete;
-  mst_fused_state_t& operator=(const mst_fused_state_t&) = delete;
   mst_fused_state_t(int n_, long long m_, standard_context_t& ctx) : n(n_), m(m_) {
     // (the sort's merge passes keep run widths w with 2 w an int; positions are ints)
     if (m > (1LL << 29)) throw mgx_error(MGX_E_FRONTIER_OVERFLOW, "mgx mst: more than 2^29 CSR entries");
@@ -492,10 +490,9 @@ struct mst_fused_state_t {
     out_a = mem_t<int>(N, ctx); out_b = mem_t<int>(N, ctx);
     out_w = mem_t<float>(N, ctx);
     tile_sum = mem_t<double>(N / MST_SUM_TILE + 2, ctx);
-    MGX_HIP(hipHostMalloc((void**)&h_pinned, MST_S_WORDS * sizeof(u64), hipHostMallocDefault));
+    h_pinned = pinned_t<u64>(MST_S_WORDS);
     ctx.reserve_scratch(scan_scratch_bytes(std::max<long long>((long long)n + 1, 2 * m)));
   }
-  ~mst_fused_state_t() { if (h_pinned) (void)hipHostFree(h_pinned); }
 
   // enqueue the build of setup[symmetric]; `t` must outlive the launches
   void build(mst_setup_t& s, mst_setup_tmp_t& t, const int* ro, const int* ci, const float* w, const int* co, const int* ri,
@@ -608,7 +605,7 @@ struct mst_fused_state_t {
       const unsigned epoch = single ? ctx.next_lookback_epoch() : 0u;
       typedef compact_t::no_pred_t P;
       hipLaunchKernelGGL((k_compact_upsweep<P, true>), dim3((unsigned)ntiles), dim3(BLOCK), 0, st, P(), s.cap, s.bits.data(), partials,
-                         single ? ctx.lookback_status : (unsigned long long*)nullptr, ctx.lookback_ticket, ctx.lookback_ticket_base,
+                         single ? ctx.lookback_status.data() : (unsigned long long*)nullptr, ctx.lookback_ticket.data(), ctx.lookback_ticket_base,
                          epoch, (long long*)nullptr, 0LL);
       if (single) ctx.lookback_ticket_base += (unsigned)ntiles;
       else hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(BLOCK), 0, st, partials, ntiles, (long long*)nullptr, 0LL);
@@ -642,8 +639,7 @@ struct mst_fused_state_t {
     cc_label_stats(comp.data(), n, hot.data(), sizes.data(), stat.data(), max_blocks, st);
     mst_sum_list(out_w.data(), d_count, (long long)n, tile_sum.data(), words.data(), s.nanw.data(), s.off.data(), n, stat.data(), st);
     MGX_CHECK_LAUNCH("mgx mst finish");
-    MGX_HIP(hipMemcpyAsync(h_pinned, stat.data(), MST_S_WORDS * sizeof(u64), hipMemcpyDeviceToHost, st));
-    MGX_HIP(hipStreamSynchronize(st));
+    h_pinned.fetch(stat.data(), MST_S_WORDS, st);
     ++waits;
     for (int i = 0; i < MST_S_WORDS; ++i) h[i] = (long long)h_pinned[i];
     if (h[MST_S_NAN]) {
@@ -654,7 +650,7 @@ struct mst_fused_state_t {
     s.entries = h[MST_S_ENTRIES];
     last = symmetric ? 1 : 0;
     long long cs[3];
-    cc_unpack_stats(h_pinned, cs);
+    cc_unpack_stats(h_pinned.data(), cs);
     return {h[MST_S_EDGES], cs[0], cs[1], cs[2], h[MST_S_ROUNDS], waits, h[MST_S_STEPS], h[MST_S_ENTRIES]};
   }
 

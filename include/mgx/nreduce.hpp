@@ -679,7 +679,7 @@ inline long long nr_full_frontier(const nr_layout_t& L_in, GetValue get, V* redu
   struct publish_t {            // (behind everything else, whichever way the function is left)
     bool subset; hipStream_t s; const u64* e; long long* h; long long* mb; long long seq;
     ~publish_t() { if (subset) hipLaunchKernelGGL(k_nr_publish, dim3(1), dim3(1), 0, s, e, h, mb, seq); }
-  } publish{subset, s, ctx.nr_edges(), host_flag + 1, ctx.mailbox, seq};
+  } publish{subset, s, ctx.nr_edges(), host_flag + 1, ctx.mailbox.data(), seq};
   if (L.nrs_mu) {
     // the long rows by slice of their destinations + the short rows, one launch; then the fold
     static unsigned char seen_s[64] = {};

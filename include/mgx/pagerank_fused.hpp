@@ -271,13 +271,11 @@ struct pagerank_state_t {
   mem_t<long long> part_cnt;
   mem_t<double> trace;
   mem_t<pagerank_ctrl_t> ctrl;
-  pagerank_ctrl_t* h_ctrl = nullptr; // pinned
+  pinned_t<pagerank_ctrl_t> h_ctrl;
   const float* result = nullptr;     // the last run's ranks by original id (nullptr: no run yet)
   int trace_cap = 0;
   int last_iterations = 0;
 
-  pagerank_state_t(const pagerank_state_t&) = delete;
-  pagerank_state_t& operator=(const pagerank_state_t&) = delete;
   pagerank_state_t(int n_, context_t& ctx) : n(n_) {
     const size_t N = (size_t)std::max(n, 1);
     rank = mem_t<float>(N, ctx);
@@ -286,9 +284,8 @@ struct pagerank_state_t {
     part = mem_t<double>(2 * (size_t)PGR_MAX_PARTIALS, ctx);
     part_cnt = mem_t<long long>((size_t)PGR_MAX_PARTIALS, ctx);
     ctrl = mem_t<pagerank_ctrl_t>(1, ctx);
-    MGX_HIP(hipHostMalloc((void**)&h_ctrl, sizeof(pagerank_ctrl_t), hipHostMallocDefault));
+    h_ctrl = pinned_t<pagerank_ctrl_t>(1);
   }
-  ~pagerank_state_t() { if (h_ctrl) (void)hipHostFree(h_ctrl); }
 
   int update_grid(const standard_context_t& ctx) const { return grid_for(n, BLOCK, std::min(std::max(ctx.num_cus, 1) * 8, PGR_MAX_PARTIALS)); }
 
@@ -323,9 +320,8 @@ struct pagerank_state_t {
   }
   // the control block to the host: one wait
   const pagerank_ctrl_t& look(standard_context_t& ctx) {
-    MGX_HIP(hipMemcpyAsync(h_ctrl, ctrl.data(), sizeof(pagerank_ctrl_t), hipMemcpyDeviceToHost, ctx.stream()));
-    MGX_HIP(hipStreamSynchronize(ctx.stream()));
-    return *h_ctrl;
+    h_ctrl.fetch(ctrl.data(), 1, ctx.stream());
+    return h_ctrl[0];
   }
 
   // iterations to enqueue after a look that found the run unfinished
@@ -413,7 +409,7 @@ struct pagerank_state_t {
       if (c.done || enqueued >= max_iter) break;
       batch = std::min(next_batch(c), max_iter - enqueued);
     }
-    const pagerank_ctrl_t& c = *h_ctrl;
+    const pagerank_ctrl_t& c = h_ctrl[0];
     if (layout) {
       hipLaunchKernelGGL(k_pagerank_unpermute, dim3(grid_n), dim3(BLOCK), 0, st, (const float*)rank.data(), g.old_of_new, rank_orig.data(), n);
       ++out.launches;

@@ -10,6 +10,7 @@
 //   * errors are status codes / exceptions, never exit() (frontier.hxx:53-59).
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -20,6 +21,7 @@
 #include <limits>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -115,164 +117,13 @@ inline void set_current_stream(hipStream_t s) { current_stream_ref() = s; }
 
 // Every write into a frontier's buffer from OUTSIDE an operator (frontier_t::load, the C-ABI's load / fill / fill_iota, a device
 // pointer handed to the caller) moves this counter on: what an operator remembered about a frontier's contents (the advance's
-// keep-ballots for the filter behind it) is only good while it stands still.  Host-side, one per process.
-inline unsigned long long& frontier_generation() {
-  static unsigned long long g = 0;
+// keep-ballots for the filter behind it) is only good while it stands still.  Host-side, one per process: several host threads
+// (the rank threads of a loopback world) move and read it, so it is atomic -- relaxed: it orders nothing, it only has to differ.
+inline std::atomic<unsigned long long>& frontier_generation() {
+  static std::atomic<unsigned long long> g{0};
   return g;
 }
-inline void frontier_touched() { ++frontier_generation(); }
-
-struct standard_context_t : context_t {
-  int device = 0;
-  hipStream_t _stream = nullptr;   // nullptr == the legacy default stream, like the reference
-  bool own_stream = false;
-  // scratch arena (device) -- grows only outside operators
-  void* scratch = nullptr;
-  size_t scratch_bytes = 0;
-  // pinned mailbox for the 8-byte count read-backs (advance.hxx:43, filter.hxx:21).  Device-visible: the kernel that
-  // produces a count stores it here itself (a hipMemcpyAsync D2H of 8 bytes is a blit kernel of its own: ~20 us)
-  long long* mailbox = nullptr;
-  // mailbox[1]: the sequence number of the last count a kernel delivered (scan.hpp).  The host used to wait for the stream
-  // (hipStreamSynchronize: ~10-20 us of runtime wake-up per operator call, two calls per superstep of an enactor) -- now it
-  // spins on this word, which the producing kernel stores at system scope behind the count (mailbox_spin = false: the old wait)
-  long long mailbox_seq = 0;
-  // The scratch arena is shared by every operator of the context; scratch_epoch counts who wrote it.  `keep` is what an advance
-  // left there for the filter behind it (gunrock/advance.hxx -> filter.hxx): the keep-ballots of its output slots, valid only for
-  // that very frontier, iteration and functor, and only while nobody else has touched the arena since.
-  unsigned long long scratch_epoch = 0;
-  struct keep_record_t {
-    const void* data = nullptr;
-    long long n = 0;
-    int iteration = 0;
-    const void* functor = nullptr;
-    unsigned long long epoch = 0;
-    bool valid = false;
-    unsigned long long generation = 0;     // frontier_generation() when the ballots were left
-  } keep;
-  bool mailbox_spin = true;
-  int num_cus = 256;
-  // single-pass scans (scan.hpp): one 64-bit status word per tile, tagged with the launch's epoch so that the array never
-  // needs clearing, and the dynamic tile counter.  Private to those kernels (nothing else writes here: a stale word
-  // can only carry an OLDER epoch).
-  unsigned long long* lookback_status = nullptr;
-  size_t lookback_tiles = 0;
-  unsigned* lookback_ticket = nullptr;      // monotonically increasing across launches; a launch subtracts its base
-  unsigned lookback_ticket_base = 0;        // (host mirror: tickets handed out by the launches enqueued so far)
-  unsigned lookback_epoch = 0;
-  // the neighbour-reduce's verdict word (mgx/nreduce.hpp): lives behind the ticket counter in the same 64-byte allocation,
-  // holds the epoch of the last full-frontier call whose frontier was not the iota (0: none yet)
-  unsigned nr_epoch = 0;
-  unsigned* nr_flag() const { return lookback_ticket + 8; }
-  // ... and behind that the degree sum of the subset frontiers (64 bits at byte 48; only ever added to: nr_edges_base is what it
-  // held before the call in flight)
-  unsigned long long* nr_edges() const { return (unsigned long long*)(lookback_ticket + 12); }
-  unsigned long long nr_edges_base = 0;
-  // what the last neighborhood_kernel call on this context did (gunrock/neighborhood.hxx writes it on the host, behind its own wait;
-  // mgx_graph_nr_last_call reads it).  body: 0 the general LBS kernel, 1 the layout's unit blocks, 2 the layout's sliced long rows;
-  // frontier: 0 other, 1 full, 2 subset (as the host classified it); rejected: the layout's kernels were enqueued but the device's
-  // verdict on the frontier sent the call to the general kernel (body is then 0); edges: what the call returned
-  struct nr_last_call_t {
-    bool valid = false;
-    int body = 0, frontier = 0, rejected = 0;
-    long long edges = 0;
-  } nr_last_call;
-  unsigned next_nr_epoch() {
-    if (++nr_epoch == 0u) nr_epoch = 1u;      // (2^32 calls: a stale word could only name the call 2^32 - 1 before this one)
-    return nr_epoch;
-  }
-
-  explicit standard_context_t(bool print_prop = false, hipStream_t s = nullptr) : _stream(s) {
-    set_current_stream(s);
-    MGX_HIP(hipGetDevice(&device));
-    hipDeviceProp_t prop;
-    MGX_HIP(hipGetDeviceProperties(&prop, device));
-    num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    // MGX_GRID_CUS only ever lowers the count: the "chip-sized" grids (num_cus * 8 workgroups) then run their grid-stride loops
-    // several times on a small test graph -- the carry-over of a wave's stage and every kernel's later iterations
-    if (const char* e = env("MGX_GRID_CUS")) num_cus = (int)std::min<long long>(std::max<long long>(std::atoll(e), 1), num_cus);
-    if (print_prop) std::printf("%s : %d CUs\n", prop.name, num_cus);
-    MGX_HIP(hipHostMalloc((void**)&mailbox, 64 * sizeof(long long), hipHostMallocDefault));
-    for (int i = 0; i < 64; ++i) mailbox[i] = 0;
-    reserve_scratch(1 << 20);
-  }
-  standard_context_t(const standard_context_t&) = delete;
-  standard_context_t& operator=(const standard_context_t&) = delete;
-  ~standard_context_t() override {
-    if (lookback_status) (void)hipFree(lookback_status);
-    if (lookback_ticket) (void)hipFree(lookback_ticket);
-    if (scratch) (void)hipFree(scratch);
-    if (mailbox) (void)hipHostFree(mailbox);
-  }
-  hipStream_t stream() const override { return _stream; }
-  // Work already enqueued by this context is finished first: the scans' look-back tickets and epochs (scan.hpp), the
-  // scratch arena and the mailbox assume that all launches of a context are serialised on ONE stream.
-  void set_stream(hipStream_t s) {
-    if (s != _stream) (void)hipStreamSynchronize(_stream);
-    _stream = s;
-    set_current_stream(s);
-  }
-  void make_current() const { set_current_stream(_stream); }
-  void synchronize() { MGX_HIP(hipStreamSynchronize(_stream)); }
-  // wait for the count a kernel of this context's stream delivers under sequence number `seq` (mailbox[0] then holds it)
-  void mailbox_wait(long long seq) {
-    if (mailbox_spin) {
-      volatile long long* const flag = mailbox + 1;
-      long long spins = 0;
-      while (*flag != seq) {
-        if (++spins > 20000000LL) { MGX_HIP(hipStreamSynchronize(_stream)); break; }      // (a failed launch: let the runtime report it)
-        __builtin_ia32_pause();
-      }
-      __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    } else {
-      MGX_HIP(hipStreamSynchronize(_stream));
-    }
-  }
-
-  // Make sure the arena holds `bytes`.  Called from constructors of graphs,
-  // frontiers and problems -- never from an operator in steady state.
-  void reserve_scratch(size_t bytes) {
-    if (bytes <= scratch_bytes) return;
-    bytes = (bytes + 4095) & ~size_t(4095);
-    // the new arena first: a failed allocation leaves the old one (and its size) in place.  Whatever an operator left in the old
-    // arena for the next one (the advance's keep-ballots, `keep`) is gone with it: the epoch moves on.
-    void* fresh = nullptr;
-    if (scratch) MGX_HIP(hipStreamSynchronize(_stream));
-    if (hipMalloc(&fresh, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      if (scratch) { (void)hipFree(scratch); scratch = nullptr; scratch_bytes = 0; }     // (make room and try once more)
-      MGX_HIP(hipMalloc(&fresh, bytes));
-    } else if (scratch) {
-      MGX_HIP(hipFree(scratch));
-    }
-    scratch = fresh;
-    scratch_bytes = bytes;
-    ++scratch_epoch;
-    keep.valid = false;
-    // status words for a scan over as many items as this arena serves (scan_scratch_bytes: >= n / 8 bytes for n items,
-    // 2048 items per tile)
-    const size_t tiles = bytes / 256 + 64;
-    if (tiles > lookback_tiles) {
-      if (lookback_status) { MGX_HIP(hipStreamSynchronize(_stream)); MGX_HIP(hipFree(lookback_status)); lookback_status = nullptr; }
-      MGX_HIP(hipMalloc((void**)&lookback_status, tiles * sizeof(unsigned long long)));
-      MGX_HIP(hipMemsetAsync(lookback_status, 0, tiles * sizeof(unsigned long long), _stream));
-      lookback_tiles = tiles;
-      lookback_epoch = 0;
-    }
-    if (!lookback_ticket) {
-      MGX_HIP(hipMalloc((void**)&lookback_ticket, 64));
-      MGX_HIP(hipMemsetAsync(lookback_ticket, 0, 64, _stream));
-      lookback_ticket_base = 0;
-    }
-  }
-  // epoch of the next single-pass launch: 1 .. 2^30 - 1, never 0 (cleared words); at wrap-around the words are cleared
-  unsigned next_lookback_epoch() {
-    if (++lookback_epoch >= (1u << 30)) {
-      MGX_HIP(hipMemsetAsync(lookback_status, 0, lookback_tiles * sizeof(unsigned long long), _stream));
-      lookback_epoch = 1;
-    }
-    return lookback_epoch;
-  }
-};
+inline void frontier_touched() { frontier_generation().fetch_add(1, std::memory_order_relaxed); }
 
 // ---------------------------------------------------------------------------
 // mem_t<T>: RAII device array (may also borrow an external device pointer)
@@ -337,6 +188,52 @@ inline hipError_t dtod(T* dst, const T* src, size_t n, hipStream_t s) {
 template <typename T>
 inline hipError_t dtod(T* dst, const T* src, size_t n) { return dtod(dst, src, n, current_stream()); }
 
+// ---------------------------------------------------------------------------
+// pinned_t<T>: RAII pinned host array (device-visible: a kernel may store into it);  event_t: RAII hipEvent_t
+// ---------------------------------------------------------------------------
+template <typename T>
+class pinned_t {
+  T* _ptr = nullptr;
+  size_t _size = 0;
+
+ public:
+  pinned_t() {}
+  explicit pinned_t(size_t count) : _size(count) {
+    if (count) MGX_HIP(hipHostMalloc((void**)&_ptr, count * sizeof(T), hipHostMallocDefault));
+  }
+  pinned_t(const pinned_t&) = delete;
+  pinned_t& operator=(const pinned_t&) = delete;
+  pinned_t(pinned_t&& r) noexcept { swap(r); }
+  pinned_t& operator=(pinned_t&& r) noexcept { swap(r); return *this; }
+  ~pinned_t() { if (_ptr) (void)hipHostFree(_ptr); }
+  void swap(pinned_t& r) noexcept { std::swap(_ptr, r._ptr); std::swap(_size, r._size); }
+  T* data() const { return _ptr; }
+  size_t size() const { return _size; }
+  T& operator[](size_t i) const { return _ptr[i]; }
+  T* operator->() const { return _ptr; }
+  // the read-back of a few words: the copy on `st`, then the wait for `st`
+  void fetch(const T* dev, size_t count, hipStream_t st) { MGX_HIP(dtoh(data(), dev, count, st)); }
+};
+
+class event_t {
+  hipEvent_t _ev = nullptr;
+
+ public:
+  event_t() { MGX_HIP(hipEventCreate(&_ev)); }
+  event_t(const event_t&) = delete;
+  event_t& operator=(const event_t&) = delete;
+  event_t(event_t&& r) noexcept { std::swap(_ev, r._ev); }
+  event_t& operator=(event_t&& r) noexcept { std::swap(_ev, r._ev); return *this; }
+  ~event_t() { if (_ev) (void)hipEventDestroy(_ev); }
+  hipEvent_t get() const { return _ev; }
+  operator hipEvent_t() const { return _ev; }
+};
+
+static_assert(!std::is_copy_constructible<pinned_t<int>>::value && !std::is_copy_assignable<pinned_t<int>>::value &&
+              std::is_nothrow_move_constructible<pinned_t<int>>::value, "pinned_t is move-only");
+static_assert(!std::is_copy_constructible<event_t>::value && !std::is_copy_assignable<event_t>::value &&
+              std::is_nothrow_move_constructible<event_t>::value, "event_t is move-only");
+
 template <typename T>
 inline mem_t<T> to_mem(const std::vector<T>& h, context_t& c) {
   mem_t<T> m(h.size(), c);
@@ -349,6 +246,169 @@ inline std::vector<T> from_mem(const mem_t<T>& m) {
   MGX_HIP(dtoh(h, m.data(), m.size()));
   return h;
 }
+
+struct standard_context_t : context_t {
+  int device = 0;
+  hipStream_t _stream = nullptr;   // nullptr == the legacy default stream, like the reference
+  bool own_stream = false;
+  // scratch arena (device) -- grows only outside operators
+  void* scratch = nullptr;
+  size_t scratch_bytes = 0;
+  // pinned mailbox for the 8-byte count read-backs (advance.hxx:43, filter.hxx:21).  Device-visible: the kernel that
+  // produces a count stores it here itself (a hipMemcpyAsync D2H of 8 bytes is a blit kernel of its own: ~20 us)
+  pinned_t<long long> mailbox;
+  // mailbox[1]: the sequence number of the last count a kernel delivered (scan.hpp).  The host used to wait for the stream
+  // (hipStreamSynchronize: ~10-20 us of runtime wake-up per operator call, two calls per superstep of an enactor) -- now it
+  // spins on this word, which the producing kernel stores at system scope behind the count (mailbox_spin = false: the old wait)
+  long long mailbox_seq = 0;
+  // The scratch arena is shared by every operator of the context; scratch_epoch counts who wrote it.  `keep` is what an advance
+  // left there for the filter behind it (gunrock/advance.hxx -> filter.hxx): the keep-ballots of its output slots, valid only for
+  // that very frontier, iteration and functor, and only while nobody else has touched the arena since.
+  unsigned long long scratch_epoch = 0;
+  struct keep_record_t {
+    const void* data = nullptr;
+    long long n = 0;
+    int iteration = 0;
+    const void* functor = nullptr;
+    unsigned long long epoch = 0;
+    bool valid = false;
+    unsigned long long generation = 0;     // frontier_generation() when the ballots were left
+  } keep;
+  bool mailbox_spin = true;
+  int num_cus = 256;
+  // single-pass scans (scan.hpp): one 64-bit status word per tile, tagged with the launch's epoch so that the array never
+  // needs clearing, and the dynamic tile counter.  Private to those kernels (nothing else writes here: a stale word
+  // can only carry an OLDER epoch).
+  mem_t<unsigned long long> lookback_status;
+  size_t lookback_tiles = 0;
+  mem_t<unsigned> lookback_ticket;          // monotonically increasing across launches; a launch subtracts its base
+  unsigned lookback_ticket_base = 0;        // (host mirror: tickets handed out by the launches enqueued so far)
+  unsigned lookback_epoch = 0;
+  // the neighbour-reduce's verdict word (mgx/nreduce.hpp): lives behind the ticket counter in the same 64-byte allocation,
+  // holds the epoch of the last full-frontier call whose frontier was not the iota (0: none yet)
+  unsigned nr_epoch = 0;
+  unsigned* nr_flag() const { return lookback_ticket.data() + 8; }
+  // ... and behind that the degree sum of the subset frontiers (64 bits at byte 48; only ever added to: nr_edges_base is what it
+  // held before the call in flight)
+  unsigned long long* nr_edges() const { return (unsigned long long*)(lookback_ticket.data() + 12); }
+  unsigned long long nr_edges_base = 0;
+  // what the last neighborhood_kernel call on this context did (gunrock/neighborhood.hxx writes it on the host, behind its own wait;
+  // mgx_graph_nr_last_call reads it).  body: 0 the general LBS kernel, 1 the layout's unit blocks, 2 the layout's sliced long rows;
+  // frontier: 0 other, 1 full, 2 subset (as the host classified it); rejected: the layout's kernels were enqueued but the device's
+  // verdict on the frontier sent the call to the general kernel (body is then 0); edges: what the call returned
+  struct nr_last_call_t {
+    bool valid = false;
+    int body = 0, frontier = 0, rejected = 0;
+    long long edges = 0;
+  } nr_last_call;
+  unsigned next_nr_epoch() {
+    if (++nr_epoch == 0u) nr_epoch = 1u;      // (2^32 calls: a stale word could only name the call 2^32 - 1 before this one)
+    return nr_epoch;
+  }
+
+  explicit standard_context_t(bool print_prop = false, hipStream_t s = nullptr) : _stream(s) {
+    set_current_stream(s);
+    MGX_HIP(hipGetDevice(&device));
+    hipDeviceProp_t prop;
+    MGX_HIP(hipGetDeviceProperties(&prop, device));
+    num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    // MGX_GRID_CUS only ever lowers the count: the "chip-sized" grids (num_cus * 8 workgroups) then run their grid-stride loops
+    // several times on a small test graph -- the carry-over of a wave's stage and every kernel's later iterations
+    if (const char* e = env("MGX_GRID_CUS")) num_cus = (int)std::min<long long>(std::max<long long>(std::atoll(e), 1), num_cus);
+    if (print_prop) std::printf("%s : %d CUs\n", prop.name, num_cus);
+    mailbox = pinned_t<long long>(64);
+    for (int i = 0; i < 64; ++i) mailbox[i] = 0;
+    reserve_scratch(1 << 20);
+  }
+  standard_context_t(const standard_context_t&) = delete;
+  standard_context_t& operator=(const standard_context_t&) = delete;
+  ~standard_context_t() override { if (scratch) (void)hipFree(scratch); }
+  hipStream_t stream() const override { return _stream; }
+  // Work already enqueued by this context is finished first: the scans' look-back tickets and epochs (scan.hpp), the
+  // scratch arena and the mailbox assume that all launches of a context are serialised on ONE stream.
+  void set_stream(hipStream_t s) {
+    if (s != _stream) (void)hipStreamSynchronize(_stream);
+    _stream = s;
+    set_current_stream(s);
+  }
+  void make_current() const { set_current_stream(_stream); }
+  void synchronize() { MGX_HIP(hipStreamSynchronize(_stream)); }
+  // wait for the count a kernel of this context's stream delivers under sequence number `seq` (mailbox[0] then holds it)
+  void mailbox_wait(long long seq) {
+    if (mailbox_spin) {
+      volatile long long* const flag = mailbox.data() + 1;
+      long long spins = 0;
+      while (*flag != seq) {
+        if (++spins > 20000000LL) { MGX_HIP(hipStreamSynchronize(_stream)); break; }      // (a failed launch: let the runtime report it)
+        __builtin_ia32_pause();
+      }
+      __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    } else {
+      MGX_HIP(hipStreamSynchronize(_stream));
+    }
+  }
+
+  // Make sure the arena holds `bytes`.  Called from constructors of graphs,
+  // frontiers and problems -- never from an operator in steady state.
+  void reserve_scratch(size_t bytes) {
+    if (bytes <= scratch_bytes) return;
+    bytes = (bytes + 4095) & ~size_t(4095);
+    // The new arena first: while that allocation is tried the old arena stands untouched.  If it fails, the old arena is freed
+    // to make room and the allocation is tried once more; if that fails too, an arena of the previous size is put back (it was
+    // just freed: there is room) before the error leaves, so that a context does not drop below its constructor's 1 MB floor.
+    // Only if even that fails does the error leave with scratch == nullptr and scratch_bytes == 0.  Whatever an operator left in
+    // the old arena for the next one (the advance's keep-ballots, `keep`) is gone with it: the epoch moves on, and does so as
+    // soon as the old arena is freed, before anything can throw.
+    void* fresh = nullptr;
+    if (scratch) MGX_HIP(hipStreamSynchronize(_stream));
+    hipError_t e = hipMalloc(&fresh, bytes);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      const size_t old_bytes = scratch_bytes;
+      if (scratch) (void)hipFree(scratch);
+      scratch = nullptr;
+      scratch_bytes = 0;
+      ++scratch_epoch;
+      keep.valid = false;
+      e = hipMalloc(&fresh, bytes);
+      if (e != hipSuccess) {
+        (void)hipGetLastError();
+        if (old_bytes && hipMalloc(&scratch, old_bytes) == hipSuccess) scratch_bytes = old_bytes;
+        else scratch = nullptr;
+        throw hip_error(e, "hipMalloc(&fresh, bytes)", __FILE__, __LINE__);
+      }
+    } else if (scratch) {
+      MGX_HIP(hipFree(scratch));
+    }
+    scratch = fresh;
+    scratch_bytes = bytes;
+    ++scratch_epoch;
+    keep.valid = false;
+    // status words for a scan over as many items as this arena serves (scan_scratch_bytes: >= n / 8 bytes for n items,
+    // 2048 items per tile)
+    const size_t tiles = bytes / 256 + 64;
+    if (tiles > lookback_tiles) {
+      if (lookback_status.data()) MGX_HIP(hipStreamSynchronize(_stream));
+      lookback_status = mem_t<unsigned long long>(tiles, *this);
+      MGX_HIP(hipMemsetAsync(lookback_status.data(), 0, tiles * sizeof(unsigned long long), _stream));
+      lookback_tiles = tiles;
+      lookback_epoch = 0;
+    }
+    if (!lookback_ticket.data()) {
+      lookback_ticket = mem_t<unsigned>(16, *this);      // 64 bytes: the ticket, nr_flag() and nr_edges()
+      MGX_HIP(hipMemsetAsync(lookback_ticket.data(), 0, 64, _stream));
+      lookback_ticket_base = 0;
+    }
+  }
+  // epoch of the next single-pass launch: 1 .. 2^30 - 1, never 0 (cleared words); at wrap-around the words are cleared
+  unsigned next_lookback_epoch() {
+    if (++lookback_epoch >= (1u << 30)) {
+      MGX_HIP(hipMemsetAsync(lookback_status.data(), 0, lookback_tiles * sizeof(unsigned long long), _stream));
+      lookback_epoch = 1;
+    }
+    return lookback_epoch;
+  }
+};
 
 // fill / fill_function / transform: generic element kernels -------------------
 template <typename F>

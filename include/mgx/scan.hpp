@@ -201,7 +201,7 @@ inline long long* transform_scan(F f, long long n, int* out, standard_context_t&
   if ((size_t)ntiles > ctx.lookback_tiles || (size_t)(ntiles + 2) * sizeof(long long) > ctx.scratch_bytes)
     throw mgx_error(MGX_E_INVALID, "scan: scratch arena too small (reserve_scratch was not called for this size)");
   hipStream_t st = ctx.stream();
-  long long* const host_slot = host_total ? ctx.mailbox : (long long*)nullptr;
+  long long* const host_slot = host_total ? ctx.mailbox.data() : (long long*)nullptr;
   const long long seq = host_total ? ++ctx.mailbox_seq : 0;
   if (n > 0 && ntiles <= SCAN_LOOKBACK_MAX_TILES) {
     // every tile resident at once: a tile looks back over aggregates that are published as soon as their tiles have
@@ -209,8 +209,8 @@ inline long long* transform_scan(F f, long long n, int* out, standard_context_t&
     // tiles in flight, window by window at ~1 us per dependent cross-XCD poll: the RMAT-22 operator-path traversal
     // went from 2.5 to 2.9 ms with the single pass everywhere.)
     const unsigned epoch = ctx.next_lookback_epoch();
-    hipLaunchKernelGGL(k_scan_lookback<F>, dim3((unsigned)ntiles), dim3(BLOCK), 0, st, f, n, out, ctx.lookback_status,
-                       ctx.lookback_ticket, ctx.lookback_ticket_base, epoch, d_total, host_slot, seq);
+    hipLaunchKernelGGL(k_scan_lookback<F>, dim3((unsigned)ntiles), dim3(BLOCK), 0, st, f, n, out, ctx.lookback_status.data(),
+                       ctx.lookback_ticket.data(), ctx.lookback_ticket_base, epoch, d_total, host_slot, seq);
     ctx.lookback_ticket_base += (unsigned)ntiles;
   } else if (n > 0) {
     hipLaunchKernelGGL(k_scan_tile_sums<F>, dim3((unsigned)ntiles), dim3(BLOCK), 0, st, f, n, partials);
@@ -353,10 +353,10 @@ struct compact_t {
     const unsigned epoch = single ? ctx.next_lookback_epoch() : 0u;
     const long long seq = ++ctx.mailbox_seq;
     hipLaunchKernelGGL((k_compact_upsweep<P, FROM_BITS>), dim3((unsigned)ntiles), dim3(BLOCK), 0, st, pred, n, bits, partials,
-                       single ? ctx.lookback_status : (unsigned long long*)nullptr, ctx.lookback_ticket, ctx.lookback_ticket_base,
-                       epoch, ctx.mailbox, seq);
+                       single ? ctx.lookback_status.data() : (unsigned long long*)nullptr, ctx.lookback_ticket.data(), ctx.lookback_ticket_base,
+                       epoch, ctx.mailbox.data(), seq);
     if (single) ctx.lookback_ticket_base += (unsigned)ntiles;
-    if (!single) hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(BLOCK), 0, st, partials, ntiles, ctx.mailbox, seq);
+    if (!single) hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(BLOCK), 0, st, partials, ntiles, ctx.mailbox.data(), seq);
     MGX_CHECK_LAUNCH("compact: kernel launch");
     ctx.mailbox_wait(seq);
     return ctx.mailbox[0];

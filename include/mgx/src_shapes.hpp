@@ -78,12 +78,8 @@ struct src_shape_cache_t {
   // traversal's launches -- and returns false: THIS traversal gets the graph-wide launch sequence, and collect() behind its final
   // wait (the copy is older than everything the traversal enqueued) puts the shape into the cache for the next call with that source.
   // (A wait here cost a one-call-per-source loop over fresh sources 35 us per call: 0.308 -> 0.344 ms on RMAT-22.)
-  unsigned* pinned = nullptr;          // 4 words, hipHostMalloc
+  pinned_t<unsigned> pinned;           // 16 words (the kernel writes 4), allocated at the first request
   int pending = -1;                    // the source whose shape is on its way
-  ~src_shape_cache_t() { if (pinned) (void)hipHostFree(pinned); }
-  src_shape_cache_t() {}
-  src_shape_cache_t(const src_shape_cache_t&) = delete;
-  src_shape_cache_t& operator=(const src_shape_cache_t&) = delete;
   bool lookup_or_request(const int* ro, const int* ci, int n, int lm, int src, std::vector<unsigned>& table, standard_context_t& ctx) {
     if (lm != long_min) { seen.clear(); long_min = lm; pending = -1; }
     table.assign(4, 0u);
@@ -91,16 +87,16 @@ struct src_shape_cache_t {
     if (src < 0 || src >= n) return true;                         // (classifies as "unknown")
     auto it = seen.find(src);
     if (it != seen.end()) { for (int q = 0; q < 4; ++q) table[(size_t)q] = it->second[(size_t)q]; return true; }
-    if (!pinned) MGX_HIP(hipHostMalloc((void**)&pinned, 64, hipHostMallocDefault));
+    if (!pinned.data()) pinned = pinned_t<unsigned>(16);
     // (the kernel stores straight into the pinned words: no copy of its own on the stream)
-    hipLaunchKernelGGL(k_src_shapes_one, dim3(1), dim3(64), 0, ctx.stream(), ro, ci, lm, src, (uint4*)pinned);
+    hipLaunchKernelGGL(k_src_shapes_one, dim3(1), dim3(64), 0, ctx.stream(), ro, ci, lm, src, (uint4*)pinned.data());
     pending = src;
     ++launches;
     return false;
   }
   // behind a wait for the stream's work enqueued AFTER lookup_or_request: the requested shape has arrived
   void collect() {
-    if (pending < 0 || !pinned) return;
+    if (pending < 0 || !pinned.data()) return;
     if (seen.size() > (1u << 20)) seen.clear();
     seen[pending] = {pinned[0], pinned[1], pinned[2], pinned[3]};
     pending = -1;

@@ -48,12 +48,7 @@ struct dsssp_state_t {
   mem_t<unsigned long long> counters;   // [0..ranks) bin counts, [ranks] next-frontier cursor
   long long bin_cap = 0, frontier_size = 0;
   int cur = 0;
-  unsigned long long* host_counters = nullptr;
-
-  dsssp_state_t() {}
-  dsssp_state_t(const dsssp_state_t&) = delete;
-  dsssp_state_t& operator=(const dsssp_state_t&) = delete;
-  ~dsssp_state_t() { if (host_counters) (void)hipHostFree(host_counters); }
+  pinned_t<unsigned long long> host_counters;
 
   void init(standard_context_t& ctx, int n_global_, int v_lo_, int v_hi_, int ranks_, int rank_, const int* ro, const int* ci,
             const float* w, long long m_local_) {
@@ -71,7 +66,7 @@ struct dsssp_state_t {
     send_ids = mem_t<int>((size_t)ranks * (size_t)bin_cap + 1, ctx);
     bins = mem_t<unsigned long long>((size_t)ranks * (size_t)bin_cap + 1, ctx);
     counters = mem_t<unsigned long long>((size_t)ranks + 1, ctx);
-    MGX_HIP(hipHostMalloc((void**)&host_counters, (ranks + 1) * sizeof(unsigned long long), hipHostMallocDefault));
+    host_counters = pinned_t<unsigned long long>((size_t)ranks + 1);
     ctx.reserve_scratch(scan_scratch_bytes(n_local) + (1 << 16));
   }
 };
@@ -175,8 +170,7 @@ inline void dsssp_expand(dsssp_state_t& st, standard_context_t& ctx, long long* 
         },
         (long long)ranks * cap, ctx);
   }
-  MGX_HIP(hipMemcpyAsync(st.host_counters, cnt, (size_t)ranks * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  MGX_HIP(hipStreamSynchronize(s));
+  st.host_counters.fetch(cnt, (size_t)ranks, s);
   if (edges_out) *edges_out = front;
 }
 
@@ -203,7 +197,7 @@ inline void dsssp_receive(dsssp_state_t& st, const unsigned long long* pairs, lo
 // next frontier becomes current; returns its size
 inline long long dsssp_swap(dsssp_state_t& st, standard_context_t& ctx) {
   hipStream_t s = ctx.stream();
-  MGX_HIP(hipMemcpyAsync(st.host_counters + st.ranks, st.counters.data() + st.ranks, sizeof(unsigned long long),
+  MGX_HIP(hipMemcpyAsync(st.host_counters.data() + st.ranks, st.counters.data() + st.ranks, sizeof(unsigned long long),
                          hipMemcpyDeviceToHost, s));
   MGX_HIP(hipMemsetAsync(st.counters.data() + st.ranks, 0, sizeof(unsigned long long), s));
   MGX_HIP(hipStreamSynchronize(s));
@@ -222,18 +216,13 @@ struct dsssp_run_bufs_t {
   mem_t<unsigned long long> matrix;     // R x R bin counts (row = sender), then R frontier sizes
   mem_t<unsigned long long> recv;       // what the other ranks send in a superstep: at most bin_cap pairs each
   mem_t<unsigned long long> mine;       // my row of counters / my frontier size, as the all-gathers' send buffer
-  unsigned long long* host_matrix = nullptr;
-  dsssp_run_bufs_t() {}
-  dsssp_run_bufs_t(const dsssp_run_bufs_t&) = delete;
-  dsssp_run_bufs_t& operator=(const dsssp_run_bufs_t&) = delete;
-  ~dsssp_run_bufs_t() { if (host_matrix) (void)hipHostFree(host_matrix); }
+  pinned_t<unsigned long long> host_matrix;
   void ensure(const dsssp_state_t& st, standard_context_t& ctx) {
     const size_t R = (size_t)st.ranks;
     if (matrix.size() < R * R + R) {
       matrix = mem_t<unsigned long long>(R * R + R, ctx);
       mine = mem_t<unsigned long long>(R + 1, ctx);
-      if (host_matrix) (void)hipHostFree(host_matrix);
-      MGX_HIP(hipHostMalloc((void**)&host_matrix, (R * R + R) * sizeof(unsigned long long), hipHostMallocDefault));
+      host_matrix = pinned_t<unsigned long long>(R * R + R);
     }
     const size_t want = R > 1 ? (R - 1) * (size_t)st.bin_cap + 1 : 1;
     if (recv.size() < want) recv = mem_t<unsigned long long>(want, ctx);
@@ -256,10 +245,9 @@ inline void dsssp_run(dsssp_state_t& st, comm_t& cm, dsssp_run_bufs_t& bufs, int
     relaxed += edges;
     if (coll) {
       st.host_counters[me] = 0;                       // (a rank never bins its own vertices: expand relaxed them)
-      MGX_HIP(hipMemcpyAsync(bufs.mine.data(), st.host_counters, (size_t)R * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+      MGX_HIP(hipMemcpyAsync(bufs.mine.data(), st.host_counters.data(), (size_t)R * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
       MGX_RCCL(api.AllGather(bufs.mine.data(), bufs.matrix.data(), (size_t)R, ncclUint64, cm.comm, s));
-      MGX_HIP(hipMemcpyAsync(bufs.host_matrix, bufs.matrix.data(), (size_t)R * R * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-      MGX_HIP(hipStreamSynchronize(s));
+      bufs.host_matrix.fetch(bufs.matrix.data(), (size_t)R * R, s);
       std::vector<long long> from(R, 0);
       long long total = 0;
       for (int r = 0; r < R; ++r) {
@@ -287,10 +275,9 @@ inline void dsssp_run(dsssp_state_t& st, comm_t& cm, dsssp_run_bufs_t& bufs, int
     ++supersteps;
     if (coll) {
       bufs.host_matrix[(size_t)R * R] = (unsigned long long)nf;
-      MGX_HIP(hipMemcpyAsync(bufs.mine.data() + R, bufs.host_matrix + (size_t)R * R, sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+      MGX_HIP(hipMemcpyAsync(bufs.mine.data() + R, bufs.host_matrix.data() + (size_t)R * R, sizeof(unsigned long long), hipMemcpyHostToDevice, s));
       MGX_RCCL(api.AllGather(bufs.mine.data() + R, bufs.matrix.data() + (size_t)R * R, 1, ncclUint64, cm.comm, s));
-      MGX_HIP(hipMemcpyAsync(bufs.host_matrix, bufs.matrix.data() + (size_t)R * R, (size_t)R * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-      MGX_HIP(hipStreamSynchronize(s));
+      bufs.host_matrix.fetch(bufs.matrix.data() + (size_t)R * R, (size_t)R, s);
       nf = 0;
       for (int r = 0; r < R; ++r) nf += (long long)bufs.host_matrix[r];
     }

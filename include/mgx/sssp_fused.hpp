@@ -909,13 +909,13 @@ struct sssp_fused_state_t {
   mem_t<u32> frontier_bits;          // the frontier as a bitmap (the sweep; allocated on demand)
   unsigned dense_div = 4;            // an iteration whose frontier holds >= m / dense_div edges sweeps the unit blocks (sssp_dense_*; 0: never)
   mem_t<bfs_ctrl_t> ctrl;
-  bfs_ctrl_t* host_ctrl = nullptr;
+  pinned_t<bfs_ctrl_t> host_ctrl;
   int n = 0;
   int iters_hint = 12;
   float delta = 0.f;                 // near / far bucket width (0: off) (mgx_sssp_run_delta)
   // per-launch timing of k_sssp_relax (measurement runs: mgx_sssp_set_kernel_timing; an event costs ~6 us of stream gap)
   bool time_kernels = false;
-  std::vector<hipEvent_t> ev;        // pairs around the relax launches of a batch, made on demand
+  std::vector<event_t> ev;           // pairs around the relax launches of a batch, made on demand
   double relax_ms = 0.0;             // of the last run
   long long relax_launches = 0;
   sssp_fused_state_t(int num_nodes, standard_context_t& ctx) : n(num_nodes) {
@@ -927,13 +927,7 @@ struct sssp_fused_state_t {
       q_du[i] = mem_t<u32>((size_t)num_nodes + 1, ctx);
     }
     ctrl = mem_t<bfs_ctrl_t>(1, ctx);
-    MGX_HIP(hipHostMalloc((void**)&host_ctrl, sizeof(bfs_ctrl_t), hipHostMallocDefault));
-  }
-  sssp_fused_state_t(const sssp_fused_state_t&) = delete;
-  sssp_fused_state_t& operator=(const sssp_fused_state_t&) = delete;
-  ~sssp_fused_state_t() {
-    if (host_ctrl) (void)hipHostFree(host_ctrl);
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    host_ctrl = pinned_t<bfs_ctrl_t>(1);
   }
 };
 
@@ -1002,7 +996,7 @@ inline void sssp_fused_run(sssp_fused_state_t& st, const int* row_offsets, const
   for (int batch = 0;; ++batch) {
     const int nit = batch == 0 ? st.iters_hint : 2;
     if (st.time_kernels)
-      while ((int)st.ev.size() < 2 * nit) { hipEvent_t e; MGX_HIP(hipEventCreate(&e)); st.ev.push_back(e); }
+      while ((int)st.ev.size() < 2 * nit) st.ev.emplace_back();
     for (int i = 0; i < nit; ++i, ++it) {
       if (st.time_kernels) MGX_HIP(hipEventRecord(st.ev[2 * i], s));
       hipLaunchKernelGGL(k_sssp_relax<1024>, dim3(ctx.num_cus * 2), dim3(1024), SSSP_HOTN * 2, s, a, it);
@@ -1012,7 +1006,7 @@ inline void sssp_fused_run(sssp_fused_state_t& st, const int* row_offsets, const
       else hipLaunchKernelGGL(k_sssp_build<512>, dim3(bfs_build_grid(st.n, 512)), dim3(512), 0, s, a, it);
     }
     MGX_CHECK_LAUNCH("fused SSSP: kernel launch");
-    MGX_HIP(hipMemcpyAsync(st.host_ctrl, st.ctrl.data(), offsetof(bfs_ctrl_t, trace) + 64 * sizeof(u64), hipMemcpyDeviceToHost, s));
+    MGX_HIP(hipMemcpyAsync(st.host_ctrl.data(), st.ctrl.data(), offsetof(bfs_ctrl_t, trace) + 64 * sizeof(u64), hipMemcpyDeviceToHost, s));
     MGX_HIP(hipStreamSynchronize(s));
     for (int i = 0; st.time_kernels && i < nit; ++i) {
       float ms = 0.f;

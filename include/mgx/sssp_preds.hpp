@@ -114,10 +114,9 @@ struct sssp_pred_state_t {
   mem_t<unsigned short> done;
   mem_t<u32> wl;
   mem_t<unsigned long long> counters;     // [0] work-list count, [1] (as int) changed
-  unsigned long long* host = nullptr;     // pinned copy of the two
+  pinned_t<unsigned long long> host;      // pinned copy of the two (allocated at the first call)
   long long last_ties = 0;                // equal-distance tight edges pass 1 found
   int last_rounds = 0;                    // rounds the last call needed (1: pass 1 alone)
-  ~sssp_pred_state_t() { if (host) (void)hipHostFree(host); }
 };
 
 // pred[] (n ints, original ids like dist[]) from the final distances.  Synchronises.
@@ -128,7 +127,7 @@ inline void sssp_build_preds(sssp_pred_state_t& st, const int* row_offsets, cons
   unsigned long long cap = (unsigned long long)m / 8ull + 4096ull;
   if (st.wl.size() < 2 * cap) st.wl = mem_t<u32>((size_t)(2 * cap), ctx);
   if (!st.counters.size()) st.counters = mem_t<unsigned long long>(2, ctx);
-  if (!st.host) MGX_HIP(hipHostMalloc((void**)&st.host, 64, hipHostMallocDefault));
+  if (!st.host.data()) st.host = pinned_t<unsigned long long>(8);
   pred_args_t a;
   a.row_offsets = row_offsets; a.col_indices = col_indices; a.weights = weights; a.dist = dist; a.pred = pred; a.done = st.done.data();
   a.n = n; a.m = m; a.src = src; a.wl = st.wl.data(); a.wl_count = st.counters.data(); a.wl_cap = cap;
@@ -139,8 +138,7 @@ inline void sssp_build_preds(sssp_pred_state_t& st, const int* row_offsets, cons
   if (m > 0) hipLaunchKernelGGL(k_sssp_pred_edges<true>, dim3(grid), dim3(BLOCK), 0, s, a, 1);
   hipLaunchKernelGGL(k_sssp_pred_mark, dim3(grid_for(n, BLOCK, 1 << 30)), dim3(BLOCK), 0, s, a);
   MGX_CHECK_LAUNCH("SSSP predecessors: kernel launch");
-  MGX_HIP(hipMemcpyAsync(st.host, st.counters.data(), 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  MGX_HIP(hipStreamSynchronize(s));
+  st.host.fetch(st.counters.data(), 2, s);
   const unsigned long long ties = st.host[0];
   st.last_ties = (long long)ties;
   st.last_rounds = 1;
@@ -151,10 +149,9 @@ inline void sssp_build_preds(sssp_pred_state_t& st, const int* row_offsets, cons
     if (from_list) hipLaunchKernelGGL(k_sssp_pred_round, dim3(grid_for((long long)ties, BLOCK, ctx.num_cus * 8)), dim3(BLOCK), 0, s, a, ties, round);
     else hipLaunchKernelGGL(k_sssp_pred_edges<false>, dim3(grid), dim3(BLOCK), 0, s, a, round);
     MGX_CHECK_LAUNCH("SSSP predecessors: tie round launch");
-    MGX_HIP(hipMemcpyAsync(st.host, st.counters.data(), 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    MGX_HIP(hipStreamSynchronize(s));
+    st.host.fetch(st.counters.data(), 2, s);
     st.last_rounds = round;
-    if (*(const int*)(st.host + 1) == 0) return;
+    if (*(const int*)(st.host.data() + 1) == 0) return;
   }
   // 65 533 rounds and still assigning: a chain of equal-distance vertices longer than the round stamps count.  The preds assigned
   // so far are a forest of valid tight edges; say so rather than return a partial answer silently.

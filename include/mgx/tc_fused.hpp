@@ -514,21 +514,18 @@ struct tc_state_t {
   tc_opts_t opts;
   tc_dag_t dag[2];                  // [symmetric]
   mem_t<u64> tri;
-  u64* h_pinned = nullptr;
+  pinned_t<u64> h_pinned;
   int last = -1;                    // the DAG of the last run (-1: no run yet)
   long long launches = 0;
   long long waits = 0;              // host waits of the run in progress: counted where the host waits, not stated
 
-  tc_state_t(const tc_state_t&) = delete;
-  tc_state_t& operator=(const tc_state_t&) = delete;
   tc_state_t(int n_, long long m_, standard_context_t& ctx) : n(n_), m(m_), opts(tc_opts_t::from_env()) {
     // (the merge passes of the sort run for rows of up to m entries at run widths w with 2 w an int)
     if (m > (1LL << 30)) throw mgx_error(MGX_E_FRONTIER_OVERFLOW, "mgx tc: more than 2^30 CSR entries");
     tri = mem_t<u64>((size_t)std::max(n, 1), ctx);
-    MGX_HIP(hipHostMalloc((void**)&h_pinned, TC_S_WORDS * sizeof(u64), hipHostMallocDefault));
+    h_pinned = pinned_t<u64>(TC_S_WORDS);
     ctx.reserve_scratch(scan_scratch_bytes((long long)n + 1));
   }
-  ~tc_state_t() { if (h_pinned) (void)hipHostFree(h_pinned); }
 
   template <typename F>
   void scan(F f, int* out, standard_context_t& ctx) {
@@ -643,8 +640,7 @@ struct tc_state_t {
   // the stat words of d to the host: THE host wait.  Throws when the build's size check failed.
   void read_stats(tc_dag_t& d, bool built_now, standard_context_t& ctx) {
     const hipStream_t st = ctx.stream();
-    MGX_HIP(hipMemcpyAsync(h_pinned, d.stat.data(), TC_S_WORDS * sizeof(u64), hipMemcpyDeviceToHost, st));
-    MGX_HIP(hipStreamSynchronize(st));
+    h_pinned.fetch(d.stat.data(), TC_S_WORDS, st);
     ++waits;
     for (int i = 0; i < TC_S_WORDS; ++i) d.h[i] = (long long)h_pinned[i];
     if (d.h[TC_S_ERR]) {

@@ -301,12 +301,8 @@ static void ensure_nr_slices(mgx_graph_s* g) {
   ctx.synchronize();
   const int rc = mgx_nrs_build_device(G.d_layout_row_offsets.data(), G.d_layout_col_indices.data(), rows, S, slices, &mu, &off, first, &total,
                                       ctx.stream());
-  if (rc != 0) {                       // (the memory is not there: the unit blocks serve -- the call that asked is not failed for it)
-    (void)hipGetLastError();
-    if (mu) (void)hipFree(mu);
-    if (off) (void)hipFree(off);
-    return;
-  }
+  // (the builder hands arrays back only when it succeeds with total > 0: NULL in both on every other way out)
+  if (rc != 0) { (void)hipGetLastError(); return; }      // (the memory is not there: the unit blocks serve -- the call that asked is not failed for it)
   if (total <= 0 || !mu || !off) return;
   G.d_nrs_mu = mem_t<unsigned>::adopt((unsigned*)mu, ((size_t)total + 4) * 4);
   G.d_nrs_off = mem_t<unsigned>::adopt(off, (size_t)(slices + 1) * (size_t)rows + 1);
@@ -1652,7 +1648,7 @@ int mgx_dbfs2_cold_levels(mgx_dbfs2_t h, int64_t* levels, int64_t* pairs) {
 int mgx_dbfs2_path_levels(mgx_dbfs2_t h, int64_t* out4) {
   MGX_TRY
   MGX_REQUIRE(h && out4, "NULL argument");
-  const mgx::bfs_ctrl_t* hc = h->st.fs->host_ctrl;          // (as of the last mgx_dbfs2_status / mgx_dbfs2_run)
+  const mgx::bfs_ctrl_t* hc = h->st.fs->host_ctrl.data();          // (as of the last mgx_dbfs2_status / mgx_dbfs2_run)
   out4[0] = (int64_t)hc->small_levels;                       // levels whose push appended its discoveries to the id list itself
   out4[1] = (int64_t)hc->vshort_slots;                       // levels whose short rows were walked vertex by vertex
   out4[2] = (int64_t)hc->d2_declared_level >= 0 ? 1 : 0;     // a sweep declared its list overflowed (the last such level is kept, not a count)
@@ -2130,7 +2126,7 @@ int mgx_sssp_iteration_trace(mgx_sssp_t p, int cap, int64_t* frontier, int64_t* 
   MGX_TRY
   MGX_REQUIRE(p && iterations, "NULL argument");
   MGX_REQUIRE(p->fused != nullptr, "mgx_sssp_iteration_trace: no mgx_sssp_run yet");
-  const mgx::bfs_ctrl_t* hc = p->fused->host_ctrl;
+  const mgx::bfs_ctrl_t* hc = p->fused->host_ctrl.data();
   const int it = hc->levels < 63 ? hc->levels : 63;
   *iterations = hc->levels;
   for (int i = 0; i < it && i < cap; ++i) {

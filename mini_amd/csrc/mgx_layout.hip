@@ -25,6 +25,8 @@ struct tmp_t {
   hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
   ~tmp_t() { if (p) (void)hipFree(p); }
   template <typename T> T* as() const { return (T*)p; }
+  // hand the array to the caller (a builder's out-parameter, on its success path alone)
+  template <typename T> T* release() { T* q = (T*)p; p = nullptr; return q; }
 };
 
 #define LAY_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return (int)e_; } while (0)
@@ -211,26 +213,19 @@ extern "C" int mgx_units_build_device(const int* ro, const int* ci, int n, int m
   const int tot = (int)U;
   LAY_TRY(hipMemcpyAsync(uoff.as<int>() + n, &tot, 4, hipMemcpyHostToDevice, stream));
   const long long Up = (U + 15) / 16 * 16;
-  LAY_TRY(hipMalloc((void**)owner, (size_t)Up * 4));
-  hipError_t e = hipMalloc((void**)ucol, (((size_t)Up << ushift) + 4) * 4);
-  if (e != hipSuccess) { (void)hipFree(*owner); *owner = nullptr; return (int)e; }
-  e = hipMalloc((void**)ucnt, (size_t)Up + 16);
-  if (e == hipSuccess) e = hipMalloc((void**)ufirst, ((size_t)n + 1) * 4);
-  if (e != hipSuccess) {
-    (void)hipFree(*owner); (void)hipFree(*ucol); if (*ucnt) (void)hipFree(*ucnt);
-    *owner = nullptr; *ucol = nullptr; *ucnt = nullptr; *ufirst = nullptr;
-    return (int)e;
-  }
-  hipLaunchKernelGGL(k_unit_fill, dim3(4096), dim3(256), 0, stream, ro, ci, n, uoff.as<int>(), ushift, hot_limit, *owner, *ucol, *ucnt);
+  tmp_t own, col, ucn, fst;                               // (the out-parameters stay NULL unless everything below succeeds)
+  LAY_TRY(own.alloc((size_t)Up * 4));
+  LAY_TRY(col.alloc((((size_t)Up << ushift) + 4) * 4));
+  LAY_TRY(ucn.alloc((size_t)Up + 16));
+  LAY_TRY(fst.alloc(((size_t)n + 1) * 4));
+  hipLaunchKernelGGL(k_unit_fill, dim3(4096), dim3(256), 0, stream, ro, ci, n, uoff.as<int>(), ushift, hot_limit, own.as<int>(), col.as<int>(),
+                     ucn.as<unsigned char>());
   const long long tail = ((Up - U) << ushift) + 4;
-  hipLaunchKernelGGL(k_unit_tail, dim3((unsigned)((tail + 255) / 256)), dim3(256), 0, stream, n, (int)U, (int)Up, ushift, *owner, *ucol, *ucnt);
-  (void)hipMemcpyAsync(*ufirst, uoff.as<int>(), ((size_t)n + 1) * 4, hipMemcpyDeviceToDevice, stream);
-  e = hipStreamSynchronize(stream);                       // (tot lives on this frame)
-  if (e != hipSuccess) {
-    (void)hipFree(*owner); (void)hipFree(*ucol); (void)hipFree(*ucnt); (void)hipFree(*ufirst);
-    *owner = nullptr; *ucol = nullptr; *ucnt = nullptr; *ufirst = nullptr;
-    return (int)e;
-  }
+  hipLaunchKernelGGL(k_unit_tail, dim3((unsigned)((tail + 255) / 256)), dim3(256), 0, stream, n, (int)U, (int)Up, ushift, own.as<int>(),
+                     col.as<int>(), ucn.as<unsigned char>());
+  (void)hipMemcpyAsync(fst.p, uoff.as<int>(), ((size_t)n + 1) * 4, hipMemcpyDeviceToDevice, stream);
+  LAY_TRY(hipStreamSynchronize(stream));                  // (tot lives on this frame)
+  *owner = own.release<int>(); *ucol = col.release<int>(); *ucnt = ucn.release<unsigned char>(); *ufirst = fst.release<int>();
   *units = U; *units_pad = Up;
   return 0;
 }
@@ -322,13 +317,14 @@ extern "C" int mgx_cold_build_device(const int* ro, const int* ci, int n, int ro
   const long long E = (long long)last_off + last_cnt;
   slice_off[slices] = (int)E;
   if (E <= 0) return 0;
-  LAY_TRY(hipMalloc((void**)owner, ((size_t)E + 256) * 4));
-  hipError_t e = hipMalloc((void**)dst, ((size_t)E + 256) * 4);
-  if (e != hipSuccess) { (void)hipFree(*owner); *owner = nullptr; return (int)e; }
-  hipLaunchKernelGGL(k_cold_fill, dim3(2048), dim3(256), 0, stream, ro, ci, row0, rows, cnt.as<int>(), off.as<int>(), slices, *owner, *dst);
-  hipLaunchKernelGGL(k_cold_pad, dim3(1), dim3(256), 0, stream, (int)E, 256, n, *owner, *dst);
-  e = hipStreamSynchronize(stream);
-  if (e != hipSuccess) { (void)hipFree(*owner); (void)hipFree(*dst); *owner = nullptr; *dst = nullptr; return (int)e; }
+  tmp_t own, to;
+  LAY_TRY(own.alloc(((size_t)E + 256) * 4));
+  LAY_TRY(to.alloc(((size_t)E + 256) * 4));
+  hipLaunchKernelGGL(k_cold_fill, dim3(2048), dim3(256), 0, stream, ro, ci, row0, rows, cnt.as<int>(), off.as<int>(), slices, own.as<int>(),
+                     to.as<int>());
+  hipLaunchKernelGGL(k_cold_pad, dim3(1), dim3(256), 0, stream, (int)E, 256, n, own.as<int>(), to.as<int>());
+  LAY_TRY(hipStreamSynchronize(stream));
+  *owner = own.release<int>(); *dst = to.release<int>();
   *pairs = E;
   return 0;
 }
@@ -384,18 +380,17 @@ extern "C" int mgx_cold_pack_device(const int* owner, const int* dst, int used, 
   for (int q = used; q < 64; ++q) P.lo[q] = 0;
   const unsigned total = off[used];
   if (total == 0u) return 0;
-  tmp_t bad;
+  tmp_t bad, packed, cb;
   LAY_TRY(bad.alloc(8));
   LAY_TRY(hipMemsetAsync(bad.p, 0, 8, stream));
-  LAY_TRY(hipMalloc((void**)pk, ((size_t)total + 256) * 4));
-  hipError_t e = hipMalloc((void**)cbase, ((size_t)acc + 64) * 4);
-  if (e != hipSuccess) { (void)hipFree(*pk); *pk = nullptr; return (int)e; }
-  (void)hipMemsetAsync(*cbase, 0, ((size_t)acc + 64) * 4, stream);
-  hipLaunchKernelGGL(k_cold_pack, dim3(4096), dim3(256), 0, stream, owner, dst, P, *pk, *cbase, bad.as<unsigned>());
+  LAY_TRY(packed.alloc(((size_t)total + 256) * 4));
+  LAY_TRY(cb.alloc(((size_t)acc + 64) * 4));
+  (void)hipMemsetAsync(cb.p, 0, ((size_t)acc + 64) * 4, stream);
+  hipLaunchKernelGGL(k_cold_pack, dim3(4096), dim3(256), 0, stream, owner, dst, P, packed.as<unsigned>(), cb.as<unsigned>(), bad.as<unsigned>());
   unsigned hb[2] = {0, 0};
-  e = hipMemcpyAsync(hb, bad.p, 8, hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (e != hipSuccess) { (void)hipFree(*pk); (void)hipFree(*cbase); *pk = nullptr; *cbase = nullptr; return (int)e; }
+  LAY_TRY(hipMemcpyAsync(hb, bad.p, 8, hipMemcpyDeviceToHost, stream));
+  LAY_TRY(hipStreamSynchronize(stream));
+  *pk = packed.release<unsigned>(); *cbase = cb.release<unsigned>();
   const unsigned long long badmask = (unsigned long long)hb[0] | ((unsigned long long)hb[1] << 32);
   const unsigned long long all = used == 64 ? ~0ull : ((1ull << used) - 1ull);
   *mask = all & ~badmask;
@@ -867,10 +862,11 @@ extern "C" int mgx_nrs_build_device(const int* ro, const int* ci, int rows, unsi
   for (int k = 0; k <= slices + 1; ++k) first[k] = 0u;
   if (rows <= 0 || slices <= 0 || slice_n == 0u || slice_n > 65535u) return 0;
   const size_t cells = (size_t)(slices + 1) * (size_t)rows;
-  tmp_t cnt, st;
-  unsigned* offs = nullptr;
+  tmp_t cnt, st, offs_t, units;
   LAY_TRY(cnt.alloc((cells + 1) * 4));
-  LAY_TRY(hipMalloc((void**)&offs, (cells + 1) * 4));
+  LAY_TRY(offs_t.alloc((cells + 1) * 4));
+  unsigned* const offs = offs_t.as<unsigned>();
+  auto none = [&](int rc) { for (int k = 0; k <= slices + 1; ++k) first[k] = 0u; return rc; };      // (every way out without slices)
   hipLaunchKernelGGL(k_nrs_counts, dim3((unsigned)((cells + 1 + 255) / 256)), dim3(256), 0, stream, ro, ci, rows, slice_n, slices,
                      cnt.as<unsigned>());
   // (64-bit sums would be needed past 2^32 mini-units: the entries are fewer than 2^31, a mini-unit holds at least one)
@@ -882,15 +878,14 @@ extern "C" int mgx_nrs_build_device(const int* ro, const int* ci, int rows, unsi
     e = hipMemcpyAsync(first + k, offs + (size_t)k * rows, 4, hipMemcpyDeviceToHost, stream);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
   const unsigned M = first[slices + 1];
-  if (e != hipSuccess || M == 0u || M >= (1u << 31)) { (void)hipFree(offs); for (int k = 0; k <= slices + 1; ++k) first[k] = 0u; return (int)e; }
-  void* units = nullptr;
-  e = hipMalloc(&units, ((size_t)M + 4) * 16);
-  if (e != hipSuccess) { (void)hipFree(offs); for (int k = 0; k <= slices + 1; ++k) first[k] = 0u; (void)hipGetLastError(); return 0; }   // (no memory: no slices)
-  hipLaunchKernelGGL(k_nrs_fill, dim3(8192), dim3(256), 0, stream, ro, ci, rows, slice_n, slices, (const unsigned*)offs, M, (uint4*)units);
-  e = hipMemsetAsync((char*)units + (size_t)M * 16, 0xFF, 64, stream);
+  if (e != hipSuccess || M == 0u || M >= (1u << 31)) return none((int)e);
+  e = units.alloc(((size_t)M + 4) * 16);
+  if (e != hipSuccess) { (void)hipGetLastError(); return none(0); }   // (no memory: no slices)
+  hipLaunchKernelGGL(k_nrs_fill, dim3(8192), dim3(256), 0, stream, ro, ci, rows, slice_n, slices, (const unsigned*)offs, M, units.as<uint4>());
+  e = hipMemsetAsync(units.as<char>() + (size_t)M * 16, 0xFF, 64, stream);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (e != hipSuccess) { (void)hipFree(offs); (void)hipFree(units); for (int k = 0; k <= slices + 1; ++k) first[k] = 0u; return (int)e; }
-  *mu = units; *off = offs; *total = (long long)M;
+  if (e != hipSuccess) return none((int)e);
+  *mu = units.release<void>(); *off = offs_t.release<unsigned>(); *total = (long long)M;
   return 0;
 }
 
