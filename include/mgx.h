@@ -49,6 +49,7 @@ typedef struct mgx_tc_s* mgx_tc_t;
 typedef struct mgx_bc_s* mgx_bc_t;
 typedef struct mgx_pagerank_s* mgx_pagerank_t;
 typedef struct mgx_mst_s* mgx_mst_t;
+typedef struct mgx_ktruss_s* mgx_ktruss_t;
 typedef struct mgx_dbfs_s* mgx_dbfs_t;
 typedef struct mgx_dbfs2_s* mgx_dbfs2_t;
 typedef struct mgx_dsssp_s* mgx_dsssp_t;
@@ -761,6 +762,50 @@ MGX_API int mgx_mst_labels_device(mgx_mst_t p, const int** d_labels);
  * items (a lane each), [2] MGX_MST_LONG_MIN in effect, [3] MGX_MST_SEG in effect, [4] merge passes of the setup sort, [5] 1 if the
  * setup was reused, [6] [7] 0 */
 MGX_API int mgx_mst_info(mgx_mst_t p, int64_t* out8);
+
+/* ---- k-truss decomposition (include/mgx/ktruss_fused.hpp, include/gunrock/ktruss/) ----
+ * The graph is the underlying simple undirected graph of the triangle count (self-loops and duplicate entries change nothing,
+ * original ids, `symmetric` as in mgx_tc_run).  Its edges are the entries of the oriented graph that count builds: edge e joins
+ * src[e] to dst[e], stats[1] of them.  sup0[e] = the triangles that contain e; truss[e] = the largest k such that e lies in a
+ * subgraph whose every edge is in at least k - 2 of its triangles (an edge without triangles: 2); vtruss[v] = the largest trussness
+ * of an edge at v (0: none); hist[k] = edges of trussness k.  Both paths and tests/ktruss_model.py peel by the same simultaneous
+ * rule, so supports after every pass, levels and passes are unique.
+ * stats (may be NULL), int64[8]: [0] largest trussness (0 without edges), [1] edges, [2] triangles, [3] levels (values of k that had
+ * a front), [4] passes, [5] 1 if this run built the oriented graph and the adjacency with edge ids (kept per `symmetric` on the
+ * handle), [6] host waits the run made, counted where the host waits (the first run's include the builds': the oriented graph's
+ * stats, the adjacency's size check, the two of the sort's host side; operator path: one per operator call), [7] launches (fused:
+ * the idle ones behind the run's end included; the sort's counted as if every band ran; operator path: two per operator call).
+ * A graph of more than 2^30 entries is MGX_E_FRONTIER_OVERFLOW at the first run, no memory is MGX_E_HIP.  Every run starts
+ * afresh, on the context's stream. */
+MGX_API int mgx_ktruss_create(mgx_graph_t g, mgx_ktruss_t* out);
+MGX_API int mgx_ktruss_free(mgx_ktruss_t p);
+/* the fused path: supports by the triangle count's kernels with the adds sent to the entries; the peel as a chain of launches
+ * whose kind is decided on the device, one host wait per batch of launches (64, 128, 256, 256 ...) */
+MGX_API int mgx_ktruss_run(mgx_ktruss_t p, int symmetric, int64_t* stats);
+/* the operator path: one advance for the supports, three filters over edge ids per pass; the host loops */
+MGX_API int mgx_ktruss_enact(mgx_ktruss_t p, int symmetric, int64_t* stats);
+/* results of the last run of either path (MGX_E_INVALID before any run); any array of _edges and _adjacency may be NULL.
+ * _edges, _support: stats[1] entries in the order of the oriented graph's entries; _vertex_truss: n; _histogram: min(cap, n + 1)
+ * counts; _adjacency: ro[n + 1], ci and eid[2 stats[1]]: row v = the simple neighbours of v ascending, each with its edge's id.
+ * _order: the peel order of the last FUSED run (every front is a range of it; MGX_E_INVALID when the last run was not fused).
+ * Device pointers stay valid until the next run or free. */
+MGX_API int mgx_ktruss_edges(mgx_ktruss_t p, int* h_src, int* h_dst, int* h_truss);
+MGX_API int mgx_ktruss_support(mgx_ktruss_t p, int* h_sup0);
+MGX_API int mgx_ktruss_vertex_truss(mgx_ktruss_t p, int* h_vtruss);
+MGX_API int mgx_ktruss_histogram(mgx_ktruss_t p, int64_t* h_hist, int cap);
+MGX_API int mgx_ktruss_order(mgx_ktruss_t p, int* h_order);
+MGX_API int mgx_ktruss_adjacency(mgx_ktruss_t p, int* h_ro, int* h_ci, int* h_eid);
+MGX_API int mgx_ktruss_truss_device(mgx_ktruss_t p, const int** d_truss);
+MGX_API int mgx_ktruss_vertex_truss_device(mgx_ktruss_t p, const int** d_vtruss);
+/* what every launch of the last fused run's peel was, in order: 1 smallest support, 2 list the level's first front, 3 expand,
+ * 4 seal, 5 behind the end.  *launches: how many the peel enqueued; min(*launches, cap, 65536) kinds are written.  MGX_E_INVALID
+ * before any fused run. */
+MGX_API int mgx_ktruss_step_kinds(mgx_ktruss_t p, int* host_kinds, int cap, int64_t* launches);
+/* timing (measurement tools; off by default): on != 0 makes every fused run record events round its support launches and its
+ * peel (one more host wait at the run's end, not counted in stats[6]); mgx_ktruss_phase_ms then gives out[2] = ms of the support
+ * launches and of the peel (its clears and idle launches included) of the last fused run */
+MGX_API int mgx_ktruss_set_timing(mgx_ktruss_t p, int on);
+MGX_API int mgx_ktruss_phase_ms(mgx_ktruss_t p, double* out);
 
 /* ---- segmented sort (mgpu::segmented_sort, lspar_enactor.hxx:85; mgx/segsort.hpp) ----
  * Sorts d_keys[0, count) (and d_vals with them; NULL: keys only) in place, stably, ascending or descending, within segments:

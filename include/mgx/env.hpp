@@ -58,6 +58,9 @@ inline const env_switch_t* env_switches(int* count) {
     {"MGX_TC_SHORT_MAX", "oriented rows of at most N entries are counted an entry a lane (default 16)"},
     {"MGX_TC_WAVE_MAX", "longer rows of at most N entries are staged in LDS by a wave, the rest by a workgroup (default 256)"},
     {"MGX_TC_STAGE", "entries of an LDS stage; a longer row is staged in chunks (default and at most 4096; a wave's: 512)"},
+    // ---- k-truss decomposition (ktruss_opts_t::from_env: read once per handle; both defaults are unmeasured guesses)
+    {"MGX_KTRUSS_SHORT_MAX", "front edges whose shorter adjacency row has at most N entries are expanded a lane each, the rest by waves (default 16)"},
+    {"MGX_KTRUSS_SEG", "entries of the shorter row one wave expands; a longer row goes out as (edge, segment) items (default 512)"},
     // ---- betweenness centrality (bc_opts_t::from_env: read once per handle; all four defaults are unmeasured guesses)
     {"MGX_BC_LANE_MAX", "rows of at most N entries are folded by one lane (default 16)"},
     {"MGX_BC_HUGE_MIN", "rows of at least N entries are cut into segments folded by several workgroups, the rest by a wave (default 8192)"},

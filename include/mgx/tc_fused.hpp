@@ -35,6 +35,8 @@
 //   tri[a]: one 64-bit add per row (k_tc_short: from the wave's LDS counters); tri[b]: one per entry and chunk;
 //   tri[w]: the staged kernels count the hits on w in an LDS counter beside w's slot of the stage and add them once per chunk,
 //   k_tc_short adds one per hit; the total: one add per workgroup.
+// The intersection bodies and the three count kernels take a template parameter EDGES (false: all of the above, unchanged).  true
+// is the k-truss's support of every entry (mgx/ktruss_fused.hpp): the same triangles, the adds sent to their three ENTRIES.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -284,11 +286,15 @@ struct tc_count_args_t {
   u64* tri;
   u64* stat;
   int stage;              // entries of a stage the staged kernels use (at most their LDS arrays)
+  int* sup = nullptr;     // EDGES (mgx/ktruss_fused.hpp): the per-entry supports the adds go to instead of tri
 };
 
 // Common elements of the sorted rows ci[p, p + pl) and ci[q, q + ql): the shorter one's entries are searched in the longer,
 // each search from where the last one ended.  tri[w] gets one add per common element w.
-__device__ __forceinline__ int tc_intersect(const int* __restrict__ ci, int p, int pl, int q, int ql, u64* tri) {
+// EDGES (the k-truss's supports, mgx/ktruss_fused.hpp): `sink` is the per-entry array, and the two positions of w -- in the row
+// searched from and in the row searched in, both entries of the triangle -- get the add instead of w (32-bit, one per hit each).
+template <bool EDGES = false, typename T>
+__device__ __forceinline__ int tc_intersect(const int* __restrict__ ci, int p, int pl, int q, int ql, T* sink) {
   if (pl > ql) {
     const int t = p; p = q; q = t;
     const int tl = pl; pl = ql; ql = tl;
@@ -305,8 +311,13 @@ __device__ __forceinline__ int tc_intersect(const int* __restrict__ ci, int p, i
     }
     if (lo < qe && ci[lo] == x) {
       ++c;
+      if constexpr (EDGES) {
+        atomicAdd(sink + p + i, 1);
+        atomicAdd(sink + lo, 1);
+      } else {
+        tc_add(sink + x, 1ull);
+      }
       ++lo;
-      tc_add(tri + x, 1ull);
     }
   }
   return c;
@@ -325,7 +336,8 @@ __device__ __forceinline__ void tc_flush_total(u64 mine, u64* total) {
   }
 }
 
-// short rows: a wave takes 64 of them and spreads their entries over its lanes
+// short rows: a wave takes 64 of them and spreads their entries over its lanes.  EDGES: the entry's own count goes to the entry
+template <bool EDGES = false>
 __global__ __launch_bounds__(BLOCK) void k_tc_short(tc_count_args_t a) {
   __shared__ int s_scan[WAVES_PER_BLOCK][WAVE];
   __shared__ unsigned s_acc[WAVES_PER_BLOCK][WAVE];
@@ -362,16 +374,20 @@ __global__ __launch_bounds__(BLOCK) void k_tc_short(tc_count_args_t a) {
         const int j = t - (sc[r] - da);
         const int b = a.ci[ra + j];
         const int rb = a.ro[b];
-        const int c = tc_intersect(a.ci, ra, da, rb, a.ro[b + 1] - rb, a.tri);
+        int c;
+        if constexpr (EDGES) c = tc_intersect<true>(a.ci, ra, da, rb, a.ro[b + 1] - rb, a.sup);
+        else c = tc_intersect(a.ci, ra, da, rb, a.ro[b + 1] - rb, a.tri);
         if (c) {
-          tc_add(a.tri + b, (u64)c);
+          if constexpr (EDGES) atomicAdd(a.sup + ra + j, c);
+          else tc_add(a.tri + b, (u64)c);
           atomicAdd(acc + r, (unsigned)c);
         }
       }
     }
     wave_lds_fence();
     const unsigned mine = acc[lane];
-    if (mine) tc_add(a.tri + v, (u64)mine);
+    if constexpr (!EDGES)
+      if (mine) tc_add(a.tri + v, (u64)mine);
     total += mine;
     wave_lds_fence();                                        // (read before the next rows fill the arrays)
   }
@@ -392,7 +408,10 @@ __device__ __forceinline__ int tc_find(const int* s, int n, int x) {
 // One staged row a by a team of TEAM threads (a wave or the workgroup), thread `tid` of it: per chunk of at most S entries of
 // row a in `stage`, groups of TC_GROUP lanes stream the rows b of all of row a's entries; hits[k] counts the hits on stage[k].
 // Returns this thread's share of tri[a]'s count (group leaders only).
-template <int TEAM>
+// EDGES: a triangle found at entry (a, b) with common element c adds to its three entries: the entry itself (once per entry and
+// chunk), c's slot of the stage = its position in row a (through the hit counters, once per chunk), and the streamed position of c
+// in row b (one add per hit: nothing aggregates it).
+template <int TEAM, bool EDGES = false>
 __device__ __forceinline__ u64 tc_staged_row(const tc_count_args_t& a, int va, int* stage, unsigned* hits, int S, int tid) {
   constexpr int G = TC_GROUP, NG = TEAM / G;
   const int lane = lane_id(), sub = lane % G, gshift = lane - sub, g = tid / G;
@@ -422,11 +441,15 @@ __device__ __forceinline__ u64 tc_staged_row(const tc_count_args_t& a, int va, i
         int pos = -1;
         if (act) pos = tc_find(stage, cl, a.ci[rb + k]);
         const u64 hm = __ballot(pos >= 0);
-        if (pos >= 0) atomicAdd(hits + pos, 1u);
+        if (pos >= 0) {
+          atomicAdd(hits + pos, 1u);
+          if constexpr (EDGES) atomicAdd(a.sup + rb + k, 1);
+        }
         cb += __popcll((hm >> gshift) & gmask);
       }
       if (sub == 0 && cb) {
-        tc_add(a.tri + b, (u64)cb);
+        if constexpr (EDGES) atomicAdd(a.sup + ra + j, cb);
+        else tc_add(a.tri + b, (u64)cb);
         ca += (u64)cb;
       }
     }
@@ -434,7 +457,11 @@ __device__ __forceinline__ u64 tc_staged_row(const tc_count_args_t& a, int va, i
     else __syncthreads();
     for (int k = tid; k < cl; k += TEAM) {
       const unsigned h = hits[k];
-      if (h) tc_add(a.tri + stage[k], (u64)h);
+      if constexpr (EDGES) {
+        if (h) atomicAdd(a.sup + ra + c0 + k, (int)h);
+      } else {
+        if (h) tc_add(a.tri + stage[k], (u64)h);
+      }
     }
     if (TEAM == WAVE) wave_lds_fence();                       // (read before the next chunk fills the stage)
     else __syncthreads();
@@ -443,6 +470,7 @@ __device__ __forceinline__ u64 tc_staged_row(const tc_count_args_t& a, int va, i
 }
 
 // rows a wave stages
+template <bool EDGES = false>
 __global__ __launch_bounds__(BLOCK) void k_tc_wave(tc_count_args_t a) {
   __shared__ int s_stage[WAVES_PER_BLOCK][TC_WAVE_STAGE];
   __shared__ unsigned s_hits[WAVES_PER_BLOCK][TC_WAVE_STAGE];
@@ -452,9 +480,9 @@ __global__ __launch_bounds__(BLOCK) void k_tc_wave(tc_count_args_t a) {
   u64 total = 0;
   for (long long it = (long long)blockIdx.x * WAVES_PER_BLOCK + w; it < nm; it += (long long)gridDim.x * WAVES_PER_BLOCK) {
     const int va = a.m_list[it];
-    const u64 ca = wave_sum(tc_staged_row<WAVE>(a, va, s_stage[w], s_hits[w], S, lane));
+    const u64 ca = wave_sum(tc_staged_row<WAVE, EDGES>(a, va, s_stage[w], s_hits[w], S, lane));
     if (lane == 0) {
-      if (ca) tc_add(a.tri + va, ca);
+      if (!EDGES && ca) tc_add(a.tri + va, ca);
       total += ca;
     }
   }
@@ -462,6 +490,7 @@ __global__ __launch_bounds__(BLOCK) void k_tc_wave(tc_count_args_t a) {
 }
 
 // rows a workgroup stages
+template <bool EDGES = false>
 __global__ __launch_bounds__(BLOCK) void k_tc_block(tc_count_args_t a) {
   __shared__ int s_stage[TC_BLOCK_STAGE];
   __shared__ unsigned s_hits[TC_BLOCK_STAGE];
@@ -471,13 +500,13 @@ __global__ __launch_bounds__(BLOCK) void k_tc_block(tc_count_args_t a) {
   u64 total = 0;
   for (long long it = blockIdx.x; it < nl; it += gridDim.x) {
     const int va = a.l_list[it];
-    const u64 ca = wave_sum(tc_staged_row<BLOCK>(a, va, s_stage, s_hits, S, (int)threadIdx.x));
+    const u64 ca = wave_sum(tc_staged_row<BLOCK, EDGES>(a, va, s_stage, s_hits, S, (int)threadIdx.x));
     if (lane_id() == 0) s_ca[threadIdx.x / WAVE] = ca;
     __syncthreads();
     if (threadIdx.x == 0) {
       u64 t = 0;
       for (int w = 0; w < WAVES_PER_BLOCK; ++w) t += s_ca[w];
-      if (t) tc_add(a.tri + va, t);
+      if (!EDGES && t) tc_add(a.tri + va, t);
       total += t;
     }
     __syncthreads();
@@ -681,9 +710,9 @@ struct tc_state_t {
     tc_count_args_t a;
     a.ro = d.ro.data(); a.ci = d.ci.data(); a.s_list = d.s_list.data(); a.m_list = d.m_list.data(); a.l_list = d.l_list.data();
     a.cnt = d.words.data(); a.tri = tri.data(); a.stat = d.stat.data(); a.stage = opts.stage;
-    hipLaunchKernelGGL(k_tc_block, dim3(max_blocks), dim3(BLOCK), 0, st, a);      // the heaviest rows first
-    hipLaunchKernelGGL(k_tc_wave, dim3(max_blocks), dim3(BLOCK), 0, st, a);
-    hipLaunchKernelGGL(k_tc_short, dim3(max_blocks), dim3(BLOCK), 0, st, a);
+    hipLaunchKernelGGL(k_tc_block<false>, dim3(max_blocks), dim3(BLOCK), 0, st, a);      // the heaviest rows first
+    hipLaunchKernelGGL(k_tc_wave<false>, dim3(max_blocks), dim3(BLOCK), 0, st, a);
+    hipLaunchKernelGGL(k_tc_short<false>, dim3(max_blocks), dim3(BLOCK), 0, st, a);
     launches += 5;                                             // (two clears, three kernels)
     MGX_CHECK_LAUNCH("mgx tc run");
     read_stats(d, built_now, ctx);

@@ -265,6 +265,21 @@ SIGNATURES = {
     "mgx_mst_labels": [_vp, _vp],
     "mgx_mst_labels_device": [_vp, _pvp],
     "mgx_mst_info": [_vp, _pi64],
+    "mgx_ktruss_create": [_vp, _pvp],
+    "mgx_ktruss_free": [_vp],
+    "mgx_ktruss_run": [_vp, _i, _pi64],
+    "mgx_ktruss_enact": [_vp, _i, _pi64],
+    "mgx_ktruss_edges": [_vp, _vp, _vp, _vp],
+    "mgx_ktruss_support": [_vp, _vp],
+    "mgx_ktruss_vertex_truss": [_vp, _vp],
+    "mgx_ktruss_histogram": [_vp, _pi64, _i],
+    "mgx_ktruss_order": [_vp, _vp],
+    "mgx_ktruss_adjacency": [_vp, _vp, _vp, _vp],
+    "mgx_ktruss_truss_device": [_vp, _pvp],
+    "mgx_ktruss_vertex_truss_device": [_vp, _pvp],
+    "mgx_ktruss_step_kinds": [_vp, _vp, _i, _pi64],
+    "mgx_ktruss_set_timing": [_vp, _i],
+    "mgx_ktruss_phase_ms": [_vp, C.POINTER(C.c_double)],
     "mgx_rmat_edges": [_vp, _i, _i64, _i64, _u64, _i, _vp, _vp, _vp],
 }
 _RESTYPES = {"mgx_comm_library": C.c_char_p, "mgx_strerror": C.c_char_p, "mgx_last_error": C.c_char_p, "mgx_host_free": None}

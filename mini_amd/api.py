@@ -4,7 +4,7 @@ Names follow the reference (gunrock/src/*.hxx): Graph ~ graph_device_t, Frontier
 BfsProblem ~ bfs_problem_t + bfs_enactor_t, SsspProblem ~ sssp_problem_t + sssp_enactor_t,
 PrProblem ~ pr_problem_t + pr_enactor_t, KcoreProblem ~ kcore_problem_t + kcore_enactor_t,
 ColorProblem ~ coloring_problem_t + coloring_enactor_t, LsparProblem ~ lspar_problem_t + lspar_enactor_t,
-CcProblem ~ cc_problem_t + cc_enactor_t, TcProblem ~ tc_problem_t + tc_enactor_t, BcProblem ~ bc_problem_t + bc_enactor_t, MstProblem ~ mst_problem_t + mst_enactor_t, PageRankProblem ~ pagerank_problem_t + pagerank_enactor_t.  Every method is one C-ABI call; nothing is computed here but TcProblem.clustering() / transitivity(), one numpy division on the counts, and BcProblem.centrality()'s two scalings.
+CcProblem ~ cc_problem_t + cc_enactor_t, TcProblem ~ tc_problem_t + tc_enactor_t, BcProblem ~ bc_problem_t + bc_enactor_t, MstProblem ~ mst_problem_t + mst_enactor_t, KtrussProblem ~ ktruss_problem_t + ktruss_enactor_t, PageRankProblem ~ pagerank_problem_t + pagerank_enactor_t.  Every method is one C-ABI call; nothing is computed here but TcProblem.clustering() / transitivity(), one numpy division on the counts, BcProblem.centrality()'s two scalings, and KtrussProblem's canonical edge order (u < v, sorted by (u, v): one lexsort of what the library returns in its own edge order).
 """
 import ctypes as C
 
@@ -948,6 +948,138 @@ class TcProblem:
     def close(self):
         if self._h:
             lib.mgx_tc_free(self._h)
+            self._h = None
+
+
+class KtrussProblem:
+    """k-truss decomposition: ktruss_problem_t + ktruss_enactor_t, and the fused path beside them, on the underlying
+    simple undirected graph, in original ids.  The getters describe the last run of either path."""
+
+    KEYS = ("max_truss", "edges", "triangles", "levels", "passes", "built", "host_waits", "launches")
+    STEP_KINDS = {1: "min", 2: "list", 3: "expand", 4: "seal", 5: "idle"}
+
+    def __init__(self, graph):
+        h = C.c_void_p()
+        check(lib.mgx_ktruss_create(graph._h, C.byref(h)))
+        self.graph, self._h = graph, h
+        self._m = None
+
+    def _go(self, fn, symmetric):
+        st = (C.c_int64 * 8)()
+        self._m = None
+        check(fn(self._h, int(bool(symmetric)), st))
+        self._m = int(st[1])
+        return dict(zip(self.KEYS, (int(x) for x in st)))
+
+    def run(self, symmetric=True):
+        """fused path -> the stats dict of KEYS.  symmetric=True is the caller's word that every entry has its reverse; False is
+        right on any graph."""
+        return self._go(lib.mgx_ktruss_run, symmetric)
+
+    def enact(self, symmetric=True):
+        """operator path (one advance for the supports, three filters over edge ids per pass); the same stats"""
+        return self._go(lib.mgx_ktruss_enact, symmetric)
+
+    def _edge_count(self):
+        if self._m is None:
+            check(lib.mgx_ktruss_edges(self._h, None, None, None))            # raises: no run yet
+        return self._m
+
+    def _raw_edges(self):
+        m = self._edge_count()
+        a, b, t = (np.empty(max(m, 1), dtype=np.int32) for _ in range(3))
+        check(lib.mgx_ktruss_edges(self._h, _ptr(a), _ptr(b), _ptr(t)))
+        return a[:m], b[:m], t[:m]
+
+    def _canonical(self):
+        """(u, v, permutation): the edges with u < v, sorted by (u, v) -- the same whatever orientation the run used"""
+        a, b, _ = self._raw_edges()
+        u, v = np.minimum(a, b), np.maximum(a, b)
+        perm = np.lexsort((v, u))
+        return u[perm], v[perm], perm
+
+    def edges(self):
+        """(u int32, v int32, truss int32) with u < v, sorted by (u, v)"""
+        u, v, perm = self._canonical()
+        return u, v, self._raw_edges()[2][perm]
+
+    def support(self):
+        """the triangles that contain each edge (int32), in the order of edges()"""
+        m = self._edge_count()
+        out = np.empty(max(m, 1), dtype=np.int32)
+        check(lib.mgx_ktruss_support(self._h, _ptr(out)))
+        return out[:m][self._canonical()[2]]
+
+    def vertex_truss(self):
+        """vtruss[v]: the largest trussness of an edge at v, 0 if there is none (int32)"""
+        out = np.empty(self.graph.num_nodes, dtype=np.int32)
+        check(lib.mgx_ktruss_vertex_truss(self._h, _ptr(out)))
+        return out
+
+    def histogram(self):
+        """hist[k]: the edges of trussness k (int64), k = 0 .. the largest trussness"""
+        cap = self.graph.num_nodes + 1
+        out = (C.c_int64 * cap)()
+        check(lib.mgx_ktruss_histogram(self._h, out, cap))
+        h = np.array(out[:], dtype=np.int64)
+        top = int(np.flatnonzero(h).max()) if h.any() else 0
+        return h[:top + 1]
+
+    def order(self):
+        """the peel order of the last run(): edge ids (positions of the oriented graph's entries); every front is a range of it"""
+        m = self._edge_count()
+        out = np.empty(max(m, 1), dtype=np.int32)
+        check(lib.mgx_ktruss_order(self._h, _ptr(out)))
+        return out[:m]
+
+    def adjacency(self):
+        """(row_offsets, col_indices, edge_ids): row v = the simple neighbours of v ascending, each with its edge's id"""
+        m = self._edge_count()
+        ro = np.empty(self.graph.num_nodes + 1, dtype=np.int32)
+        ci, eid = (np.empty(max(2 * m, 1), dtype=np.int32) for _ in range(2))
+        check(lib.mgx_ktruss_adjacency(self._h, _ptr(ro), _ptr(ci), _ptr(eid)))
+        return ro, ci[:2 * m], eid[:2 * m]
+
+    def raw_edges(self):
+        """(src, dst, truss) in the order of the oriented graph's entries: what the edge ids of order() and adjacency() index"""
+        return self._raw_edges()
+
+    def step_kinds(self):
+        """what every launch of the last run()'s peel was, in order (the first 65536): codes of STEP_KINDS"""
+        n = C.c_int64()
+        out = np.empty(1 << 16, dtype=np.int32)
+        check(lib.mgx_ktruss_step_kinds(self._h, _ptr(out), len(out), C.byref(n)))
+        return out[:min(n.value, len(out))].copy()
+
+    def set_timing(self, on):
+        """measurement tools: every run() records events round its support launches and its peel"""
+        check(lib.mgx_ktruss_set_timing(self._h, int(bool(on))))
+
+    def phase_ms(self):
+        """ms of the support launches and of the peel of the last timed run()"""
+        out = (C.c_double * 2)()
+        check(lib.mgx_ktruss_phase_ms(self._h, out))
+        return {"support": out[0], "peel": out[1]}
+
+    def truss_edges(self, k):
+        """(u, v) of the edges of trussness >= k: the k-truss with its isolated vertices dropped"""
+        u, v, t = self.edges()
+        keep = t >= k
+        return u[keep], v[keep]
+
+    def truss_device_ptr(self):
+        p = C.c_void_p()
+        check(lib.mgx_ktruss_truss_device(self._h, C.byref(p)))
+        return p.value
+
+    def vertex_truss_device_ptr(self):
+        p = C.c_void_p()
+        check(lib.mgx_ktruss_vertex_truss_device(self._h, C.byref(p)))
+        return p.value
+
+    def close(self):
+        if self._h:
+            lib.mgx_ktruss_free(self._h)
             self._h = None
 
 

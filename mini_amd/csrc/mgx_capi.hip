@@ -16,6 +16,7 @@
 #include "gunrock/cc/cc_enactor.hxx"
 #include "gunrock/coloring/coloring_enactor.hxx"
 #include "gunrock/lspar/lspar_enactor.hxx"
+#include "gunrock/ktruss/ktruss_enactor.hxx"
 #include "gunrock/mst/mst_enactor.hxx"
 #include "gunrock/pagerank/pagerank_enactor.hxx"
 #include "gunrock/pr/pr_enactor.hxx"
@@ -29,6 +30,7 @@
 #include "mgx/kcore_fused.hpp"
 #include "mgx/color_fused.hpp"
 #include "mgx/lspar_fused.hpp"
+#include "mgx/ktruss_fused.hpp"
 #include "mgx/mst_fused.hpp"
 #include "mgx/pagerank_fused.hpp"
 #include "mgx/env.hpp"
@@ -158,6 +160,12 @@ struct mgx_mst_s : mgx_problem_s {
   const float* w = nullptr;
   long long edges = 0;
   double total = 0.0;
+};
+
+struct mgx_ktruss_s : mgx_problem_s {
+  std::unique_ptr<mgx::ktruss_state_t> st;                        // lazily: the DAGs and adjacencies (per `symmetric`), the run's arrays
+  std::shared_ptr<ktruss::ktruss_problem_t> p[2];                 // lazily: the operator path's view of them
+  std::unique_ptr<ktruss::ktruss_enactor_t> e[2];
 };
 
 struct mgx_dbfs_s {
@@ -2991,6 +2999,147 @@ int mgx_mst_info(mgx_mst_t p, int64_t* out) {
   MGX_REQUIRE(p && out, "NULL argument");
   MGX_REQUIRE(p->fused, "mgx_mst_info: no fused run yet");
   put_stats(out, 8, p->fused->info());
+  MGX_CATCH
+}
+
+// ---- k-truss decomposition -----------------------------------------------------------
+int mgx_ktruss_create(mgx_graph_t g, mgx_ktruss_t* out) { return create_handle(g, out); }
+int mgx_ktruss_free(mgx_ktruss_t p) { return free_handle(p); }
+static mgx::ktruss_state_t& ktruss_state(mgx_ktruss_t p) {
+  if (!p->st) p->st.reset(new mgx::ktruss_state_t(p->graph().num_nodes, p->graph().num_edges, p->ctx()));
+  return *p->st;
+}
+int mgx_ktruss_run(mgx_ktruss_t p, int symmetric, int64_t* stats) {
+  MGX_TRY
+  auto [ctx, g] = enter(p);
+  put_stats(stats, 8, ktruss_state(p).run(g.d_row_offsets.data(), g.d_col_indices.data(), symmetric != 0, ctx));
+  MGX_CATCH
+}
+int mgx_ktruss_enact(mgx_ktruss_t p, int symmetric, int64_t* stats) {
+  MGX_TRY
+  auto [ctx, g] = enter(p);
+  mgx::ktruss_state_t& st = ktruss_state(p);
+  const int sym = symmetric != 0 ? 1 : 0;
+  st.start_run();
+  if (st.n <= 0) { put_stats(stats, 8, {0, 0, 0, 0, 0, 0, 0, 0}); return MGX_OK; }
+  const bool built_now = st.ensure_graph(sym != 0, g.d_row_offsets.data(), g.d_col_indices.data(), ctx);
+  mgx::ktruss_graph_t& kg = st.gr[sym];
+  mgx::tc_dag_t& d = st.tc.dag[sym];
+  const hipStream_t s = ctx.stream();
+  // the operator's view borrows the arrays: a new one whenever they are not the ones it holds (either path may have rebuilt)
+  std::shared_ptr<ktruss::ktruss_problem_t>& view = p->p[sym];
+  if (!view || view->gslice->d_row_offsets.data() != d.ro.data() || view->gslice->d_col_indices.data() != d.ci.data()) {
+    const ktruss::ktruss_problem_t::data_slice_t slice = {d.ro.data(), d.ci.data(), kg.src.data(), kg.adj_ro.data(), kg.adj_ci.data(),
+                                                          kg.adj_eid.data(), kg.sup0.data(), kg.sup.data(), kg.state.data(),
+                                                          kg.truss.data(), st.vtruss.data(), st.hist.data()};
+    view = std::make_shared<ktruss::ktruss_problem_t>(slice, st.n, kg.m, ctx);
+    ++st.tc.waits;                                     // (its data slice goes up with a blocking copy)
+    p->e[sym].reset(new ktruss::ktruss_enactor_t(ctx, std::max(std::max(st.n, kg.m), 1)));
+  }
+  ktruss::ktruss_enactor_t& e = *p->e[sym];
+  e.waits = e.calls = 0;
+  MGX_HIP(hipMemsetAsync(kg.sup0.data(), 0, (size_t)std::max(kg.m, 1) * sizeof(int), s));
+  MGX_HIP(hipMemsetAsync(d.stat.data() + mgx::TC_S_TOTAL, 0, sizeof(mgx::u64), s));
+  e.supports(view, ctx);
+  hipLaunchKernelGGL(mgx::k_ktruss_sum, dim3(grid_for(std::max(kg.m, 1), mgx::BLOCK, std::max(ctx.num_cus, 1) * 8)), dim3(mgx::BLOCK), 0, s,
+                     (const int*)kg.sup0.data(), kg.m, d.stat.data());
+  MGX_CHECK_LAUNCH("mgx ktruss enact");
+  st.begin_peel(kg, ctx);
+  e.peel(view, ctx);
+  st.tc.waits += e.waits;
+  st.tc.launches += 3 + 2 * e.calls;                   // (two clears, the sum; a scan and an expansion, or the two sweeps of a compaction, per call)
+  st.tc.read_stats(d, false, ctx);
+  st.res[0] = e.largest; st.res[1] = kg.m; st.res[2] = d.h[mgx::TC_S_TOTAL] / 3; st.res[3] = e.levels; st.res[4] = e.passes;
+  put_stats(stats, 8, st.finish_run(sym, built_now));
+  MGX_CATCH
+}
+static mgx::ktruss_graph_t& ktruss_last(mgx_ktruss_t p, const char* who) {
+  require_run(p->st && p->st->last >= 0, who);
+  return p->st->gr[p->st->last];
+}
+int mgx_ktruss_edges(mgx_ktruss_t p, int* h_src, int* h_dst, int* h_truss) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  mgx::ktruss_graph_t& kg = ktruss_last(p, "mgx_ktruss_edges");
+  if (h_src) read_back(p, h_src, (const int*)kg.src.data(), (size_t)kg.m);
+  if (h_dst) read_back(p, h_dst, (const int*)p->st->tc.dag[p->st->last].ci.data(), (size_t)kg.m);
+  if (h_truss) read_back(p, h_truss, (const int*)kg.truss.data(), (size_t)kg.m);
+  MGX_CATCH
+}
+int mgx_ktruss_support(mgx_ktruss_t p, int* host) {
+  MGX_TRY
+  MGX_REQUIRE(p && host, "NULL argument");
+  mgx::ktruss_graph_t& kg = ktruss_last(p, "mgx_ktruss_support");
+  read_back(p, host, (const int*)kg.sup0.data(), (size_t)kg.m);
+  MGX_CATCH
+}
+int mgx_ktruss_vertex_truss(mgx_ktruss_t p, int* host) {
+  MGX_TRY
+  MGX_REQUIRE(p && host, "NULL argument");
+  ktruss_last(p, "mgx_ktruss_vertex_truss");
+  read_back(p, host, (const int*)p->st->vtruss.data(), (size_t)p->st->n);
+  MGX_CATCH
+}
+int mgx_ktruss_histogram(mgx_ktruss_t p, int64_t* host, int cap) {
+  MGX_TRY
+  MGX_REQUIRE(p && host && cap >= 0, "bad argument");
+  ktruss_last(p, "mgx_ktruss_histogram");
+  std::vector<int> h((size_t)std::min<long long>(cap, (long long)p->st->n + 1));
+  read_back(p, h.data(), (const int*)p->st->hist.data(), h.size());
+  std::copy(h.begin(), h.end(), host);
+  MGX_CATCH
+}
+int mgx_ktruss_order(mgx_ktruss_t p, int* host) {
+  MGX_TRY
+  MGX_REQUIRE(p && host, "NULL argument");
+  mgx::ktruss_graph_t& kg = ktruss_last(p, "mgx_ktruss_order");
+  MGX_REQUIRE(p->st->last_fused, "mgx_ktruss_order: the last run was not a fused run");
+  read_back(p, host, (const int*)kg.order.data(), (size_t)kg.m);
+  MGX_CATCH
+}
+int mgx_ktruss_adjacency(mgx_ktruss_t p, int* h_ro, int* h_ci, int* h_eid) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  mgx::ktruss_graph_t& kg = ktruss_last(p, "mgx_ktruss_adjacency");
+  if (h_ro) read_back(p, h_ro, (const int*)kg.adj_ro.data(), (size_t)p->st->n + 1);
+  if (h_ci) read_back(p, h_ci, (const int*)kg.adj_ci.data(), 2 * (size_t)kg.m);
+  if (h_eid) read_back(p, h_eid, (const int*)kg.adj_eid.data(), 2 * (size_t)kg.m);
+  MGX_CATCH
+}
+int mgx_ktruss_truss_device(mgx_ktruss_t p, const int** out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  *out = ktruss_last(p, "mgx_ktruss_truss_device").truss.data();
+  MGX_CATCH
+}
+int mgx_ktruss_vertex_truss_device(mgx_ktruss_t p, const int** out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  ktruss_last(p, "mgx_ktruss_vertex_truss_device");
+  *out = p->st->vtruss.data();
+  MGX_CATCH
+}
+int mgx_ktruss_step_kinds(mgx_ktruss_t p, int* host_kinds, int cap, int64_t* launches) {
+  MGX_TRY
+  MGX_REQUIRE(p && launches && cap >= 0 && (host_kinds || cap == 0), "bad argument");
+  require_run(p->st && p->st->log_launches >= 0, "mgx_ktruss_step_kinds");
+  *launches = p->st->log_launches;
+  const long long have = std::min<long long>(std::min<long long>(p->st->log_launches, mgx::KTRUSS_LOG_CAP), cap);
+  read_back(p, host_kinds, (const int*)p->st->ctl.data()->log, (size_t)have);
+  MGX_CATCH
+}
+int mgx_ktruss_set_timing(mgx_ktruss_t p, int on) {
+  MGX_TRY
+  enter(p);
+  ktruss_state(p).timing = on != 0;
+  MGX_CATCH
+}
+int mgx_ktruss_phase_ms(mgx_ktruss_t p, double* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->st && p->st->log_launches >= 0, "mgx_ktruss_phase_ms");
+  out[0] = p->st->phase_ms[0];
+  out[1] = p->st->phase_ms[1];
   MGX_CATCH
 }
 
