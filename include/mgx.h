@@ -50,6 +50,7 @@ typedef struct mgx_bc_s* mgx_bc_t;
 typedef struct mgx_pagerank_s* mgx_pagerank_t;
 typedef struct mgx_mst_s* mgx_mst_t;
 typedef struct mgx_ktruss_s* mgx_ktruss_t;
+typedef struct mgx_scc_s* mgx_scc_t;
 typedef struct mgx_dbfs_s* mgx_dbfs_t;
 typedef struct mgx_dbfs2_s* mgx_dbfs2_t;
 typedef struct mgx_dsssp_s* mgx_dsssp_t;
@@ -806,6 +807,42 @@ MGX_API int mgx_ktruss_step_kinds(mgx_ktruss_t p, int* host_kinds, int cap, int6
  * launches and of the peel (its clears and idle launches included) of the last fused run */
 MGX_API int mgx_ktruss_set_timing(mgx_ktruss_t p, int on);
 MGX_API int mgx_ktruss_phase_ms(mgx_ktruss_t p, double* out);
+
+/* ---- strongly connected components (include/mgx/scc_fused.hpp, include/gunrock/scc/) ----
+ * The graph is the directed graph whose arcs are the CSR entries (v -> u), in original ids; an attached layout is ignored,
+ * self-loops and duplicate entries change no label.  label[v] = the smallest vertex id of v's strongly connected component (a
+ * vertex on no cycle is a component of its own).  Both runs need the graph's genuine CSC for the in-entries: without it they
+ * return MGX_E_INVALID.  Both paths and tests/scc_model.py run the same scheme -- trim to the fixpoint, one pivot reach, colouring
+ * rounds, a trim behind each -- whose alive set after every phase is unique.
+ * stats (may be NULL), int64[8]: [0] components, [1] the largest one's size, [2] its label (ties: the smaller), [3] vertices the
+ * trims removed over the whole run, [4] size of the pivot's component (0: nobody was alive after the first trim), [5] rounds,
+ * [6] host waits (fused: one per batch of launches and one for [0] - [2]; operator path: one per operator call and that one),
+ * [7] launches (fused: the idle ones behind the run's end included; operator path: operator calls).  Every run starts afresh, on
+ * the context's stream; a second run allocates nothing.  A run that fails leaves no result: the getters, mgx_scc_step_kinds and
+ * mgx_scc_phase_ms included, return MGX_E_INVALID until a run succeeds.  MGX_E_HIP "a fixpoint did not end": more than n + 2
+ * launches of one kind in a row, which the definition rules out -- a fault of the library, reported instead of run on. */
+MGX_API int mgx_scc_create(mgx_graph_t g, mgx_scc_t* out);
+MGX_API int mgx_scc_free(mgx_scc_t p);
+/* the fused path: a chain of launches whose kind is decided on the device, one host wait per batch of launches (64, 128, 256,
+ * 256 ...) */
+MGX_API int mgx_scc_run(mgx_scc_t p, int64_t* stats);
+/* the operator path: filters that recount for the trims and the pivot, advances with an atomicMin functor forward and a claiming
+ * functor over the transposed graph backward; the host loops */
+MGX_API int mgx_scc_enact(mgx_scc_t p, int64_t* stats);
+/* the labels of the last run of either path (MGX_E_INVALID before any run); the device pointer stays valid until the next run or
+ * free */
+MGX_API int mgx_scc_labels(mgx_scc_t p, int* host_labels);
+MGX_API int mgx_scc_labels_device(mgx_scc_t p, const int** d_labels);
+/* what every launch of the last fused run was, in order: 1 degrees, 2 list the first trim front, 3 expand (take the degrees down
+ * for who left), 4 pivot: largest product, 5 pivot: smallest id, 6 round init, 7 forward sweep, 8 roots, 9 backward sweep, 10 seal,
+ * 11 behind the end.  *launches: how many the run enqueued; min(*launches, cap, 65536) kinds are written.  MGX_E_INVALID before
+ * any fused run. */
+MGX_API int mgx_scc_step_kinds(mgx_scc_t p, int* host_kinds, int cap, int64_t* launches);
+/* timing (measurement tools; off by default): on != 0 makes every launch of a fused run add the device's wall clock since the
+ * launch before it to that launch's phase; mgx_scc_phase_ms then gives out[4] = ms of the last fused run's degree init, trims
+ * (all of them), pivot phase and rounds */
+MGX_API int mgx_scc_set_timing(mgx_scc_t p, int on);
+MGX_API int mgx_scc_phase_ms(mgx_scc_t p, double* out);
 
 /* ---- segmented sort (mgpu::segmented_sort, lspar_enactor.hxx:85; mgx/segsort.hpp) ----
  * Sorts d_keys[0, count) (and d_vals with them; NULL: keys only) in place, stably, ascending or descending, within segments:

@@ -61,6 +61,8 @@ inline const env_switch_t* env_switches(int* count) {
     // ---- k-truss decomposition (ktruss_opts_t::from_env: read once per handle; both defaults are unmeasured guesses)
     {"MGX_KTRUSS_SHORT_MAX", "front edges whose shorter adjacency row has at most N entries are expanded a lane each, the rest by waves (default 16)"},
     {"MGX_KTRUSS_SEG", "entries of the shorter row one wave expands; a longer row goes out as (edge, segment) items (default 512)"},
+    {"MGX_SCC_LONG_MIN", "out- or in-rows of at least N entries of a front vertex go out as (vertex, segment) items, a wave each; shorter ones take a lane (default 32, an unmeasured guess)"},
+    {"MGX_SCC_SEG", "entries of a long row one wave takes (default 256, an unmeasured guess)"},
     // ---- betweenness centrality (bc_opts_t::from_env: read once per handle; all four defaults are unmeasured guesses)
     {"MGX_BC_LANE_MAX", "rows of at most N entries are folded by one lane (default 16)"},
     {"MGX_BC_HUGE_MIN", "rows of at least N entries are cut into segments folded by several workgroups, the rest by a wave (default 8192)"},

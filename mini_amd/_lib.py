@@ -280,6 +280,15 @@ SIGNATURES = {
     "mgx_ktruss_step_kinds": [_vp, _vp, _i, _pi64],
     "mgx_ktruss_set_timing": [_vp, _i],
     "mgx_ktruss_phase_ms": [_vp, C.POINTER(C.c_double)],
+    "mgx_scc_create": [_vp, _pvp],
+    "mgx_scc_free": [_vp],
+    "mgx_scc_run": [_vp, _pi64],
+    "mgx_scc_enact": [_vp, _pi64],
+    "mgx_scc_labels": [_vp, _vp],
+    "mgx_scc_labels_device": [_vp, _pvp],
+    "mgx_scc_step_kinds": [_vp, _vp, _i, _pi64],
+    "mgx_scc_set_timing": [_vp, _i],
+    "mgx_scc_phase_ms": [_vp, C.POINTER(C.c_double)],
     "mgx_rmat_edges": [_vp, _i, _i64, _i64, _u64, _i, _vp, _vp, _vp],
 }
 _RESTYPES = {"mgx_comm_library": C.c_char_p, "mgx_strerror": C.c_char_p, "mgx_last_error": C.c_char_p, "mgx_host_free": None}

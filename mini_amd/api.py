@@ -1083,6 +1083,68 @@ class KtrussProblem:
             self._h = None
 
 
+class SccProblem:
+    """Strongly connected components: scc_problem_t + scc_enactor_t, and the fused path beside them, on the directed
+    graph of the CSR entries, which needs its genuine CSC (Graph.build_csc, or one uploaded with the graph).  labels() describes
+    the last run of either path: label[v] = the smallest vertex id of v's strongly connected component."""
+
+    KEYS = ("components", "largest", "largest_label", "trimmed", "pivot_size", "rounds", "host_waits", "launches")
+    STEP_KINDS = {1: "degrees", 2: "list", 3: "expand", 4: "pivot_max", 5: "pivot_pick", 6: "round_init", 7: "forward", 8: "roots",
+                  9: "backward", 10: "seal", 11: "idle"}
+    PHASES = ("init", "trim", "pivot", "rounds")
+
+    def __init__(self, graph):
+        h = C.c_void_p()
+        check(lib.mgx_scc_create(graph._h, C.byref(h)))
+        self.graph, self._h = graph, h
+
+    def _go(self, fn):
+        st = (C.c_int64 * 8)()
+        check(fn(self._h, st))
+        return dict(zip(self.KEYS, (int(x) for x in st)))
+
+    def run(self):
+        """fused path -> the stats dict of KEYS"""
+        return self._go(lib.mgx_scc_run)
+
+    def enact(self):
+        """operator path (recounting filters for the trims and the pivot, advances forward and over the transposed graph); the
+        same stats"""
+        return self._go(lib.mgx_scc_enact)
+
+    def labels(self):
+        out = np.empty(self.graph.num_nodes, dtype=np.int32)
+        check(lib.mgx_scc_labels(self._h, _ptr(out)))
+        return out
+
+    def labels_device_ptr(self):
+        p = C.c_void_p()
+        check(lib.mgx_scc_labels_device(self._h, C.byref(p)))
+        return p.value
+
+    def step_kinds(self):
+        """what every launch of the last run() was, in order (the first 65536): codes of STEP_KINDS"""
+        n = C.c_int64()
+        out = np.empty(1 << 16, dtype=np.int32)
+        check(lib.mgx_scc_step_kinds(self._h, _ptr(out), len(out), C.byref(n)))
+        return out[:min(n.value, len(out))].copy()
+
+    def set_timing(self, on):
+        """measurement tools: every launch of a run() keeps the device's wall clock per phase"""
+        check(lib.mgx_scc_set_timing(self._h, int(bool(on))))
+
+    def phase_ms(self):
+        """ms of the degree init, the trims, the pivot phase and the rounds of the last timed run()"""
+        out = (C.c_double * 4)()
+        check(lib.mgx_scc_phase_ms(self._h, out))
+        return dict(zip(self.PHASES, (float(x) for x in out)))
+
+    def close(self):
+        if self._h:
+            lib.mgx_scc_free(self._h)
+            self._h = None
+
+
 class BcProblem:
     """Betweenness centrality: bc_problem_t + bc_enactor_t, and the fused path beside them.  centrality() is the sum
     over the last run's sources; sigma(), delta() and labels() describe its LAST source; original ids."""

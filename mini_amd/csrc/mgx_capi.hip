@@ -17,6 +17,7 @@
 #include "gunrock/coloring/coloring_enactor.hxx"
 #include "gunrock/lspar/lspar_enactor.hxx"
 #include "gunrock/ktruss/ktruss_enactor.hxx"
+#include "gunrock/scc/scc_enactor.hxx"
 #include "gunrock/mst/mst_enactor.hxx"
 #include "gunrock/pagerank/pagerank_enactor.hxx"
 #include "gunrock/pr/pr_enactor.hxx"
@@ -31,6 +32,7 @@
 #include "mgx/color_fused.hpp"
 #include "mgx/lspar_fused.hpp"
 #include "mgx/ktruss_fused.hpp"
+#include "mgx/scc_fused.hpp"
 #include "mgx/mst_fused.hpp"
 #include "mgx/pagerank_fused.hpp"
 #include "mgx/env.hpp"
@@ -166,6 +168,15 @@ struct mgx_ktruss_s : mgx_problem_s {
   std::unique_ptr<mgx::ktruss_state_t> st;                        // lazily: the DAGs and adjacencies (per `symmetric`), the run's arrays
   std::shared_ptr<ktruss::ktruss_problem_t> p[2];                 // lazily: the operator path's view of them
   std::unique_ptr<ktruss::ktruss_enactor_t> e[2];
+};
+
+struct mgx_scc_s : mgx_problem_s {
+  std::unique_ptr<mgx::scc_fused_state_t> fused;                  // lazily: the fused path's state, lists and state words
+  std::unique_ptr<scc::scc_state_t> op_state;                     // lazily: the operator path's arrays, its two views of them
+  std::shared_ptr<scc::scc_problem_t> fwd, bwd;
+  std::unique_ptr<scc::scc_enactor_t> e;
+  std::unique_ptr<mgx::cc_label_stats_t> label_stats;             // lazily: the operator path's stats
+  const int* labels = nullptr;                                    // the last run's labels (nullptr: no run yet)
 };
 
 struct mgx_dbfs_s {
@@ -3140,6 +3151,83 @@ int mgx_ktruss_phase_ms(mgx_ktruss_t p, double* out) {
   require_run(p->st && p->st->log_launches >= 0, "mgx_ktruss_phase_ms");
   out[0] = p->st->phase_ms[0];
   out[1] = p->st->phase_ms[1];
+  MGX_CATCH
+}
+
+// ---- strongly connected components --------------------------------------------------
+int mgx_scc_create(mgx_graph_t g, mgx_scc_t* out) { return create_handle(g, out); }
+int mgx_scc_free(mgx_scc_t p) { return free_handle(p); }
+int mgx_scc_run(mgx_scc_t p, int64_t* stats) {
+  MGX_TRY
+  auto [ctx, g] = enter(p);
+  MGX_REQUIRE(!g.csc_is_csr, "mgx_scc_run: needs the graph's genuine CSC (mgx_graph_build_csc)");
+  if (!p->fused) p->fused.reset(new mgx::scc_fused_state_t(g.num_nodes, g.num_edges, ctx));
+  p->labels = nullptr;
+  const std::vector<long long> st = p->fused->run(g.d_row_offsets.data(), g.d_col_indices.data(), g.d_col_offsets.data(),
+                                                  g.d_row_indices.data(), ctx);
+  p->labels = p->fused->label.data();
+  put_stats(stats, 8, st);
+  MGX_CATCH
+}
+int mgx_scc_enact(mgx_scc_t p, int64_t* stats) {
+  MGX_TRY
+  auto [ctx, g] = enter(p);
+  MGX_REQUIRE(!g.csc_is_csr, "mgx_scc_enact: needs the graph's genuine CSC (mgx_graph_build_csc)");
+  p->labels = nullptr;
+  const int n = g.num_nodes;
+  if (n <= 0) { put_stats(stats, 8, {0, 0, 0, 0, 0, 0, 0, 0}); return MGX_OK; }
+  if (!p->op_state) p->op_state.reset(new scc::scc_state_t(n, ctx));
+  scc::scc_state_t& os = *p->op_state;
+  // the views borrow the graph's arrays: new ones whenever those are not the ones they hold (the CSC may have been rebuilt)
+  if (!p->fwd || p->bwd->gslice->d_row_offsets.data() != g.d_col_offsets.data() || p->bwd->gslice->d_col_indices.data() != g.d_row_indices.data()) {
+    const scc::scc_problem_t::data_slice_t slice = {g.d_row_offsets.data(), g.d_col_indices.data(), g.d_col_offsets.data(), g.d_row_indices.data(),
+                                                    os.d_state.data(), os.d_col.data(), os.d_claim.data(), os.d_label.data(), os.d_scalars.data()};
+    p->fwd = std::make_shared<scc::scc_problem_t>(p->g->g, slice, ctx);
+    p->bwd = std::make_shared<scc::scc_problem_t>(slice, n, g.num_edges, ctx);
+  }
+  if (!p->e) p->e.reset(new scc::scc_enactor_t(ctx, n, g.num_edges));
+  if (!p->label_stats) p->label_stats.reset(new mgx::cc_label_stats_t(n, ctx));
+  p->e->enact(p->fwd, p->bwd, os, ctx);
+  const std::vector<long long> st = p->label_stats->run(os.d_label.data(), n, ctx);
+  p->labels = os.d_label.data();
+  put_stats(stats, 8, {st[0], st[1], st[2], p->e->trimmed, p->e->pivot_size, p->e->rounds, p->e->waits + 1, p->e->calls});
+  MGX_CATCH
+}
+int mgx_scc_labels(mgx_scc_t p, int* host) {
+  MGX_TRY
+  MGX_REQUIRE(p && host, "NULL argument");
+  require_run(p->labels, "mgx_scc_labels");
+  read_back(p, host, p->labels, p->n());
+  MGX_CATCH
+}
+int mgx_scc_labels_device(mgx_scc_t p, const int** out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->labels, "mgx_scc_labels_device");
+  *out = p->labels;
+  MGX_CATCH
+}
+int mgx_scc_step_kinds(mgx_scc_t p, int* host_kinds, int cap, int64_t* launches) {
+  MGX_TRY
+  MGX_REQUIRE(p && launches && cap >= 0 && (host_kinds || cap == 0), "bad argument");
+  require_run(p->fused && p->fused->launches >= 0, "mgx_scc_step_kinds");
+  *launches = p->fused->launches;
+  const long long have = std::min<long long>(std::min<long long>(p->fused->launches, mgx::SCC_LOG_CAP), cap);
+  read_back(p, host_kinds, (const int*)p->fused->ctl.data()->log, (size_t)have);
+  MGX_CATCH
+}
+int mgx_scc_set_timing(mgx_scc_t p, int on) {
+  MGX_TRY
+  auto [ctx, g] = enter(p);
+  if (!p->fused) p->fused.reset(new mgx::scc_fused_state_t(g.num_nodes, g.num_edges, ctx));
+  p->fused->timing = on != 0;
+  MGX_CATCH
+}
+int mgx_scc_phase_ms(mgx_scc_t p, double* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->fused && p->fused->launches >= 0, "mgx_scc_phase_ms");
+  for (int i = 0; i < 4; ++i) out[i] = p->fused->phase_ms[i];
   MGX_CATCH
 }
 
