@@ -290,7 +290,13 @@ __device__ __forceinline__ void bfs_mini_body(const bfs_fused_args_t& a, int arg
   }
   flush();
   found = (int)wave_sum((u32)found);
-  if (lane == 0 && found) atomicAdd(&c->reached_mini, (u64)found);
+  if (lane == 0 && found) {
+    atomicAdd(&c->reached_mini, (u64)found);
+    if (a.count_marks) {             // statistics for the tools, as the chain and the push bodies keep them: a claim here is a discovery
+      atomicAdd(&c->claims, (u64)found);
+      if (level < 64) atomicAdd(&c->claims_level[level], (u64)found);
+    }
+  }
 }
 template <int NT>
 __global__ __launch_bounds__(NT) void k_bfs_mini(bfs_fused_args_t a, int arg) {

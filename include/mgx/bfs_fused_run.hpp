@@ -123,9 +123,10 @@ __device__ __forceinline__ void bfs_slot_open(const bfs_fused_args_t& a, const b
   bfs_slot_marks_clear(a, p.slot + 1);
   c->slot_level[(p.slot + 1) & 3] = p.level + 1;
   c->skip_build[p.slot & 3] = 0;
-  if (p.dense) c->dense_slots += 1;
+  // (a bottom-up level behind a lazy build carries both flags -- bfs_slot_plan sets them for whatever finds no queues -- and runs neither body)
+  if (p.dense && !p.pulls) c->dense_slots += 1;
   if (p.cold || p.colds) { c->cold_slot = p.slot; c->cold_slots += 1; }
-  if (p.vshort) c->vshort_slots += 1;
+  if (p.vshort && !p.pulls) c->vshort_slots += 1;
 }
 
 // Push of one slot, ONE launch: block 0 opens the level (or runs the chain of small levels and everybody else

@@ -741,7 +741,33 @@ VARIANTS = [{}, {"MGX_BFS_COLD_TEST": "1"}, {"MGX_BFS_COLD_TEST": "1", "MGX_BFS_
             # range shortened to one run and to a third, the per-source launch plan off / on with M launches forced on small graphs
             {"MGX_BFS_PACK24": "0", "MGX_BFS_DENSE": "1000000"}, {"MGX_BFS_PACK24": "0"}, {"MGX_BFS_DENSE": "1000000", "MGX_BFS_DEFER": "1", "MGX_BFS_DEFER_WORDS": "32"},
             {"MGX_BFS_DEFER_WORDS": "6016", "MGX_BFS_DEFER": "1", "MGX_BFS_HOT_MIN_EDGES": "0"}, {"MGX_BFS_DEFER_WORDS": "0"},
-            {"MGX_BFS_MINI": "2", "MGX_BFS_SRC_PLAN": "0"}, {"MGX_BFS_MINI": "2", "MGX_BFS_SRC_PLAN": "1", "MGX_BFS_CHAIN_BIG_EDGES": "64"}]
+            {"MGX_BFS_MINI": "2", "MGX_BFS_SRC_PLAN": "0"}, {"MGX_BFS_MINI": "2", "MGX_BFS_SRC_PLAN": "1", "MGX_BFS_CHAIN_BIG_EDGES": "64"},
+            # no chain of either kind: every level a device-wide slot
+            {"MGX_BFS_CHAIN_MAX_EDGES": "0", "MGX_BFS_SEED_CHAIN": "0"}]
+
+
+def _variant_promises(env, tot):
+    """what a variant's switches promise about the bodies its six trials ran (tot: the counters summed over them): a switch that
+    stopped selecting its body fails here, not only a body that computes wrong labels"""
+    on = lambda key, value: env.get(key) == value
+    if on("MGX_BFS_DENSE", "1000000"):
+        assert tot["dense_slots"] >= 1, tot
+    if on("MGX_BFS_VSHORT", "1000000"):
+        assert tot["vshort_slots"] >= 1, tot
+    if on("MGX_BFS_LAZY", "1048576"):
+        assert tot["lazy_slots"] >= 1, tot
+    if on("MGX_BFS_MINI", "2"):
+        assert tot["mini_slots"] >= 1, tot
+    if on("MGX_BFS_DENSE", "0"):
+        assert tot["dense_slots"] == 0, tot
+    if on("MGX_BFS_VSHORT", "0"):
+        assert tot["vshort_slots"] == 0, tot
+    if on("MGX_BFS_LAZY", "0"):
+        assert tot["lazy_slots"] == 0, tot
+    if on("MGX_BFS_MINI", "0"):
+        assert tot["mini_slots"] == 0, tot
+    if on("MGX_BFS_CHAIN_MAX_EDGES", "0"):       # (alone it switches the in-place chain off too; with MGX_BFS_SEED_CHAIN=0 said out loud)
+        assert tot["small_levels"] == tot["mini_slots"], tot
 
 
 @pytest.mark.parametrize("variant", range(len(VARIANTS)))
@@ -756,6 +782,7 @@ def test_bfs_kernel_variants_on_random_graphs(gpu_ctx, oracle, monkeypatch, vari
     for k, v in VARIANTS[variant].items():
         monkeypatch.setenv(k, v)
     rng = np.random.default_rng(100 + variant)
+    tot = dict.fromkeys(("small_levels", "dense_slots", "vshort_slots", "lazy_slots", "mini_slots"), 0)
     for trial in range(6):
         kind = trial % 3
         if kind == 0:      # star forest, hubs of every size
@@ -780,6 +807,9 @@ def test_bfs_kernel_variants_on_random_graphs(gpu_ctx, oracle, monkeypatch, vari
             st = bfs.run(src)
             assert np.array_equal(bfs.labels(), want), (variant, trial, src)
             assert st["m_t"] == int(deg[want >= 0].sum())
+            for k in tot:
+                tot[k] += st[k]
+    _variant_promises(VARIANTS[variant], tot)
 
 
 @pytest.mark.parametrize("build_list", [0, 1])
