@@ -51,6 +51,7 @@ typedef struct mgx_pagerank_s* mgx_pagerank_t;
 typedef struct mgx_mst_s* mgx_mst_t;
 typedef struct mgx_ktruss_s* mgx_ktruss_t;
 typedef struct mgx_scc_s* mgx_scc_t;
+typedef struct mgx_lpa_s* mgx_lpa_t;
 typedef struct mgx_dbfs_s* mgx_dbfs_t;
 typedef struct mgx_dbfs2_s* mgx_dbfs2_t;
 typedef struct mgx_dsssp_s* mgx_dsssp_t;
@@ -843,6 +844,57 @@ MGX_API int mgx_scc_step_kinds(mgx_scc_t p, int* host_kinds, int cap, int64_t* l
  * (all of them), pivot phase and rounds */
 MGX_API int mgx_scc_set_timing(mgx_scc_t p, int on);
 MGX_API int mgx_scc_phase_ms(mgx_scc_t p, double* out);
+
+/* ---- label propagation and modularity (include/mgx/lpa_fused.hpp, include/gunrock/lpa/) ----
+ * Community detection by label propagation, in original ids; an attached layout is ignored.  symmetric != 0 is the caller's word
+ * that every entry has its reverse: each CSR entry (v, u), u != v, gives v one vote for label[u].  symmetric == 0 is right on any
+ * graph: each entry (v, u), u != v, gives v one vote for label[u] and u one vote for label[v]; it needs the graph's genuine CSC
+ * and is MGX_E_INVALID without one.  Self-loops never vote, duplicate entries vote once each, edge weights are not used.
+ * label_0[v] = v; in iteration t every vertex with votes wants the label most of its votes carry (its current one on a tie, else
+ * the smallest); unstable_t counts those that want another.  unstable_t == 0 ends the run (converged, iterations = t), t ==
+ * max_iter ends it too.  mode MGX_LPA_SYNC: every unstable vertex moves; MGX_LPA_LAZY: those with color_key(v, color_salt(seed,
+ * t)) & 1 (include/mgx/color_hash.hpp) -- the synchronous rule oscillates on anything bipartite.  Both paths and
+ * tests/lpa_model.py compute the same labels bit for bit.
+ * mode must be 0 or 1 and max_iter in [0, 2^20], else MGX_E_INVALID before any device work; more than 2^30 entries:
+ * MGX_E_FRONTIER_OVERFLOW (mgx_lpa_enact with symmetric == 0: 2^30 entries or more, its 2 m vote slots are addressed by ints).
+ * stats (may be NULL), int64[10]: [0] communities (distinct labels), [1] the largest one's size, [2] its label (ties: the
+ * smaller), [3] iterations, [4] converged (0 / 1), [5] unstable of the last iteration evaluated, [6] rows evaluated over the run
+ * (operator path: n x (iterations + 1)), [7] rows that overflowed their LDS table, [8] host waits (fused: one per batch of
+ * launches and one for [0] - [2]), [9] launches (fused: the idle ones behind the run's end included; operator path: operator
+ * calls).  Every run starts afresh, on the context's stream; a second run allocates nothing.  A run that fails leaves no result:
+ * the getters return MGX_E_INVALID until a run succeeds. */
+#define MGX_LPA_SYNC 0
+#define MGX_LPA_LAZY 1
+MGX_API int mgx_lpa_create(mgx_graph_t g, mgx_lpa_t* out);
+MGX_API int mgx_lpa_free(mgx_lpa_t p);
+/* the fused path: a chain of launches whose kind is decided on the device, one host wait per batch of launches (64, 128, 256,
+ * 256 ...) */
+MGX_API int mgx_lpa_run(mgx_lpa_t p, int symmetric, int mode, uint32_t seed, int max_iter, int64_t* stats);
+/* the operator path: advances that gather every vote's label, the segmented sort, a filter that scans every vertex's sorted votes
+ * and one that applies the moves; every vertex every iteration */
+MGX_API int mgx_lpa_enact(mgx_lpa_t p, int symmetric, int mode, uint32_t seed, int max_iter, int64_t* stats);
+/* the labels of the last run of either path; the device pointer stays valid until the next run or free */
+MGX_API int mgx_lpa_labels(mgx_lpa_t p, int* host_labels);
+MGX_API int mgx_lpa_labels_device(mgx_lpa_t p, const int** d_labels);
+/* per iteration of the last run (iterations + 1 of them), three values: unstable_t, the vertices whose label changed, the vertices
+ * evaluated.  *iterations: how many triples the run has; min(*iterations, cap) are written. */
+MGX_API int mgx_lpa_trace(mgx_lpa_t p, int64_t* host_triples, int cap, int64_t* iterations);
+/* what every launch of the last fused run was, in order: 1 setup, 2 evaluate all vertices, 3 evaluate the active list, 4 the long
+ * rows, 5 apply over all vertices, 6 apply over the list, 7 behind the end, 8 mark the voters of the movers' long rows.  *launches: how many the run enqueued;
+ * min(*launches, cap, 65536) kinds are written.  MGX_E_INVALID before any fused run. */
+MGX_API int mgx_lpa_step_kinds(mgx_lpa_t p, int* host_kinds, int cap, int64_t* launches);
+/* the last fused run, int64[9]: [0] - [3] vertices whose rows have no entries / take a lane / a wave / a workgroup, [4] - [7]
+ * MGX_LPA_SHORT_MAX, _WAVE_MAX, _TABLE and _LIST_DIV as read, [8] rows that overflowed their table over the whole run */
+MGX_API int mgx_lpa_bins(mgx_lpa_t p, int64_t* out);
+/* timing (measurement tools; off by default): mgx_lpa_phase_ms gives out[4] = ms of the last fused run's setup, evaluations,
+ * long rows and applies */
+MGX_API int mgx_lpa_set_timing(mgx_lpa_t p, int on);
+MGX_API int mgx_lpa_phase_ms(mgx_lpa_t p, double* out);
+/* Modularity of any labelling (d_labels: n labels in [0, n) on the device): out[3] = {S_in, S_sq, W} with S_in the votes whose two
+ * ends carry equal labels, S_sq the sum over the labels of (the votes of their vertices)^2, W all votes; Q = S_in / W - S_sq /
+ * W^2 (0 when W == 0) is the caller's division.  A label outside [0, n): MGX_E_INVALID, found at the call's host wait.  The n
+ * sums the call needs are allocated at the graph's first call and kept with it: a second call allocates nothing. */
+MGX_API int mgx_modularity(mgx_graph_t g, const int* d_labels, int symmetric, uint64_t* out);
 
 /* ---- segmented sort (mgpu::segmented_sort, lspar_enactor.hxx:85; mgx/segsort.hpp) ----
  * Sorts d_keys[0, count) (and d_vals with them; NULL: keys only) in place, stably, ascending or descending, within segments:

@@ -63,6 +63,11 @@ inline const env_switch_t* env_switches(int* count) {
     {"MGX_KTRUSS_SEG", "entries of the shorter row one wave expands; a longer row goes out as (edge, segment) items (default 512)"},
     {"MGX_SCC_LONG_MIN", "out- or in-rows of at least N entries of a front vertex go out as (vertex, segment) items, a wave each; shorter ones take a lane (default 32, an unmeasured guess)"},
     {"MGX_SCC_SEG", "entries of a long row one wave takes (default 256, an unmeasured guess)"},
+    // ---- label propagation (lpa_opts_t::from_env: read once per handle; all four defaults are unmeasured guesses)
+    {"MGX_LPA_SHORT_MAX", "vertices whose rows have at most N entries find their label a lane each, the labels in registers (default and at most 16)"},
+    {"MGX_LPA_WAVE_MAX", "longer rows of at most N entries take a wave each and a wave-private LDS table; the rest a workgroup (default 256, at most 512)"},
+    {"MGX_LPA_TABLE", "labels a workgroup's LDS table holds, a power of two in [32, 2048]; a row with more distinct labels is passed over by hash class (default 2048)"},
+    {"MGX_LPA_LIST_DIV", "0 / N: every iteration runs over all vertices / over the active set when it has at most n / N vertices (default 8; 1: always)"},
     // ---- betweenness centrality (bc_opts_t::from_env: read once per handle; all four defaults are unmeasured guesses)
     {"MGX_BC_LANE_MAX", "rows of at most N entries are folded by one lane (default 16)"},
     {"MGX_BC_HUGE_MIN", "rows of at least N entries are cut into segments folded by several workgroups, the rest by a wave (default 8192)"},

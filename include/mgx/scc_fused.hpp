@@ -67,6 +67,7 @@
 
 #include "cc_fused.hpp"
 #include "env.hpp"
+#include "launch_chain.hpp"
 #include "runtime.hpp"
 #include "wave.hpp"
 #include "worklist.hpp"
@@ -77,8 +78,6 @@ namespace mgx {
 constexpr int SCC_LONG_MIN_DEFAULT = 32;    // rows of at least this many entries are long
 constexpr int SCC_SEG_DEFAULT = 256;        // entries of a long row one wave takes
 constexpr int SCC_STAGE = 2 * WAVE;         // a wave's LDS stage of front vertices
-constexpr int SCC_BATCH_MIN = 64;           // launches per host wait: 64, 128, 256, 256 ...
-constexpr int SCC_BATCH_MAX = 256;
 constexpr int SCC_LOG_CAP = 1 << 16;        // launches whose kind is kept for mgx_scc_step_kinds
 constexpr int SCC_NONE = 0x7fffffff;        // col of a vertex the pivot has not reached
 
@@ -500,22 +499,18 @@ struct scc_fused_state_t {
     a.vert = vert.data(); a.label = label.data(); a.items = items.data();
     a.ctl = ctl.data(); a.n = n; a.item_cap = item_cap; a.long_min = opts.long_min; a.seg = opts.seg; a.timing = timing ? 1 : 0;
     const int blocks = grid_for(n, BLOCK, std::max(ctx.num_cus, 1) * 4);
-    long long waits = 0, enqueued = 0;
-    int batch = SCC_BATCH_MIN;
+    long long waits = 0;
     // The device reports a fixpoint that does not end (bit 1 of done, after n + 2 launches of one kind).  The count below only keeps
     // the stamps, launch numbers + 1, inside an int: it is hours of launches away and catches nothing early.
     const long long most = 0x7fff0000ll;
-    for (;;) {
-      for (int j = 0; j < batch; ++j, ++enqueued)
-        hipLaunchKernelGGL(k_scc_step, dim3(blocks), dim3(BLOCK), 0, st, a, (unsigned)enqueued);
-      MGX_CHECK_LAUNCH("mgx scc step");
-      h_totals.fetch(&ctl.data()->totals, 1, st);
-      ++waits;
-      if (h_totals->done & 2) throw mgx_error(MGX_E_HIP, "mgx scc: a fixpoint did not end within n + 2 launches");
-      if (h_totals->done) break;
-      if (enqueued > most) throw mgx_error(MGX_E_HIP, "mgx scc: the run did not end");
-      batch = std::min(batch * 2, SCC_BATCH_MAX);
-    }
+    const long long enqueued = run_launch_chain(
+        [&](long long i) { hipLaunchKernelGGL(k_scc_step, dim3(blocks), dim3(BLOCK), 0, st, a, (unsigned)i); },
+        [&]() {
+          h_totals.fetch(&ctl.data()->totals, 1, st);
+          if (h_totals->done & 2) throw mgx_error(MGX_E_HIP, "mgx scc: a fixpoint did not end within n + 2 launches");
+          return h_totals->done != 0;
+        },
+        most, "mgx scc step", &waits);
     if (timing) {
       if (clock_khz == 0) {
         int dev = 0;

@@ -17,6 +17,8 @@ MGX_E_NEGATIVE_WEIGHT = -5
 MGX_E_NO_DEVICE = -6
 MGX_BFS_PUSH = 0
 MGX_BFS_DIRECTION_OPT = 1
+MGX_LPA_SYNC = 0
+MGX_LPA_LAZY = 1
 
 
 class MgxError(RuntimeError):
@@ -289,6 +291,18 @@ SIGNATURES = {
     "mgx_scc_step_kinds": [_vp, _vp, _i, _pi64],
     "mgx_scc_set_timing": [_vp, _i],
     "mgx_scc_phase_ms": [_vp, C.POINTER(C.c_double)],
+    "mgx_lpa_create": [_vp, _pvp],
+    "mgx_lpa_free": [_vp],
+    "mgx_lpa_run": [_vp, _i, _i, C.c_uint32, _i, _pi64],
+    "mgx_lpa_enact": [_vp, _i, _i, C.c_uint32, _i, _pi64],
+    "mgx_lpa_labels": [_vp, _vp],
+    "mgx_lpa_labels_device": [_vp, _pvp],
+    "mgx_lpa_trace": [_vp, _vp, _i, _pi64],
+    "mgx_lpa_step_kinds": [_vp, _vp, _i, _pi64],
+    "mgx_lpa_bins": [_vp, _pi64],
+    "mgx_lpa_set_timing": [_vp, _i],
+    "mgx_lpa_phase_ms": [_vp, C.POINTER(C.c_double)],
+    "mgx_modularity": [_vp, _vp, _i, C.POINTER(C.c_uint64)],
     "mgx_rmat_edges": [_vp, _i, _i64, _i64, _u64, _i, _vp, _vp, _vp],
 }
 _RESTYPES = {"mgx_comm_library": C.c_char_p, "mgx_strerror": C.c_char_p, "mgx_last_error": C.c_char_p, "mgx_host_free": None}

@@ -1145,6 +1145,106 @@ class SccProblem:
             self._h = None
 
 
+class LpaProblem:
+    """Label propagation: lpa_problem_t + lpa_enactor_t, and the fused path beside them.  Every vertex takes the label
+    most of its votes carry; labels() describes the last run of either path.  symmetric=True is the caller's word that every
+    entry has its reverse; symmetric=False counts every entry at both of its ends and needs the graph's genuine CSC."""
+
+    SYNC, LAZY = _lib.MGX_LPA_SYNC, _lib.MGX_LPA_LAZY
+    SEED = 15485863
+    KEYS = ("communities", "largest", "largest_label", "iterations", "converged", "unstable", "evaluated", "overflowed", "host_waits",
+            "launches")
+    STEP_KINDS = {1: "setup", 2: "evaluate_dense", 3: "evaluate_list", 4: "long_rows", 5: "apply_dense", 6: "apply_list", 7: "idle",
+                  8: "mark_long_rows"}
+    PHASES = ("setup", "evaluate", "long_rows", "apply")
+    BINS = ("rows_none", "rows_short", "rows_wave", "rows_long", "short_max", "wave_max", "table", "list_div", "overflowed")
+
+    def __init__(self, graph):
+        h = C.c_void_p()
+        check(lib.mgx_lpa_create(graph._h, C.byref(h)))
+        self.graph, self._h = graph, h
+        self._symmetric = False
+
+    def _go(self, fn, symmetric, mode, seed, max_iter):
+        st = (C.c_int64 * 10)()
+        check(fn(self._h, int(bool(symmetric)), int(mode), int(seed) & 0xFFFFFFFF, int(max_iter), st))
+        self._symmetric = bool(symmetric)
+        return dict(zip(self.KEYS, (int(x) for x in st)))
+
+    def run(self, symmetric=False, mode=LAZY, seed=SEED, max_iter=100):
+        """fused path -> the stats dict of KEYS"""
+        return self._go(lib.mgx_lpa_run, symmetric, mode, seed, max_iter)
+
+    def enact(self, symmetric=False, mode=LAZY, seed=SEED, max_iter=100):
+        """operator path (gathering advances, the segmented sort, a scanning and an applying filter); the same stats"""
+        return self._go(lib.mgx_lpa_enact, symmetric, mode, seed, max_iter)
+
+    def labels(self):
+        out = np.empty(self.graph.num_nodes, dtype=np.int32)
+        check(lib.mgx_lpa_labels(self._h, _ptr(out)))
+        return out
+
+    def labels_device_ptr(self):
+        p = C.c_void_p()
+        check(lib.mgx_lpa_labels_device(self._h, C.byref(p)))
+        return p.value
+
+    def trace(self):
+        """int64[iterations + 1, 3] of the last run: unstable, changed, evaluated per iteration"""
+        n = C.c_int64()
+        check(lib.mgx_lpa_trace(self._h, None, 0, C.byref(n)))
+        out = np.empty((n.value, 3), dtype=np.int64)
+        check(lib.mgx_lpa_trace(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def step_kinds(self):
+        """what every launch of the last run() was, in order (the first 65536): codes of STEP_KINDS"""
+        n = C.c_int64()
+        out = np.empty(1 << 16, dtype=np.int32)
+        check(lib.mgx_lpa_step_kinds(self._h, _ptr(out), len(out), C.byref(n)))
+        return out[:min(n.value, len(out))].copy()
+
+    def bins(self):
+        """the last run(): vertices per body, the switches as read, rows that overflowed their table"""
+        out = (C.c_int64 * 9)()
+        check(lib.mgx_lpa_bins(self._h, out))
+        return dict(zip(self.BINS, (int(x) for x in out)))
+
+    def set_timing(self, on):
+        """measurement tools: every launch of a run() keeps the device's wall clock per phase"""
+        check(lib.mgx_lpa_set_timing(self._h, int(bool(on))))
+
+    def phase_ms(self):
+        out = (C.c_double * 4)()
+        check(lib.mgx_lpa_phase_ms(self._h, out))
+        return dict(zip(self.PHASES, (float(x) for x in out)))
+
+    def modularity(self):
+        """(Q, S_in, S_sq, W) of the last run's labels, with the votes of that run's `symmetric`"""
+        return modularity(self.graph, self.labels_device_ptr() or 0, self._symmetric)
+
+    def close(self):
+        if self._h:
+            lib.mgx_lpa_free(self._h)
+            self._h = None
+
+
+def modularity(graph, labels, symmetric=False):
+    """Modularity of any labelling (labels in [0, n): a numpy array, a torch tensor on the device or a device address) ->
+    (Q, S_in, S_sq, W); Q = S_in / W - S_sq / W^2 in double from the three integers the library returns (0.0 when W == 0)."""
+    keep = None
+    if isinstance(labels, np.ndarray):
+        import torch
+        keep = torch.from_numpy(_np_i32(labels)).cuda()
+        torch.cuda.synchronize()
+        labels = keep
+    out = (C.c_uint64 * 3)()
+    check(lib.mgx_modularity(graph._h, _dev_ptr(labels), int(bool(symmetric)), out))
+    s_in, s_sq, w = int(out[0]), int(out[1]), int(out[2])
+    q = 0.0 if w == 0 else float(s_in) / float(w) - float(s_sq) / (float(w) * float(w))
+    return q, s_in, s_sq, w
+
+
 class BcProblem:
     """Betweenness centrality: bc_problem_t + bc_enactor_t, and the fused path beside them.  centrality() is the sum
     over the last run's sources; sigma(), delta() and labels() describe its LAST source; original ids."""

@@ -18,6 +18,7 @@
 #include "gunrock/lspar/lspar_enactor.hxx"
 #include "gunrock/ktruss/ktruss_enactor.hxx"
 #include "gunrock/scc/scc_enactor.hxx"
+#include "gunrock/lpa/lpa_enactor.hxx"
 #include "gunrock/mst/mst_enactor.hxx"
 #include "gunrock/pagerank/pagerank_enactor.hxx"
 #include "gunrock/pr/pr_enactor.hxx"
@@ -33,6 +34,7 @@
 #include "mgx/lspar_fused.hpp"
 #include "mgx/ktruss_fused.hpp"
 #include "mgx/scc_fused.hpp"
+#include "mgx/lpa_fused.hpp"
 #include "mgx/mst_fused.hpp"
 #include "mgx/pagerank_fused.hpp"
 #include "mgx/env.hpp"
@@ -57,6 +59,7 @@ struct mgx_graph_s {
   std::shared_ptr<graph_device_t> g;
   bool weights_checked = false;
   bool weights_ok = true;
+  std::unique_ptr<mgx::modularity_state_t> mod;        // lazily: mgx_modularity's sums, kept for the next call on this graph
 };
 struct mgx_frontier_s {
   mgx_ctx_s* c;
@@ -177,6 +180,16 @@ struct mgx_scc_s : mgx_problem_s {
   std::unique_ptr<scc::scc_enactor_t> e;
   std::unique_ptr<mgx::cc_label_stats_t> label_stats;             // lazily: the operator path's stats
   const int* labels = nullptr;                                    // the last run's labels (nullptr: no run yet)
+};
+
+struct mgx_lpa_s : mgx_problem_s {
+  std::unique_ptr<mgx::lpa_fused_state_t> fused;                  // lazily: the fused path's labels, lists and state words
+  std::unique_ptr<lpa::lpa_state_t> op_state;                     // lazily: the operator path's arrays, its two views of them
+  std::shared_ptr<lpa::lpa_problem_t> fwd, bwd;
+  std::unique_ptr<lpa::lpa_enactor_t> e;
+  std::unique_ptr<mgx::lpa_label_stats_t> label_stats;            // lazily: the operator path's stats
+  const int* labels = nullptr;                                    // the last run's labels (nullptr: no run yet)
+  bool last_fused = false;                                        // which path the trace is read from
 };
 
 struct mgx_dbfs_s {
@@ -3228,6 +3241,150 @@ int mgx_scc_phase_ms(mgx_scc_t p, double* out) {
   MGX_REQUIRE(p && out, "NULL argument");
   require_run(p->fused && p->fused->launches >= 0, "mgx_scc_phase_ms");
   for (int i = 0; i < 4; ++i) out[i] = p->fused->phase_ms[i];
+  MGX_CATCH
+}
+
+// ---- label propagation and modularity ----------------------------------------------
+static void lpa_check_args(const graph_device_t& g, int symmetric, int mode, int max_iter, const char* who) {
+  MGX_REQUIRE(mode == MGX_LPA_SYNC || mode == MGX_LPA_LAZY, std::string(who) + ": mode must be MGX_LPA_SYNC or MGX_LPA_LAZY");
+  MGX_REQUIRE(max_iter >= 0 && max_iter <= mgx::LPA_MAX_ITER_MAX, std::string(who) + ": max_iter must be in [0, 2^20]");
+  MGX_REQUIRE(symmetric || !g.csc_is_csr, std::string(who) + ": symmetric = 0 needs the graph's genuine CSC (mgx_graph_build_csc)");
+  if ((long long)g.num_edges > (1ll << 30)) throw mgx::mgx_error(MGX_E_FRONTIER_OVERFLOW, std::string(who) + ": more than 2^30 entries");
+}
+int mgx_lpa_create(mgx_graph_t g, mgx_lpa_t* out) { return create_handle(g, out); }
+int mgx_lpa_free(mgx_lpa_t p) { return free_handle(p); }
+int mgx_lpa_run(mgx_lpa_t p, int symmetric, int mode, uint32_t seed, int max_iter, int64_t* stats) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  p->labels = nullptr;
+  if (p->fused) p->fused->launches = -1;                     // (a run that is refused leaves nothing to the getters either)
+  lpa_check_args(p->graph(), symmetric, mode, max_iter, "mgx_lpa_run");
+  auto [ctx, g] = enter(p);
+  if (!p->fused) p->fused.reset(new mgx::lpa_fused_state_t(g.num_nodes, g.num_edges, ctx));
+  const std::vector<long long> st = p->fused->run(g.d_row_offsets.data(), g.d_col_indices.data(), g.d_col_offsets.data(),
+                                                  g.d_row_indices.data(), symmetric, mode, seed, max_iter, ctx);
+  p->labels = p->fused->vert.data();
+  p->last_fused = true;
+  put_stats(stats, 10, st);
+  MGX_CATCH
+}
+int mgx_lpa_enact(mgx_lpa_t p, int symmetric, int mode, uint32_t seed, int max_iter, int64_t* stats) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  p->labels = nullptr;
+  if (p->fused) p->fused->launches = -1;                     // (a run that is refused leaves nothing to the getters either)
+  lpa_check_args(p->graph(), symmetric, mode, max_iter, "mgx_lpa_enact");
+  // (the votes' segments are addressed by ints: both rows of every vertex are 2 m slots)
+  if (!symmetric && (long long)p->graph().num_edges >= (1ll << 30))
+    throw mgx::mgx_error(MGX_E_FRONTIER_OVERFLOW, "mgx_lpa_enact: symmetric = 0 takes fewer than 2^30 entries on the operator path");
+  auto [ctx, g] = enter(p);
+  const int n = g.num_nodes;
+  if (!p->op_state) p->op_state.reset(new lpa::lpa_state_t(n, g.num_edges, ctx));
+  lpa::lpa_state_t& os = *p->op_state;
+  if (!p->e) p->e.reset(new lpa::lpa_enactor_t(ctx, n, g.num_edges));
+  if (n <= 0) {
+    p->e->trace.clear();
+    p->labels = os.d_label.data();
+    p->last_fused = false;
+    put_stats(stats, 10, {0, 0, 0, 0, 1, 0, 0, 0, 0, 0});
+    return MGX_OK;
+  }
+  // the views borrow the graph's arrays: new ones whenever those are not the ones they hold (the CSC may have been rebuilt)
+  const lpa::lpa_problem_t::data_slice_t slice = {g.d_row_offsets.data(), g.d_col_offsets.data(), os.d_heads.data(), os.d_votes.data(),
+                                                  os.d_label.data(), os.d_want.data(), os.d_scalars.data()};
+  if (!p->fwd) p->fwd = std::make_shared<lpa::lpa_problem_t>(p->g->g, slice, ctx);
+  if (!symmetric && (!p->bwd || p->bwd->gslice->d_row_offsets.data() != g.d_col_offsets.data() ||
+                     p->bwd->gslice->d_col_indices.data() != g.d_row_indices.data())) {
+    p->fwd = std::make_shared<lpa::lpa_problem_t>(p->g->g, slice, ctx);
+    p->bwd = std::make_shared<lpa::lpa_problem_t>(slice, g.d_col_offsets.data(), g.d_row_indices.data(), n, g.num_edges, ctx);
+  }
+  if (!p->label_stats) p->label_stats.reset(new mgx::lpa_label_stats_t(n, ctx));
+  p->e->enact(p->fwd, p->bwd, os, symmetric != 0, mode, seed, max_iter, ctx);
+  const std::vector<long long> st = p->label_stats->run(os.d_label.data(), n, ctx);
+  p->labels = os.d_label.data();
+  p->last_fused = false;
+  put_stats(stats, 10, {st[0], st[1], st[2], p->e->iterations, p->e->converged, p->e->unstable, (long long)n * (p->e->iterations + 1), 0,
+                        p->e->waits + 1, p->e->calls});
+  MGX_CATCH
+}
+int mgx_lpa_labels(mgx_lpa_t p, int* host) {
+  MGX_TRY
+  MGX_REQUIRE(p && host, "NULL argument");
+  require_run(p->labels, "mgx_lpa_labels");
+  read_back(p, host, p->labels, p->n());
+  MGX_CATCH
+}
+int mgx_lpa_labels_device(mgx_lpa_t p, const int** out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->labels, "mgx_lpa_labels_device");
+  *out = p->labels;
+  MGX_CATCH
+}
+int mgx_lpa_trace(mgx_lpa_t p, int64_t* host_triples, int cap, int64_t* iterations) {
+  MGX_TRY
+  MGX_REQUIRE(p && iterations && cap >= 0 && (host_triples || cap == 0), "bad argument");
+  require_run(p->labels, "mgx_lpa_trace");
+  if (p->last_fused) {
+    const long long have = p->n() == 0 ? 0 : p->fused->iterations + 1;
+    *iterations = have;
+    const size_t take = (size_t)std::min<long long>(have, cap);
+    std::vector<mgx::lpa_trace_t> h(take);
+    read_back(p, h.data(), (const mgx::lpa_trace_t*)p->fused->trace.data(), take);
+    for (size_t i = 0; i < take; ++i) {
+      host_triples[3 * i] = h[i].unstable; host_triples[3 * i + 1] = h[i].changed; host_triples[3 * i + 2] = h[i].evaluated;
+    }
+  } else {
+    const long long have = (long long)p->e->trace.size() / 3;
+    *iterations = have;
+    std::copy(p->e->trace.begin(), p->e->trace.begin() + 3 * std::min<long long>(have, cap), host_triples);
+  }
+  MGX_CATCH
+}
+int mgx_lpa_step_kinds(mgx_lpa_t p, int* host_kinds, int cap, int64_t* launches) {
+  MGX_TRY
+  MGX_REQUIRE(p && launches && cap >= 0 && (host_kinds || cap == 0), "bad argument");
+  require_run(p->fused && p->fused->launches >= 0, "mgx_lpa_step_kinds");
+  *launches = p->fused->launches;
+  const long long have = std::min<long long>(std::min<long long>(p->fused->launches, mgx::LPA_LOG_CAP), cap);
+  read_back(p, host_kinds, (const int*)p->fused->ctl.data()->log, (size_t)have);
+  MGX_CATCH
+}
+int mgx_lpa_bins(mgx_lpa_t p, int64_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->fused && p->fused->launches >= 0, "mgx_lpa_bins");
+  const mgx::lpa_fused_state_t& f = *p->fused;
+  for (int i = 0; i < 4; ++i) out[i] = f.bins[i];
+  out[4] = f.opts.short_max; out[5] = std::max(f.opts.wave_max, f.opts.short_max); out[6] = f.opts.table; out[7] = f.opts.list_div;
+  out[8] = f.overflowed;
+  MGX_CATCH
+}
+int mgx_lpa_set_timing(mgx_lpa_t p, int on) {
+  MGX_TRY
+  auto [ctx, g] = enter(p);
+  if (!p->fused) p->fused.reset(new mgx::lpa_fused_state_t(g.num_nodes, g.num_edges, ctx));
+  p->fused->timing = on != 0;
+  MGX_CATCH
+}
+int mgx_lpa_phase_ms(mgx_lpa_t p, double* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->fused && p->fused->launches >= 0, "mgx_lpa_phase_ms");
+  for (int i = 0; i < 4; ++i) out[i] = p->fused->phase_ms[i];
+  MGX_CATCH
+}
+int mgx_modularity(mgx_graph_t g, const int* d_labels, int symmetric, uint64_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(g && out && (d_labels || g->g->num_nodes == 0), "NULL argument");
+  graph_device_t& G = *g->g;
+  MGX_REQUIRE(symmetric || !G.csc_is_csr, "mgx_modularity: symmetric = 0 needs the graph's genuine CSC (mgx_graph_build_csc)");
+  use_device(g->c);
+  standard_context_t& ctx = *g->c->ctx;
+  if (!g->mod) g->mod.reset(new mgx::modularity_state_t(G.num_nodes, ctx));      // (a second call on the graph, an LPA handle's included, allocates nothing)
+  mgx::u64 r[3];
+  g->mod->run(G.d_row_offsets.data(), G.d_col_indices.data(), G.d_col_offsets.data(), G.d_row_indices.data(), d_labels, symmetric, r, ctx);
+  out[0] = r[0]; out[1] = r[1]; out[2] = r[2];
   MGX_CATCH
 }
 
