@@ -52,6 +52,7 @@ typedef struct mgx_mst_s* mgx_mst_t;
 typedef struct mgx_ktruss_s* mgx_ktruss_t;
 typedef struct mgx_scc_s* mgx_scc_t;
 typedef struct mgx_lpa_s* mgx_lpa_t;
+typedef struct mgx_msbfs_s* mgx_msbfs_t;
 typedef struct mgx_dbfs_s* mgx_dbfs_t;
 typedef struct mgx_dbfs2_s* mgx_dbfs2_t;
 typedef struct mgx_dsssp_s* mgx_dsssp_t;
@@ -895,6 +896,59 @@ MGX_API int mgx_lpa_phase_ms(mgx_lpa_t p, double* out);
  * W^2 (0 when W == 0) is the caller's division.  A label outside [0, n): MGX_E_INVALID, found at the call's host wait.  The n
  * sums the call needs are allocated at the graph's first call and kept with it: a second call allocates nothing. */
 MGX_API int mgx_modularity(mgx_graph_t g, const int* d_labels, int symmetric, uint64_t* out);
+
+/* ---- bit-parallel multi-source BFS and closeness (include/mgx/msbfs_fused.hpp, include/gunrock/msbfs/) ----
+ * BFS depths from many sources at once, in original ids; an attached layout is ignored.  A CSR entry (u, v) is an edge u -> v;
+ * duplicates and self-loops change nothing.  depth_s[v] is the BFS depth from s along out-entries, 0 at s, -1 when unreached: what
+ * mgx_bfs_labels gives for every source.  sources[count] is cut into batches of 64 in the given order (source 64 B + b is bit b
+ * of batch B: one 64-bit word per vertex serves the batch's traversals); duplicates are allowed and give equal rows; sources ==
+ * NULL means all n vertices (count is ignored); count < 0 or an id out of range is MGX_E_INVALID before any device work; count
+ * == 0 is a valid empty run.  A batch whose deepest vertex is at depth D runs D + 1 levels.
+ * Level t is a PULL (every vertex some source has not seen ORs its in-neighbours' front words, no atomics but for segmented huge
+ * rows) iff in-entries are available and MGX_MSBFS_PULL_DIV > 0 and e_t x MGX_MSBFS_PULL_DIV >= m, e_t the out-entries of the
+ * level's front; else a PUSH over the front's list (a 64-bit atomicOr per entry that brings new bits).  In-entries are the rows
+ * themselves when symmetric != 0 (the caller's word that every entry has its reverse), else the graph's genuine CSC; with
+ * symmetric == 0 and no CSC the run is valid and every level pushes.  mgx_msbfs_enact always pushes.
+ * Results of a run, over all its sources: per source reach (vertices at depth >= 1), far (the sum of their depths), ecc (the
+ * deepest level), exact, and harm = the sum of cnt_d / d over d = 1, 2 ... in double, added in ascending d (bit-equal from run
+ * to run); per vertex reach_in (the sources, with their multiplicity, that have it at depth >= 1) and far_in (the sum of those
+ * depths); with want_depths != 0 the depths, int32[count][n].  Depths that do not fit in memory: MGX_E_HIP.  Closeness is the
+ * caller's division: reach / far x reach / (n - 1).
+ * stats (may be NULL), int64[10]: [0] sources, [1] batches, [2] levels of the deepest batch, [3] the sum of reach, [4] PUSH
+ * levels, [5] PULL levels, [6] host waits (fused: one per batch of launches of the chain -- 64, 128, 256, 256 ... -- and one for
+ * the read-back of the per-source results), [7] launches (fused: the idle ones behind the run's end included; operator path:
+ * operator calls), [8] 1 if the genuine CSC served as the in-entries (operator path: 0), [9] 1 if depths were kept.  Every run
+ * starts afresh, on the context's stream; a repeat run allocates nothing.  A run that fails leaves no result: the getters return
+ * MGX_E_INVALID until a run succeeds, as they do before any run. */
+#define MGX_MSBFS_PUSH 0
+#define MGX_MSBFS_PULL 1
+MGX_API int mgx_msbfs_create(mgx_graph_t g, mgx_msbfs_t* out);
+MGX_API int mgx_msbfs_free(mgx_msbfs_t p);
+/* the fused path: a chain of launches whose kind is decided on the device; batches of sources follow each other without a host wait */
+MGX_API int mgx_msbfs_run(mgx_msbfs_t p, const int* sources, int count, int symmetric, int want_depths, int64_t* stats);
+/* the operator path: per level an advance that ORs, a filter that dedups and finalizes, a host wait */
+MGX_API int mgx_msbfs_enact(mgx_msbfs_t p, const int* sources, int count, int symmetric, int want_depths, int64_t* stats);
+/* the last run's per-source results, host arrays of its count */
+MGX_API int mgx_msbfs_reach(mgx_msbfs_t p, int64_t* host);
+MGX_API int mgx_msbfs_far(mgx_msbfs_t p, int64_t* host);
+MGX_API int mgx_msbfs_ecc(mgx_msbfs_t p, int64_t* host);
+MGX_API int mgx_msbfs_harmonic(mgx_msbfs_t p, double* host);
+/* the last run's per-vertex sums, n each; the device pointers stay valid until the next run or free */
+MGX_API int mgx_msbfs_vertex_sums(mgx_msbfs_t p, int64_t* reach_in, int64_t* far_in);
+MGX_API int mgx_msbfs_vertex_sums_device(mgx_msbfs_t p, const int64_t** d_reach_in, const int64_t** d_far_in);
+/* the last run's depths, int32[count][n]; MGX_E_INVALID when it kept none */
+MGX_API int mgx_msbfs_depths(mgx_msbfs_t p, int* host);
+/* MGX_MSBFS_PUSH or _PULL per (batch, level) of the last fused run, the batches behind each other.  *levels: how many it ran;
+ * min(*levels, cap, 65536) kinds are written */
+MGX_API int mgx_msbfs_level_kinds(mgx_msbfs_t p, int* host_kinds, int cap, int64_t* levels);
+/* the last fused run, int64[14]: [0] - [3] out-rows without entries / a lane's / a wave's / segmented, [4] the segments of the
+ * latter, [5] - [9] the same of the in-rows (zeros when every level pushes), [10] - [13] MGX_MSBFS_SHORT_MAX, _WAVE_MAX, _SEG
+ * and _PULL_DIV as read */
+MGX_API int mgx_msbfs_bins(mgx_msbfs_t p, int64_t* out);
+/* timing (measurement tools; off by default): mgx_msbfs_phase_ms gives out[4] = ms of the last fused run's PUSH, PULL, LONG and
+ * FINALIZE launches (RESET and SEED count as FINALIZE) */
+MGX_API int mgx_msbfs_set_timing(mgx_msbfs_t p, int on);
+MGX_API int mgx_msbfs_phase_ms(mgx_msbfs_t p, double* out);
 
 /* ---- segmented sort (mgpu::segmented_sort, lspar_enactor.hxx:85; mgx/segsort.hpp) ----
  * Sorts d_keys[0, count) (and d_vals with them; NULL: keys only) in place, stably, ascending or descending, within segments:

@@ -68,6 +68,11 @@ inline const env_switch_t* env_switches(int* count) {
     {"MGX_LPA_WAVE_MAX", "longer rows of at most N entries take a wave each and a wave-private LDS table; the rest a workgroup (default 256, at most 512)"},
     {"MGX_LPA_TABLE", "labels a workgroup's LDS table holds, a power of two in [32, 2048]; a row with more distinct labels is passed over by hash class (default 2048)"},
     {"MGX_LPA_LIST_DIV", "0 / N: every iteration runs over all vertices / over the active set when it has at most n / N vertices (default 8; 1: always)"},
+    // ---- multi-source BFS (msbfs_opts_t::from_env: read once per handle; all four defaults are unmeasured guesses)
+    {"MGX_MSBFS_SHORT_MAX", "rows of at most N entries are expanded a lane each (default 32)"},
+    {"MGX_MSBFS_WAVE_MAX", "longer rows of at most N entries take a wave each, the rest go out as (vertex, segment) items (default 1024)"},
+    {"MGX_MSBFS_SEG", "entries of a segmented row one wave takes (default 1024)"},
+    {"MGX_MSBFS_PULL_DIV", "0 / N: every level pushes / a level pulls when its front's out-entries x N >= m (default 8; 2^30: whenever the front has an out-entry)"},
     // ---- betweenness centrality (bc_opts_t::from_env: read once per handle; all four defaults are unmeasured guesses)
     {"MGX_BC_LANE_MAX", "rows of at most N entries are folded by one lane (default 16)"},
     {"MGX_BC_HUGE_MIN", "rows of at least N entries are cut into segments folded by several workgroups, the rest by a wave (default 8192)"},

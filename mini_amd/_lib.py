@@ -19,6 +19,8 @@ MGX_BFS_PUSH = 0
 MGX_BFS_DIRECTION_OPT = 1
 MGX_LPA_SYNC = 0
 MGX_LPA_LAZY = 1
+MGX_MSBFS_PUSH = 0
+MGX_MSBFS_PULL = 1
 
 
 class MgxError(RuntimeError):
@@ -302,6 +304,21 @@ SIGNATURES = {
     "mgx_lpa_bins": [_vp, _pi64],
     "mgx_lpa_set_timing": [_vp, _i],
     "mgx_lpa_phase_ms": [_vp, C.POINTER(C.c_double)],
+    "mgx_msbfs_create": [_vp, _pvp],
+    "mgx_msbfs_free": [_vp],
+    "mgx_msbfs_run": [_vp, _vp, _i, _i, _i, _pi64],
+    "mgx_msbfs_enact": [_vp, _vp, _i, _i, _i, _pi64],
+    "mgx_msbfs_reach": [_vp, _vp],
+    "mgx_msbfs_far": [_vp, _vp],
+    "mgx_msbfs_ecc": [_vp, _vp],
+    "mgx_msbfs_harmonic": [_vp, _vp],
+    "mgx_msbfs_vertex_sums": [_vp, _vp, _vp],
+    "mgx_msbfs_vertex_sums_device": [_vp, _pvp, _pvp],
+    "mgx_msbfs_depths": [_vp, _vp],
+    "mgx_msbfs_level_kinds": [_vp, _vp, _i, _pi64],
+    "mgx_msbfs_bins": [_vp, _pi64],
+    "mgx_msbfs_set_timing": [_vp, _i],
+    "mgx_msbfs_phase_ms": [_vp, C.POINTER(C.c_double)],
     "mgx_modularity": [_vp, _vp, _i, C.POINTER(C.c_uint64)],
     "mgx_rmat_edges": [_vp, _i, _i64, _i64, _u64, _i, _vp, _vp, _vp],
 }

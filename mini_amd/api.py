@@ -1229,6 +1229,129 @@ class LpaProblem:
             self._h = None
 
 
+class MsBfsProblem:
+    """Bit-parallel multi-source BFS: BFS depths from many sources at once, 64 traversals to a 64-bit word per vertex,
+    and what follows from them -- reach, farness, eccentricity, harmonic and closeness centrality per source, and per vertex how
+    many sources reach it and the sum of their depths.  run() is the fused path, enact() the operator path; the getters describe
+    the last run of either.  Depths follow the out-entries: on a directed graph closeness() and harmonic() are the OUT-closeness
+    and the out-harmonic centrality of the sources (networkx's closeness_centrality is the in-closeness: run on the reversed graph
+    to get that).  symmetric=True is the caller's word that every entry has its reverse, which lets the dense levels pull over
+    the rows themselves; symmetric=False pulls over the graph's genuine CSC where it has one and pushes every level where not."""
+
+    KEYS = ("sources", "batches", "deepest", "reach", "push_levels", "pull_levels", "host_waits", "launches", "csc", "depths")
+    PUSH, PULL = _lib.MGX_MSBFS_PUSH, _lib.MGX_MSBFS_PULL
+    PHASES = ("push", "pull", "long_rows", "finalize")
+    BINS = ("out_none", "out_short", "out_wave", "out_long", "out_segments", "in_none", "in_short", "in_wave", "in_long", "in_segments",
+            "short_max", "wave_max", "seg", "pull_div")
+
+    def __init__(self, graph):
+        h = C.c_void_p()
+        check(lib.mgx_msbfs_create(graph._h, C.byref(h)))
+        self.graph, self._h = graph, h
+        self._count = 0
+
+    def _go(self, fn, sources, symmetric, depths):
+        st = (C.c_int64 * 10)()
+        if sources is None:
+            src, ptr, count = None, None, 0
+        else:
+            src = _np_i32(np.asarray(sources))
+            ptr, count = _ptr(src), len(src)
+            if count == 0:
+                src = np.zeros(1, dtype=np.int32)                # (NULL would mean every vertex)
+                ptr = _ptr(src)
+        check(fn(self._h, ptr, count, int(bool(symmetric)), int(bool(depths)), st))
+        out = dict(zip(self.KEYS, (int(x) for x in st)))
+        self._count = out["sources"]
+        return out
+
+    def run(self, sources=None, symmetric=False, depths=False):
+        """fused path from `sources` (None: every vertex) -> the stats dict of KEYS"""
+        return self._go(lib.mgx_msbfs_run, sources, symmetric, depths)
+
+    def enact(self, sources=None, symmetric=False, depths=False):
+        """operator path (an advance that ORs and a filter that finalizes per level; it always pushes); the same results"""
+        return self._go(lib.mgx_msbfs_enact, sources, symmetric, depths)
+
+    def _per_source(self, fn, dtype):
+        out = np.zeros(max(self._count, 1), dtype=dtype)
+        check(fn(self._h, _ptr(out)))
+        return out[:self._count]
+
+    def reach(self):
+        """int64[count]: the vertices every source reaches, itself not counted"""
+        return self._per_source(lib.mgx_msbfs_reach, np.int64)
+
+    def farness(self):
+        """int64[count]: the sum of the depths of the vertices every source reaches"""
+        return self._per_source(lib.mgx_msbfs_far, np.int64)
+
+    def eccentricity(self):
+        """int64[count]: the depth of the deepest vertex every source reaches"""
+        return self._per_source(lib.mgx_msbfs_ecc, np.int64)
+
+    def harmonic(self):
+        """float64[count]: the sum of 1 / depth over the vertices every source reaches (out-entries: see the class)"""
+        return self._per_source(lib.mgx_msbfs_harmonic, np.float64)
+
+    def closeness(self):
+        """float64[count]: reach / far * reach / (n - 1) (Wasserman-Faust; networkx's wf_improved=True), 0 where far == 0; the
+        OUT-closeness on a directed graph"""
+        reach, far = self.reach().astype(np.float64), self.farness().astype(np.float64)
+        n = self.graph.num_nodes
+        out = np.zeros(len(reach), dtype=np.float64)
+        ok = far > 0
+        out[ok] = reach[ok] / far[ok] * (reach[ok] / (n - 1))
+        return out
+
+    def vertex_sums(self):
+        """(reach_in, far_in), int64[n] each: the run's sources that reach every vertex and the sum of their depths there"""
+        n = self.graph.num_nodes
+        r, f = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1), dtype=np.int64)
+        check(lib.mgx_msbfs_vertex_sums(self._h, _ptr(r), _ptr(f)))
+        return r[:n], f[:n]
+
+    def vertex_sums_device_ptrs(self):
+        r, f = C.c_void_p(), C.c_void_p()
+        check(lib.mgx_msbfs_vertex_sums_device(self._h, C.byref(r), C.byref(f)))
+        return r.value, f.value
+
+    def depths(self):
+        """int32[count, n] of the last run with depths=True: -1 where the source does not reach the vertex"""
+        n = self.graph.num_nodes
+        out = np.zeros(max(self._count * n, 1), dtype=np.int32)
+        check(lib.mgx_msbfs_depths(self._h, _ptr(out)))
+        return out[:self._count * n].reshape(self._count, n)
+
+    def level_kinds(self):
+        """PUSH or PULL per (batch, level) of the last run(), the batches behind each other (the first 65536)"""
+        n = C.c_int64()
+        check(lib.mgx_msbfs_level_kinds(self._h, None, 0, C.byref(n)))
+        out = np.zeros(max(min(n.value, 1 << 16), 1), dtype=np.int32)
+        check(lib.mgx_msbfs_level_kinds(self._h, _ptr(out), len(out), C.byref(n)))
+        return out[:min(n.value, 1 << 16)].copy()
+
+    def bins(self):
+        """the last run(): out- and in-rows per body, their segments, the switches as read"""
+        out = (C.c_int64 * 14)()
+        check(lib.mgx_msbfs_bins(self._h, out))
+        return dict(zip(self.BINS, (int(x) for x in out)))
+
+    def set_timing(self, on):
+        """measurement tools: every launch of a run() keeps the device's wall clock per phase"""
+        check(lib.mgx_msbfs_set_timing(self._h, int(bool(on))))
+
+    def phase_ms(self):
+        out = (C.c_double * 4)()
+        check(lib.mgx_msbfs_phase_ms(self._h, out))
+        return dict(zip(self.PHASES, (float(x) for x in out)))
+
+    def close(self):
+        if self._h:
+            lib.mgx_msbfs_free(self._h)
+            self._h = None
+
+
 def modularity(graph, labels, symmetric=False):
     """Modularity of any labelling (labels in [0, n): a numpy array, a torch tensor on the device or a device address) ->
     (Q, S_in, S_sq, W); Q = S_in / W - S_sq / W^2 in double from the three integers the library returns (0.0 when W == 0)."""

@@ -19,6 +19,7 @@
 #include "gunrock/ktruss/ktruss_enactor.hxx"
 #include "gunrock/scc/scc_enactor.hxx"
 #include "gunrock/lpa/lpa_enactor.hxx"
+#include "gunrock/msbfs/msbfs_enactor.hxx"
 #include "gunrock/mst/mst_enactor.hxx"
 #include "gunrock/pagerank/pagerank_enactor.hxx"
 #include "gunrock/pr/pr_enactor.hxx"
@@ -35,6 +36,7 @@
 #include "mgx/ktruss_fused.hpp"
 #include "mgx/scc_fused.hpp"
 #include "mgx/lpa_fused.hpp"
+#include "mgx/msbfs_fused.hpp"
 #include "mgx/mst_fused.hpp"
 #include "mgx/pagerank_fused.hpp"
 #include "mgx/env.hpp"
@@ -190,6 +192,16 @@ struct mgx_lpa_s : mgx_problem_s {
   std::unique_ptr<mgx::lpa_label_stats_t> label_stats;            // lazily: the operator path's stats
   const int* labels = nullptr;                                    // the last run's labels (nullptr: no run yet)
   bool last_fused = false;                                        // which path the trace is read from
+};
+
+struct mgx_msbfs_s : mgx_problem_s {
+  std::unique_ptr<mgx::msbfs_fused_state_t> fused;                // lazily: the fused path's words, lists and state words
+  std::unique_ptr<msbfs::msbfs_state_t> op_state;                 // lazily: the operator path's arrays
+  std::shared_ptr<msbfs::msbfs_problem_t> p;
+  msbfs::msbfs_problem_t::data_slice_t p_slice = {};              // what p points at
+  std::unique_ptr<msbfs::msbfs_enactor_t> e;
+  int last = 0;                                                   // 0: no run yet; 1: the fused path's results; 2: the operator path's
+  long long count = 0;                                            // sources of the last run
 };
 
 struct mgx_dbfs_s {
@@ -3385,6 +3397,173 @@ int mgx_modularity(mgx_graph_t g, const int* d_labels, int symmetric, uint64_t* 
   mgx::u64 r[3];
   g->mod->run(G.d_row_offsets.data(), G.d_col_indices.data(), G.d_col_offsets.data(), G.d_row_indices.data(), d_labels, symmetric, r, ctx);
   out[0] = r[0]; out[1] = r[1]; out[2] = r[2];
+  MGX_CATCH
+}
+
+// ---- bit-parallel multi-source BFS and closeness -----------------------------------
+// the sources as the run takes them (NULL: every vertex), checked before any device work
+static long long msbfs_check_sources(mgx_msbfs_t p, const int* sources, int count, const char* who) {
+  MGX_REQUIRE(p, "NULL argument");
+  MGX_REQUIRE(count >= 0, std::string(who) + ": count must not be negative");
+  const int n = p->graph().num_nodes;
+  if (!sources) return n;
+  for (int i = 0; i < count; ++i) MGX_REQUIRE(sources[i] >= 0 && sources[i] < n, std::string(who) + ": source out of range");
+  return count;
+}
+int mgx_msbfs_create(mgx_graph_t g, mgx_msbfs_t* out) { return create_handle(g, out); }
+int mgx_msbfs_free(mgx_msbfs_t p) { return free_handle(p); }
+int mgx_msbfs_run(mgx_msbfs_t p, const int* sources, int count, int symmetric, int want_depths, int64_t* stats) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  p->last = 0;
+  if (p->fused) p->fused->launches = -1;                     // (a run that is refused leaves nothing to the getters either)
+  const long long cnt = msbfs_check_sources(p, sources, count, "mgx_msbfs_run");
+  auto [ctx, g] = enter(p);
+  if (!p->fused) p->fused.reset(new mgx::msbfs_fused_state_t(g.num_nodes, g.num_edges, ctx));
+  // the in-entries: the rows themselves on the caller's word, else the genuine CSC, else none (every level pushes)
+  const bool csc = !symmetric && !g.csc_is_csr;
+  const int* const io = symmetric ? g.d_row_offsets.data() : (csc ? g.d_col_offsets.data() : nullptr);
+  const int* const ia = symmetric ? g.d_col_indices.data() : (csc ? g.d_row_indices.data() : nullptr);
+  const std::vector<long long> st = p->fused->run(g.d_row_offsets.data(), g.d_col_indices.data(), io, ia, sources, cnt, csc, want_depths != 0, ctx);
+  p->last = 1;
+  p->count = cnt;
+  put_stats(stats, 10, st);
+  MGX_CATCH
+}
+int mgx_msbfs_enact(mgx_msbfs_t p, const int* sources, int count, int symmetric, int want_depths, int64_t* stats) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  (void)symmetric;                                           // (the operator path always pushes)
+  p->last = 0;
+  if (p->fused) p->fused->launches = -1;
+  const long long cnt = msbfs_check_sources(p, sources, count, "mgx_msbfs_enact");
+  auto [ctx, g] = enter(p);
+  const int n = g.num_nodes;
+  if (!p->op_state) p->op_state.reset(new msbfs::msbfs_state_t(n, ctx));
+  msbfs::msbfs_state_t& os = *p->op_state;
+  os.kept_depths = false;
+  os.ensure(cnt, want_depths != 0, n, ctx);
+  long long sum_reach = 0;
+  if (n > 0 && cnt > 0) {
+    if (!p->e) p->e.reset(new msbfs::msbfs_enactor_t(ctx, n, g.num_edges));
+    if (sources) MGX_HIP(mgx::htod(os.d_sources.data(), sources, (size_t)cnt, ctx.stream()));
+    if (want_depths) MGX_HIP(hipMemsetAsync(os.d_depth.data(), 0xff, (size_t)cnt * (size_t)n * sizeof(int), ctx.stream()));
+    const msbfs::msbfs_problem_t::data_slice_t slice = os.slice(n, want_depths != 0, sources != nullptr);
+    if (!p->p || memcmp(&slice, &p->p_slice, sizeof(slice)) != 0) {      // (the arrays grew, or the run wants other ones)
+      p->p = std::make_shared<msbfs::msbfs_problem_t>(p->g->g, slice, ctx);
+      memcpy(&p->p_slice, &slice, sizeof(slice));
+    }
+    p->e->enact(p->p, slice, sources, cnt, ctx);
+    MGX_HIP(mgx::dtoh(os.h_per_src.data(), (const long long*)os.d_per_src.data(), 4 * (size_t)os.cap, ctx.stream()));
+    for (long long s = 0; s < cnt; ++s) sum_reach += os.h_per_src[(size_t)s];
+  }
+  os.kept_depths = want_depths != 0;
+  p->last = 2;
+  p->count = cnt;
+  const bool ran = n > 0 && cnt > 0;
+  put_stats(stats, 10, {cnt, ran ? (cnt + 63) / 64 : 0, ran ? p->e->deepest : 0, sum_reach, ran ? p->e->levels : 0, 0, ran ? p->e->waits + 1 : 0,
+                        ran ? p->e->calls : 0, 0, want_depths ? 1 : 0});
+  MGX_CATCH
+}
+// one of the last run's per-source arrays (0 reach, 1 far, 2 ecc, 3 harm) to the caller's host array
+static void msbfs_per_source(mgx_msbfs_t p, int which, void* host, const char* who) {
+  MGX_REQUIRE(p && host, "NULL argument");
+  require_run(p->last != 0, who);
+  const bool fused = p->last == 1;
+  const std::vector<long long>& h = fused ? p->fused->h_per_src : p->op_state->h_per_src;
+  const size_t cap = (size_t)(fused ? p->fused->src_cap : p->op_state->cap);
+  if (p->count) memcpy(host, h.data() + (size_t)which * cap, (size_t)p->count * sizeof(long long));
+}
+int mgx_msbfs_reach(mgx_msbfs_t p, int64_t* host) {
+  MGX_TRY
+  msbfs_per_source(p, 0, host, "mgx_msbfs_reach");
+  MGX_CATCH
+}
+int mgx_msbfs_far(mgx_msbfs_t p, int64_t* host) {
+  MGX_TRY
+  msbfs_per_source(p, 1, host, "mgx_msbfs_far");
+  MGX_CATCH
+}
+int mgx_msbfs_ecc(mgx_msbfs_t p, int64_t* host) {
+  MGX_TRY
+  msbfs_per_source(p, 2, host, "mgx_msbfs_ecc");
+  MGX_CATCH
+}
+int mgx_msbfs_harmonic(mgx_msbfs_t p, double* host) {
+  MGX_TRY
+  msbfs_per_source(p, 3, host, "mgx_msbfs_harmonic");
+  MGX_CATCH
+}
+int mgx_msbfs_vertex_sums_device(mgx_msbfs_t p, const int64_t** d_reach_in, const int64_t** d_far_in) {
+  MGX_TRY
+  MGX_REQUIRE(p && d_reach_in && d_far_in, "NULL argument");
+  require_run(p->last != 0, "mgx_msbfs_vertex_sums_device");
+  if (p->last == 1) {
+    *d_reach_in = (const int64_t*)p->fused->reach_in();
+    *d_far_in = (const int64_t*)p->fused->far_in();
+  } else {
+    *d_reach_in = (const int64_t*)p->op_state->d_sums.data();
+    *d_far_in = (const int64_t*)(p->op_state->d_sums.data() + p->op_state->N);
+  }
+  MGX_CATCH
+}
+int mgx_msbfs_vertex_sums(mgx_msbfs_t p, int64_t* reach_in, int64_t* far_in) {
+  MGX_TRY
+  MGX_REQUIRE(p && reach_in && far_in, "NULL argument");
+  require_run(p->last != 0, "mgx_msbfs_vertex_sums");
+  if (p->count == 0) {                                       // (a run without sources touches no device array)
+    std::fill(reach_in, reach_in + p->n(), 0);
+    std::fill(far_in, far_in + p->n(), 0);
+    return MGX_OK;
+  }
+  const int64_t* r = nullptr;
+  const int64_t* f = nullptr;
+  if (p->last == 1) { r = (const int64_t*)p->fused->reach_in(); f = (const int64_t*)p->fused->far_in(); }
+  else { r = (const int64_t*)p->op_state->d_sums.data(); f = r + p->op_state->N; }
+  read_back(p, reach_in, r, p->n());
+  read_back(p, far_in, f, p->n());
+  MGX_CATCH
+}
+int mgx_msbfs_depths(mgx_msbfs_t p, int* host) {
+  MGX_TRY
+  MGX_REQUIRE(p && host, "NULL argument");
+  require_run(p->last != 0, "mgx_msbfs_depths");
+  const bool kept = p->last == 1 ? p->fused->kept_depths : p->op_state->kept_depths;
+  MGX_REQUIRE(kept, "mgx_msbfs_depths: the last run kept no depths (want_depths = 0)");
+  const int* d = p->last == 1 ? p->fused->depth.data() : p->op_state->d_depth.data();
+  read_back(p, host, d, (size_t)p->count * p->n());
+  MGX_CATCH
+}
+int mgx_msbfs_level_kinds(mgx_msbfs_t p, int* host_kinds, int cap, int64_t* levels) {
+  MGX_TRY
+  MGX_REQUIRE(p && levels && cap >= 0 && (host_kinds || cap == 0), "bad argument");
+  require_run(p->fused && p->fused->launches >= 0, "mgx_msbfs_level_kinds");
+  *levels = p->fused->levels;
+  const long long have = std::min<long long>(std::min<long long>(p->fused->levels, mgx::MSBFS_LOG_CAP), cap);
+  read_back(p, host_kinds, (const int*)p->fused->ctl.data()->log, (size_t)have);
+  MGX_CATCH
+}
+int mgx_msbfs_bins(mgx_msbfs_t p, int64_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->fused && p->fused->launches >= 0, "mgx_msbfs_bins");
+  const mgx::msbfs_fused_state_t& f = *p->fused;
+  for (int i = 0; i < mgx::MSBFS_BINS; ++i) out[i] = f.bins[i];
+  out[10] = f.opts.short_max; out[11] = f.opts.wave_max; out[12] = f.opts.seg; out[13] = f.opts.pull_div;
+  MGX_CATCH
+}
+int mgx_msbfs_set_timing(mgx_msbfs_t p, int on) {
+  MGX_TRY
+  auto [ctx, g] = enter(p);
+  if (!p->fused) p->fused.reset(new mgx::msbfs_fused_state_t(g.num_nodes, g.num_edges, ctx));
+  p->fused->timing = on != 0;
+  MGX_CATCH
+}
+int mgx_msbfs_phase_ms(mgx_msbfs_t p, double* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->fused && p->fused->launches >= 0, "mgx_msbfs_phase_ms");
+  for (int i = 0; i < 4; ++i) out[i] = p->fused->phase_ms[i];
   MGX_CATCH
 }
 
