@@ -729,6 +729,11 @@ MGX_API int mgx_pagerank_ranks(mgx_pagerank_t p, float* host_ranks);
 MGX_API int mgx_pagerank_ranks_device(mgx_pagerank_t p, const float** d_ranks);
 /* e_1 .. of the last run: min(cap, iterations, 65536) values into host_e; *iterations (may be NULL) = iterations run */
 MGX_API int mgx_pagerank_residuals(mgx_pagerank_t p, double* host_e, int cap, int* iterations);
+/* which class of the general reduce took the in-rows of the last mgx_pagerank_run (MGX_E_INVALID before any): out[4] = rows in the
+ * huge list (a workgroup each; 0 after a run on the layout), PGR_LANE_MAX (rows of at most so many entries a lane each),
+ * PGR_HUGE_MIN (rows of at least so many a workgroup each; the others a wave each), PGR_HUGE_BLOCKS (workgroups that stride over
+ * the huge list).  Reports; steers nothing. */
+MGX_API int mgx_pagerank_bins(mgx_pagerank_t p, int64_t* out);
 
 /* ---- minimum spanning forest (include/mgx/mst_fused.hpp, include/gunrock/mst/) ----
  * Every CSR entry (v, u, w) is the undirected edge {v, u} of the graph's float weight w (1.0f when none were uploaded); self-loops

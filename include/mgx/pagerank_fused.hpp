@@ -275,6 +275,7 @@ struct pagerank_state_t {
   const float* result = nullptr;     // the last run's ranks by original id (nullptr: no run yet)
   int trace_cap = 0;
   int last_iterations = 0;
+  int last_huge_rows = -1;           // the last fused run's huge list (0 after a layout run; -1: no fused run yet)
 
   pagerank_state_t(int n_, context_t& ctx) : n(n_) {
     const size_t N = (size_t)std::max(n, 1);
@@ -419,10 +420,14 @@ struct pagerank_state_t {
       result = rank.data();
     }
     last_iterations = c.iterations;
+    last_huge_rows = layout ? 0 : c.huge_rows;
     out.iterations = c.iterations; out.converged = c.converged; out.dangling = c.dangling; out.layout_path = layout ? 1 : 0;
     out.residual = c.e;
     return out;
   }
+
+  // which class took the rows of the last fused run, and the constants that draw the classes (mgx_pagerank_bins); reports only
+  std::vector<long long> bins() const { return {last_huge_rows, PGR_LANE_MAX, PGR_HUGE_MIN, PGR_HUGE_BLOCKS}; }
 };
 
 }  // namespace mgx

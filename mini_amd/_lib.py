@@ -259,6 +259,7 @@ SIGNATURES = {
     "mgx_pagerank_ranks": [_vp, _vp],
     "mgx_pagerank_ranks_device": [_vp, _pvp],
     "mgx_pagerank_residuals": [_vp, C.POINTER(C.c_double), _i, _pi],
+    "mgx_pagerank_bins": [_vp, _pi64],
     "mgx_mst_create": [_vp, _pvp],
     "mgx_mst_free": [_vp],
     "mgx_mst_run": [_vp, _i, _pi64],

@@ -1502,6 +1502,13 @@ class PageRankProblem:
         check(lib.mgx_pagerank_residuals(self._h, out.ctypes.data_as(C.POINTER(C.c_double)), int(cap), C.byref(it)))
         return out[:min(int(cap), it.value)].copy()
 
+    def bins(self):
+        """which class of the general reduce took the in-rows of the last run() (huge_rows is 0 after a layout run), and the constants
+        that draw the classes"""
+        out = (C.c_int64 * 4)()
+        check(lib.mgx_pagerank_bins(self._h, out))
+        return dict(zip(("huge_rows", "lane_max", "huge_min", "huge_blocks"), (int(x) for x in out)))
+
     def close(self):
         if self._h:
             lib.mgx_pagerank_free(self._h)

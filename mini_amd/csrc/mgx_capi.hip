@@ -2922,6 +2922,13 @@ int mgx_pagerank_residuals(mgx_pagerank_t p, double* host_e, int cap, int* itera
   read_back(p, host_e, (const double*)s.trace.data(), (size_t)std::max(std::min(std::min(cap, s.last_iterations), s.trace_cap), 0));
   MGX_CATCH
 }
+int mgx_pagerank_bins(mgx_pagerank_t p, int64_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->p && p->p->state.last_huge_rows >= 0, "mgx_pagerank_bins");
+  put_stats(out, 4, p->p->state.bins());
+  MGX_CATCH
+}
 
 
 // ---- minimum spanning forest -----------------------------------------------------------

@@ -103,7 +103,7 @@ def test_symmetric_flag_reads_the_rows_as_they_stand():
 # ---- the library side that needs no GPU --------------------------------------------------------------------------------------------
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["mgx_pagerank_create", "mgx_pagerank_free", "mgx_pagerank_run", "mgx_pagerank_enact", "mgx_pagerank_ranks",
-         "mgx_pagerank_ranks_device", "mgx_pagerank_residuals"]
+         "mgx_pagerank_ranks_device", "mgx_pagerank_residuals", "mgx_pagerank_bins"]
 KERNELS = ["k_pagerank_init", "k_pagerank_begin", "k_pagerank_reduce", "k_pagerank_huge_list", "k_pagerank_reduce_huge",
            "k_pagerank_update", "k_pagerank_verdict", "k_pagerank_unpermute", "k_pagerank_iota"]
 
@@ -127,6 +127,7 @@ def test_null_arguments_are_invalid(built):
     assert lib.mgx_pagerank_ranks(None, None) == mini_amd.MGX_E_INVALID
     assert lib.mgx_pagerank_ranks_device(None, C.byref(p)) == mini_amd.MGX_E_INVALID
     assert lib.mgx_pagerank_residuals(None, None, 0, C.byref(it)) == mini_amd.MGX_E_INVALID
+    assert lib.mgx_pagerank_bins(None, None) == mini_amd.MGX_E_INVALID
     assert lib.mgx_pagerank_free(None) == 0
 
 
