@@ -155,6 +155,7 @@ struct bfs_fused_args_t {
   u32 ub_hot_only;         // ub_col24 / ub_owner / ub_units_pad are the blocks WITHOUT the entries of the cold-edge lists: for the slots that run
                            // the cold-edge pass.  A slot that reads unit blocks without the pass (a sparse level behind a lazy build) takes the
                            // full blocks: ub_col (32 bits) or ubf_col24, ubf_owner, ubf_units_pad (bfs_dense_body)
+                           // 2: the same, and ub_col24 holds those blocks' entries at 20 bits (mgx/pack20.hpp), not at 24
   const u32* ubf_col24;
   const int* ubf_owner;
   u32 ubf_units_pad;
@@ -1145,6 +1146,7 @@ struct bfs_run_opts_t {
   int vshort = -1;         // MGX_BFS_VSHORT: 0 never, N > 0 vshort_div = N
   long long chain = -1;    // MGX_BFS_CHAIN_MAX_EDGES: 0 never (default BFS_CHAIN_CAP)
   int pack24 = 1;                     // MGX_BFS_PACK24=0
+  int pack20 = 1;                     // MGX_BFS_PACK20=0: the blocks without the cold entries at 24 bits (a layout that carries them at 20 only: the full blocks)
   int hot_units = 1;                  // MGX_BFS_HOT_UNITS=0: the full unit blocks even when the layout carries the ones without the cold entries
   int cold_pack = 1;                  // MGX_BFS_COLD_PACK=0: the cold-edge pass reads its pairs at eight bytes each: the unit-block body reads the 32-bit entries even when the graph carries the 24-bit copy
   int src_plan = 1;                   // MGX_BFS_SRC_PLAN=0: every traversal gets the same launch sequence (no per-source classes)
@@ -1190,6 +1192,7 @@ struct bfs_run_opts_t {
     geti("MGX_BFS_DEFER_WORDS", o.defer_words);
     geti("MGX_BFS_SRC_PLAN", o.src_plan);
     geti("MGX_BFS_PACK24", o.pack24);
+    geti("MGX_BFS_PACK20", o.pack20);
     geti("MGX_BFS_COLD_PACK", o.cold_pack);
     geti("MGX_BFS_HOT_UNITS", o.hot_units);
     geti("MGX_BFS_COLD", o.cold);

@@ -29,6 +29,7 @@
 #pragma once
 #include <type_traits>
 #include "bfs_fused.hpp"
+#include "pack20.hpp"
 
 namespace mgx {
 
@@ -45,6 +46,13 @@ __device__ __forceinline__ bfs_u32x4 bfs_unpack24(bfs_u32x3 w) {
   d.w = (u32)((int)w.z >> 8);
   return d;
 }
+
+// eight 20-bit entries out of five words (mgx/pack20.hpp: lane l of a 512-entry chunk holds its entries 8 l .. 8 l + 7 as one
+// 16-byte and one 4-byte word group), zero-extended: the 12 vector instructions per eight entries that bfs_unpack24 takes.  NOT
+// sign-extended -- the ids of these blocks use bit 19 -- so "no entry" stays 0xFFFFF: a vertex behind the LDS prefix, whose probe
+// reads hot[HOTW].  The blocks are read only by slots that run the cold-edge pass, where that word is all ones: visited, like -1.
+struct bfs_raw20_t { bfs_u32x4 a; u32 b; };
+__device__ __forceinline__ void bfs_unpack20(const bfs_raw20_t& r, u32 d[8]) { unpack20(r.a.x, r.a.y, r.a.z, r.a.w, r.b, d); }
 
 constexpr int BFS_DENSE_GROUP = 16;                 // units per group (the unit of interleaving)
 constexpr size_t bfs_dense_lds_bytes(int hotw) { return (size_t)hotw * 4 + 128; }
@@ -71,10 +79,11 @@ __device__ __forceinline__ u32* bfs_hot_setup(const bfs_fused_args_t& a, char* s
   return hot;
 }
 
-// the blocks a pass reads: entries at 32 or at 24 bits, owners, units (padded to a multiple of 16)
+// the blocks a pass reads: entries at 32, 24 or 20 bits, owners, units (padded to a multiple of 16)
 struct bfs_units_view_t {
   const int* col;
   const u32* col24;
+  const u32* col20;
   const int* owner;
   u32 units_pad;
 };
@@ -83,8 +92,13 @@ struct bfs_units_view_t {
 // P24: the entries come from a 24-bit copy of the unit blocks (ub.col24: the full blocks of a graph of at most 2^23 vertices, or the
 // blocks without the cold-edge lists' entries, whose ids lie inside the LDS prefix): 12 bytes per lane and load instead of 16,
 // unpacked when they are tested
+// FMT 20: the blocks without the cold-edge lists' entries at 20 bits (ub.col20, mgx/pack20.hpp): a group of 16 units is two chunks
+// of 512 entries, per chunk one 16-byte and one 4-byte load -- four loads per group as before, 20 bytes per lane and chunk instead
+// of 2 x 12; a lane's eight entries belong to unit lane >> 3 of its chunk
 
-template <int NT, int HOTW, int GPS, bool P24 = false>
+// ROLL: the four steps of a batch as a loop, not unrolled -- a quarter of the code for a few scalar instructions per group
+// (bfs_dense_body: ROLL32).
+template <int NT, int HOTW, int GPS, int FMT = 32, bool ROLL = false>
 __device__ __forceinline__ void bfs_dense_work(const bfs_fused_args_t& a, const bfs_units_view_t ub, u32* const hot, u32 hot_n, u32 defer_n, u32 block,
                                                u32 nblocks, int& marks) {
   constexpr int NW = NT / WAVE;
@@ -102,6 +116,9 @@ __device__ __forceinline__ void bfs_dense_work(const bfs_fused_args_t& a, const 
   const u32 lane_unit = (u32)lane & 15u;                       // my unit inside its group, for the owner load ...
   const u32 lane_grp = (u32)lane >> 4;                         // ... and which of the batch's 4 groups
   const u32 lane_q = (u32)lane >> 4;                           // col loads: lane l reads entries 4l..4l+3 of a 256-entry chunk = unit l >> 4 of the chunk
+  constexpr bool P24 = FMT == 24, P20 = FMT == 20;
+  const u32 lane_o = (u32)lane >> 3;                           // 20-bit entries: lane l reads entries 8l..8l+7 of a 512-entry chunk = unit l >> 3 of the chunk,
+  const u32 lane_a = (u32)lane * 4u, lane_b = PACK20_PLANE_B + (u32)lane;      // its words 0..3 and its word 4 inside the chunk
 
   // batch b of this wave: groups w + (4 b + k) W, k = 0..3
   const u32 nbatch = (w < G) ? ((G - w + W - 1) / W + 3) / 4 : 0u;
@@ -119,16 +136,29 @@ __device__ __forceinline__ void bfs_dense_work(const bfs_fused_args_t& a, const 
       return (g < G ? g : 0u) * (BFS_DENSE_GROUP * 64u);
     };
 
-    constexpr int NL = 4 * GPS;               // loads per step
-    typedef typename std::conditional<P24, bfs_u32x3, bfs_u32x4>::type raw_t;     // what a lane's load returns
+    constexpr int NL = (P20 ? 2 : 4) * GPS;   // loads per step (20 bits: load pairs)
+    typedef typename std::conditional<P20, bfs_raw20_t, typename std::conditional<P24, bfs_u32x3, bfs_u32x4>::type>::type raw_t;     // what a lane's load returns
     raw_t dL[NL], dT[NL];
     const u32* __restrict__ ucol24 = ub.col24;
+    const u32* __restrict__ ucol20 = ub.col20;
+    const u32 dummy20 = (ub.units_pad >> 3) * PACK20_CHUNK_WORDS;    // word index of the all-ones slack behind the last chunk
     // issue the 16-byte loads of groups k .. k + GPS - 1 of a batch whose activity bits are `act`
     auto issue = [&](u32 b, u32 k, u64 act) {
 #pragma unroll
       for (int g = 0; g < GPS; ++g) {
         const u32 base = group_base(b, k + (u32)g);
         const u32 bits16 = (u32)(act >> (16u * (k + (u32)g))) & 0xFFFFu;
+        if constexpr (P20) {
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            const bool on = (bits16 >> (8u * j + lane_o)) & 1u;
+            const u32 cw = ((base >> 9) + (u32)j) * PACK20_CHUNK_WORDS;          // the chunk's first word (base: a multiple of 1024 entries)
+            const u32 wa = on ? cw + lane_a : dummy20;
+            const u32 wb = on ? cw + lane_b : dummy20 + 4u;
+            dL[2 * g + j].a = __builtin_nontemporal_load((const bfs_u32x4*)(ucol20 + wa));
+            dL[2 * g + j].b = __builtin_nontemporal_load(ucol20 + wb);
+          }
+        } else
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const bool on = (bits16 >> (4u * j + lane_q)) & 1u;
@@ -165,17 +195,28 @@ __device__ __forceinline__ void bfs_dense_work(const bfs_fused_args_t& a, const 
       if (diag & 2) {                  // measurement only: consume the loads, test nothing
 #pragma unroll
         for (int j = 0; j < NL; ++j) {
-          if constexpr (P24) marks += (int)((dT[j].x ^ dT[j].y ^ dT[j].z) == 0x12345678u);
+          if constexpr (P20) marks += (int)((dT[j].a.x ^ dT[j].a.y ^ dT[j].a.z ^ dT[j].a.w ^ dT[j].b) == 0x12345678u);
+          else if constexpr (P24) marks += (int)((dT[j].x ^ dT[j].y ^ dT[j].z) == 0x12345678u);
           else marks += (int)((dT[j].x ^ dT[j].y ^ dT[j].z ^ dT[j].w) == 0x12345678u);
         }
         return;
       }
 #pragma unroll
       for (int j = 0; j < NL; ++j) {
-        bfs_u32x4 d;
-        if constexpr (P24) d = bfs_unpack24(dT[j]); else d = dT[j];
-        const u32 w0 = probe(d.x), w1 = probe(d.y), w2 = probe(d.z), w3 = probe(d.w);
-        decide(d.x, w0); decide(d.y, w1); decide(d.z, w2); decide(d.w, w3);
+        if constexpr (P20) {
+          u32 e[8];
+          bfs_unpack20(dT[j], e);
+#pragma unroll
+          for (int h = 0; h < 8; h += 4) {
+            const u32 w0 = probe(e[h]), w1 = probe(e[h + 1]), w2 = probe(e[h + 2]), w3 = probe(e[h + 3]);
+            decide(e[h], w0); decide(e[h + 1], w1); decide(e[h + 2], w2); decide(e[h + 3], w3);
+          }
+        } else {
+          bfs_u32x4 d;
+          if constexpr (P24) d = bfs_unpack24(dT[j]); else d = dT[j];
+          const u32 w0 = probe(d.x), w1 = probe(d.y), w2 = probe(d.z), w3 = probe(d.w);
+          decide(d.x, w0); decide(d.y, w1); decide(d.z, w2); decide(d.w, w3);
+        }
       }
     };
 
@@ -206,8 +247,13 @@ __device__ __forceinline__ void bfs_dense_work(const bfs_fused_args_t& a, const 
       const u32 own_cur = own_next;
       const u32 fw = gather_bits(own_cur);
       own_next = load_owner(b + 2);
+      if constexpr (ROLL) {
+#pragma unroll 1
+        for (u32 k = 0; k < 4; k += GPS) step(b, k, act);
+      } else {
 #pragma unroll
-      for (u32 k = 0; k < 4; k += GPS) step(b, k, act);
+        for (u32 k = 0; k < 4; k += GPS) step(b, k, act);
+      }
       act = __ballot((fw >> (own_cur & 31u)) & 1u);
     }
     if (pend) {
@@ -220,7 +266,13 @@ __device__ __forceinline__ void bfs_dense_work(const bfs_fused_args_t& a, const 
 
 // GPS: groups per step (1: four 16-byte loads in flight per lane while the previous four are tested; 2: eight -- for
 // launches with half the waves per CU)
-template <int NT, int HOTW, int GPS = 1>
+// P20: the kernel may meet 20-bit blocks (a.ub_hot_only == 2: the single-GPU traversal's; the partitioned ranks' blocks stay at 24 bits)
+// ROLL32: the 32-bit body's steps as a loop.  For the long-rows launch of the timing runs (k_bfs_push<false, 2>): with three unrolled
+// bodies it grows past the size where the compiler sets an SGPR pair aside for long branches and spills one (the launch must spill
+// nothing: tests/test_capi_boundary.py); the merged launch is past that size anyway and pays three more spilled SGPRs for the loop,
+// so it keeps the body unrolled.  Few levels take the 32-bit body there: MGX_BFS_PACK24=0, or a level without the cold-edge pass
+// on a graph of more than 2^23 vertices.
+template <int NT, int HOTW, int GPS = 1, bool P20 = false, bool ROLL32 = false>
 __device__ __forceinline__ void bfs_dense_body(const bfs_fused_args_t& a, int slot, u32 block, u32 nblocks, int stat_level,
                                                bool cold = false) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -232,10 +284,17 @@ __device__ __forceinline__ void bfs_dense_body(const bfs_fused_args_t& a, int sl
   const u32 defer_n = bfs_defer_limit(a, hot_n);      // marks of the vertices in [0, defer_n) wait for the end of the workgroup
   int marks = 0;
   // (grid-uniform) the blocks without the cold-edge lists' entries are for the slots that run the cold-edge pass
-  bfs_units_view_t ub{a.ub_col, a.ub_col24, a.ub_owner, a.ub_units_pad};
-  if (a.ub_hot_only && !cold) { ub.col24 = a.ubf_col24; ub.owner = a.ubf_owner; ub.units_pad = a.ubf_units_pad; }
-  if (ub.col24) bfs_dense_work<NT, HOTW, GPS, true>(a, ub, hot, hot_n, defer_n, block, nblocks, marks);
-  else bfs_dense_work<NT, HOTW, GPS, false>(a, ub, hot, hot_n, defer_n, block, nblocks, marks);
+  // (the 20-bit entries are those blocks' and nobody else's: their "no entry" reads as visited only while hot[HOTW] is all ones)
+  //  (a branch of its own in front of the others: it asks for its three arguments and nothing else)
+  if (P20 && cold && a.ub_hot_only == 2u) {
+    const bfs_units_view_t ub{nullptr, nullptr, a.ub_col24, a.ub_owner, a.ub_units_pad};
+    bfs_dense_work<NT, HOTW, GPS, 20>(a, ub, hot, hot_n, defer_n, block, nblocks, marks);
+  } else {
+    bfs_units_view_t ub{a.ub_col, a.ub_col24, nullptr, a.ub_owner, a.ub_units_pad};
+    if (a.ub_hot_only && !cold) { ub.col24 = a.ubf_col24; ub.owner = a.ubf_owner; ub.units_pad = a.ubf_units_pad; }
+    if (ub.col24) bfs_dense_work<NT, HOTW, GPS, 24>(a, ub, hot, hot_n, defer_n, block, nblocks, marks);
+    else bfs_dense_work<NT, HOTW, GPS, 32, ROLL32>(a, ub, hot, hot_n, defer_n, block, nblocks, marks);
+  }
   (void)bfs_hot_epilogue<NT>(a, hot, (defer_n + 31u) >> 5, slot, s_int + 4, marks);
   bfs_body_finish(a, marks, slot, stat_level, s_int);
 }

@@ -174,7 +174,7 @@ __global__ __launch_bounds__(1024, 8) void k_bfs_push(bfs_fused_args_t a, int ar
   const bool long_part = PART == 2 || (PART == 0 && blk < nstream);
   if (long_part) {
     const u32 bi = blk;
-    if (!COLDT && p.dense) bfs_dense_body<1024, BFS_DENSE_HOTW>(a, p.slot, bi, nstream, p.level, p.cold);
+    if (!COLDT && p.dense) bfs_dense_body<1024, BFS_DENSE_HOTW, 1, true, PART == 2>(a, p.slot, bi, nstream, p.level, p.cold);
     else bfs_stream_body<1024, BFS_STREAM_HOTW2, 8, COLDT, false, true>(a, p.slot, bi, nstream, p.level);
   } else {
     const u32 first = PART == 0 ? nstream : 0u;
@@ -453,13 +453,15 @@ inline bfs_launch_plan_t bfs_fused_plan(bfs_fused_state_t& st, const int* row_of
   // ... and then the unit blocks WITHOUT the lists' entries (every level that reads unit blocks runs the cold-edge pass: the body
   // reads those entries only to skip them), at 24 bits whatever the graph's size.  Round 5, as the partitioned ranks have had
   // them since round 4 (mgx_capi.hip): see the note at the layout's builder for what they are worth.
-  const bool hot_units = cold_lists && st.opts.pack24 && st.opts.hot_units && R.ubh.col24.data() && R.ubh.owner.data() && R.ubh.units > 0 &&
+  // (their entries at 20 bits -- mgx/pack20.hpp -- where the layout packed them so, INSTEAD of the 24-bit ones, and the run may read them)
+  const bool hot20 = st.opts.pack20 && R.ubh.col20.data() != nullptr;
+  const bool hot_units = cold_lists && st.opts.pack24 && st.opts.hot_units && (R.ubh.col24.data() || hot20) && R.ubh.owner.data() && R.ubh.units > 0 &&
                          (opt.dense < 0 || opt.dense > 0);
   if (hot_units) {
-    a.ub_col24 = R.ubh.col24.data(); a.ub_owner = R.ubh.owner.data();     // (a.ub_col: the full blocks' -- not read by the 24-bit body)
+    a.ub_col24 = hot20 ? R.ubh.col20.data() : R.ubh.col24.data(); a.ub_owner = R.ubh.owner.data();     // (a.ub_col: the full blocks' -- not read by the 24- and 20-bit bodies)
     a.ub_units = (u32)R.ubh.units; a.ub_units_pad = (u32)R.ubh.units_pad;
   }
-  a.ub_hot_only = hot_units ? 1u : 0u;
+  a.ub_hot_only = hot_units ? (hot20 ? 2u : 1u) : 0u;
   a.ubf_col24 = hot_units ? R.ub.col24.data() : nullptr; a.ubf_owner = hot_units ? R.ub.owner.data() : nullptr;
   a.ubf_units_pad = hot_units ? (u32)R.ub.units_pad : 0u;
   const bool packed = units && st.opts.pack24 && (R.ub.col24.data() != nullptr || hot_units);

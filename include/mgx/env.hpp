@@ -30,6 +30,7 @@ inline const env_switch_t* env_switches(int* count) {
     {"MGX_BFS_FLAT_LISTS", "0: a flat graph keeps the ordinary layout instead of all-entry pair lists"},
     {"MGX_BFS_HOT_UNITS", "0: no second copy of the unit blocks without the cold lists' entries"},
     {"MGX_BFS_PACK24", "0: 32-bit unit-block entries instead of the 24-bit copy"},
+    {"MGX_BFS_PACK20", "0: the unit blocks without the cold lists' entries at 24 bits per entry instead of 20"},
     {"MGX_BFS_MINI", "0 / 2: no M launches / M launches on every graph (default: from 2^22 vertices on)"},
     {"MGX_BFS_BATCH_OVERLAP", "0: a batch of sources runs in one traversal state, no launch shared by two traversals"},
     {"MGX_BFS_SEED_CHAIN", "0: the chain of small levels at the start runs inside slot 0's push launch"},

@@ -12,6 +12,8 @@ namespace mgx {
 struct unit_blocks_t {
   mem_t<int> col;                    // (units_pad << 6) + 4 entries, padding -1; empty when only the 24-bit copy is kept
   mem_t<unsigned> col24;             // the same, 24 bits each (3 bytes: 4 entries = 12 bytes, -1 = 0xFFFFFF); empty: none
+  mem_t<unsigned> col20;             // the same, 20 bits each in chunks of 512 entries (mgx/pack20.hpp, -1 = 0xFFFFF): only for blocks whose ids
+                                     // all lie below 2^20 - 1 (the ones without the cold-edge lists' entries), INSTEAD of col24; empty: none
   mem_t<int> owner;                  // units_pad: the row of unit u (padding units: a vertex that is never in a frontier)
   mem_t<unsigned char> cnt;          // real entries of every unit (a graph's full blocks: the neighbour-reduce counts them)
   mem_t<int> first;                  // n + 1: the units of row v are [first[v], first[v + 1]) (a graph's full blocks)
@@ -23,8 +25,9 @@ struct row_layout_t {
   // the long rows' unit blocks: rows of >= ub_min_degree entries
   unit_blocks_t ub;
   int ub_min_degree = 0;
-  // the same rows WITHOUT the entries that live in the cold-edge lists (what is left points into the LDS prefix): 24 bits per entry
-  // whatever the graph's size, owners of their own; a rank keeps the 32-bit entries too (and drops the full blocks)
+  // the same rows WITHOUT the entries that live in the cold-edge lists (what is left points into the LDS prefix): 20 bits per entry
+  // on a whole graph (MGX_BFS_PACK20=0: 24), 24 on a rank, whatever the graph's size, owners of their own; a rank keeps the 32-bit
+  // entries too (and drops the full blocks)
   unit_blocks_t ubh;
   // degree classes of the short rows (bfs_fused_vshort.hpp): class boundaries of the degree-sorted rows, edges of [vs_v[0], vs_v[3]),
   // the long-row threshold they were cut for, index of four -1 behind the neighbour array (0: not available)
@@ -63,6 +66,8 @@ void build_unit_blocks(unit_blocks_t& ub, const int* ro, const int* ci, int n, i
                        bool keep_index, hipStream_t s);
 // their 24-bit copy (ub.units > 0), for which the 32-bit entries go unless keep_col
 void pack_unit_blocks24(unit_blocks_t& ub, bool keep_col, hipStream_t s);
+// their 20-bit copy (ub.units > 0, every id below 2^20 - 1), for which the 32-bit entries go
+void pack_unit_blocks20(unit_blocks_t& ub, hipStream_t s);
 // first row of fewer than d entries, of rows [0, n) by non-increasing degree (h_ro: a host copy of their n + 1 offsets)
 unsigned first_row_below(const std::vector<int>& h_ro, size_t n, int d);
 // vs_v, vs_v9 and vs_edges of those rows for the long-row threshold long_min

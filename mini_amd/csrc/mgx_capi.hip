@@ -706,8 +706,15 @@ static void build_cold_lists(mgx_graph_s* g) {
   if (const char* e = mgx::env("MGX_BFS_HOT_UNITS")) hot_units = atoi(e) != 0;
   if (const char* e = mgx::env("MGX_BFS_PACK24")) hot_units = hot_units && atoi(e) != 0;
   if (!hot_units) return;
+  // Their ids lie below hot_n = 652 288 < 2^20 - 1: 20 bits per entry (mgx/pack20.hpp) INSTEAD of 24 -- a sixth off the stream that
+  // dominates the push kernel and off the blocks' memory.  MGX_BFS_PACK20=0: 24 bits, as before.
+  bool pack20 = hot_n < 0xFFFFFu;
+  if (const char* e = mgx::env("MGX_BFS_PACK20")) pack20 = pack20 && atoi(e) != 0;
   mgx::build_unit_blocks(R.ubh, ro, ci, G.num_nodes, R.vs_long_min, hot_n, mgx::owner_remap_t(), false, s);
-  if (R.ubh.units > 0) mgx::pack_unit_blocks24(R.ubh, false, s);
+  if (R.ubh.units > 0) {
+    if (pack20) mgx::pack_unit_blocks20(R.ubh, s);
+    else mgx::pack_unit_blocks24(R.ubh, false, s);
+  }
 }
 int mgx_graph_build_layout(mgx_graph_t g, int with_weights) {
   MGX_TRY
@@ -804,7 +811,7 @@ int mgx_graph_layout_info(mgx_graph_t g, int64_t* out8) {
   out8[6] = R.cold_majority ? 1 : 0;
   auto bytes = [](auto& m) -> int64_t { return m.owned() ? (int64_t)(m.size() * sizeof(*m.data())) : 0; };
   out8[7] = bytes(G.d_layout_row_offsets) + bytes(G.d_layout_col_indices) + bytes(G.d_layout_col_values) + bytes(G.d_new_of_old) + bytes(G.d_old_of_new) +
-            bytes(R.ub.col) + bytes(R.ub.col24) + bytes(R.ub.owner) + bytes(R.ubh.col24) + bytes(R.ubh.owner) + bytes(G.d_ub_w) + bytes(G.d_ub_w16) +
+            bytes(R.ub.col) + bytes(R.ub.col24) + bytes(R.ub.owner) + bytes(R.ubh.col24) + bytes(R.ubh.col20) + bytes(R.ubh.owner) + bytes(G.d_ub_w) + bytes(G.d_ub_w16) +
             bytes(R.ub.cnt) + bytes(R.ub.first) + bytes(R.cold_owner) + bytes(R.cold_dst) + bytes(R.cold_pk) + bytes(R.cold_cbase) +
             bytes(R.colds_owner) + bytes(R.colds_dst) + bytes(G.d_nrs_mu) + bytes(G.d_nrs_off) + bytes(G.d_nr_pos);
   MGX_CATCH

@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <string>
 
+#include "mgx/pack20.hpp"
 #include "mgx/row_layout.hpp"
 #include "mgx/wave.hpp"
 
@@ -412,6 +413,21 @@ __global__ __launch_bounds__(256) void k_pack24(const int4* __restrict__ in, lon
     out[3 * q + 2] = (c >> 16) | (d << 8);
   }
 }
+// 32-bit entries -> 20-bit ones in chunks of 512 (mgx/pack20.hpp): thread t is lane t & 63 of chunk t >> 6 and packs the chunk's
+// entries 8 l .. 8 l + 7 into its five words; the eight threads behind the last chunk write the all-ones slack
+__global__ __launch_bounds__(256) void k_pack20(const int4* __restrict__ in, long long slots, unsigned* __restrict__ out) {
+  for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < slots + (long long)mgx::PACK20_SLACK_WORDS; t += (long long)gridDim.x * blockDim.x) {
+    if (t >= slots) { out[(size_t)(slots >> 6) * mgx::PACK20_CHUNK_WORDS + (size_t)(t - slots)] = 0xFFFFFFFFu; continue; }
+    const int4 lo = in[2 * t], hi = in[2 * t + 1];
+    const int e[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    unsigned w[5];
+    mgx::pack20(e, w);
+    const size_t chunk = (size_t)(t >> 6);
+    const unsigned lane = (unsigned)t & 63u;
+    *(uint4*)(out + mgx::pack20_word_a(chunk, lane)) = make_uint4(w[0], w[1], w[2], w[3]);
+    out[mgx::pack20_word_b(chunk, lane)] = w[4];
+  }
+}
 }  // namespace
 }  // extern "C"
 
@@ -466,6 +482,19 @@ void pack_unit_blocks24(unit_blocks_t& ub, bool keep_col, hipStream_t s) {
   hipLaunchKernelGGL(k_pack24, dim3(grid_for(quads, 256, 16384)), dim3(256), 0, s, (const int4*)ub.col.data(), quads, ub.col24.data());
   MGX_HIP(hipStreamSynchronize(s));
   if (!keep_col) ub.col = mem_t<int>();
+}
+
+void pack_unit_blocks20(unit_blocks_t& ub, hipStream_t s) {
+  // units_pad is a multiple of 16: whole chunks of 8 units; a thread per lane of a chunk (8 entries)
+  const long long slots = ub.units_pad << 3;
+  const size_t words = pack20_words((size_t)ub.units_pad << 6);
+  unsigned* col20 = nullptr;
+  const hipError_t e = hipMalloc((void**)&col20, words * sizeof(unsigned));
+  if (e != hipSuccess) throw_hip("unit blocks, 20-bit copy: ", (int)e);
+  ub.col20 = mem_t<unsigned>::adopt(col20, words);
+  hipLaunchKernelGGL(k_pack20, dim3(grid_for(slots + PACK20_SLACK_WORDS, 256, 16384)), dim3(256), 0, s, (const int4*)ub.col.data(), slots, ub.col20.data());
+  MGX_HIP(hipStreamSynchronize(s));
+  ub.col = mem_t<int>();
 }
 
 unsigned first_row_below(const std::vector<int>& h, size_t n, int d) {
