@@ -53,6 +53,7 @@ typedef struct mgx_ktruss_s* mgx_ktruss_t;
 typedef struct mgx_scc_s* mgx_scc_t;
 typedef struct mgx_lpa_s* mgx_lpa_t;
 typedef struct mgx_msbfs_s* mgx_msbfs_t;
+typedef struct mgx_rw_s* mgx_rw_t;
 typedef struct mgx_dbfs_s* mgx_dbfs_t;
 typedef struct mgx_dbfs2_s* mgx_dbfs2_t;
 typedef struct mgx_dsssp_s* mgx_dsssp_t;
@@ -954,6 +955,60 @@ MGX_API int mgx_msbfs_bins(mgx_msbfs_t p, int64_t* out);
  * FINALIZE launches (RESET and SEED count as FINALIZE) */
 MGX_API int mgx_msbfs_set_timing(mgx_msbfs_t p, int on);
 MGX_API int mgx_msbfs_phase_ms(mgx_msbfs_t p, double* out);
+
+/* ---- random walks and node2vec sampling (include/mgx/rw_fused.hpp, include/gunrock/rw/) ----
+ * Walks along out-entries, in original ids; an attached layout is ignored.  A CSR entry (u, v) is a step u -> v, duplicates count
+ * as often as they are stored.  starts is a host int32[count], NULL means every vertex in order (count is ignored); walker w of
+ * [0, count x walks_per_start) starts at starts[w / walks_per_start] and takes up to `length` steps.  Its path has length + 1
+ * slots: slot 0 the start, -1 behind the walk's end.  A start outside [0, n), count < 0, length < 0, walks_per_start < 1, p or q
+ * not finite or <= 0, restart outside [0, 1): MGX_E_INVALID before any device work; count x walks_per_start >= 2^31:
+ * MGX_E_FRONTIER_OVERFLOW; the path matrix is addressed in 64 bits.
+ * Every draw is draw(seed, w, t, k) = fmix32(fmix32(fmix32(seed + 0x9E3779B9 (w + 1)) ^ 0x85EBCA6B (t + 1)) ^ 0xC2B2AE35 (k + 1))
+ * (fmix32: murmur3's 32-bit finalizer), t the step, k the draw within it: a walker's path depends on the graph, the seed and w
+ * alone.  u(r) = float(r >> 8) 2^-24; a position in a row of d entries is the high word of r x d (a position's probability is off
+ * 1 / d by at most 2^-32, a row's total bias at most d / 2^32).  Step t from cur (prev: the vertex before it, none at the start
+ * and behind a restart):
+ *   1. restart > 0 and u(draw(k = 0)) < restart: to the walker's start; a step and a restart.
+ *   2. cur's row is dead (no entries; weighted: its maximum weight is <= 0): the walk ends, a dead end -- with restart > 0 it
+ *      jumps to the start as in 1 instead.
+ *   3. tries i = 0 .. MGX_RW_TRIES - 1 (64): position j = hi(draw(k = 1 + 2 i) x d) in the row's STORED order, c its vertex, a =
+ *      u(draw(k = 2 + 2 i)); accepted iff a * (wmax * M) < w_j * b in float32 products.  weighted == 0: w = wmax = 1.  First order
+ *      (p == q == 1 or no prev): b = M = 1.  Second order (node2vec): b = 1 / p when c == prev, 1 when prev has an entry to c,
+ *      1 / q otherwise; M = max(1 / p, 1, 1 / q).  The unweighted first-order step takes try 0.
+ *   4. after MGX_RW_TRIES rejections: the row's first entry of maximum weight, a fallback.  The sampled distribution is the
+ *      intended one exactly where stats[6] == 0; the expected tries per step are wmax M / mean(w b).
+ * Setup, per handle, redone when a run's mode needs what is missing: weighted runs the rows' maxima (a negative or NaN weight is
+ * MGX_E_NEGATIVE_WEIGHT; a graph without uploaded weights has all 1.0f), second-order runs a check that every row ascends, and
+ * a sorted copy of col_indices for the membership search where one does not (stats[7]).
+ * stats (may be NULL), int64[10]: [0] walkers, [1] length, [2] steps taken, [3] dead ends, [4] restarts, [5] tries (candidates
+ * drawn), [6] fallbacks, [7] 1 if the membership search ran on a sorted copy, [8] launches (fused: two for a setup, one for a
+ * sorted copy's sort, one walk; operator path: operator calls on top of the setup's), [9] host waits (fused: one for the starts'
+ * upload when given, one for a setup and two for a sort, one for the counters).  Every run starts afresh, on the context's stream;
+ * a repeat run allocates nothing.  A run that fails leaves no result: the getters return MGX_E_INVALID until a run succeeds. */
+MGX_API int mgx_rw_create(mgx_graph_t g, mgx_rw_t* out);
+MGX_API int mgx_rw_free(mgx_rw_t p);
+/* the fused path: one launch walks every walker, a lane each; the paths leave through an LDS tile of MGX_RW_TILE slots */
+MGX_API int mgx_rw_run(mgx_rw_t p, const int* starts, int count, int walks_per_start, int length, uint32_t seed, int weighted, float p_ret,
+                       float q_inout, float restart, int want_paths, int want_visits, int64_t* stats);
+/* the operator path: a filter over the live walkers per step, a host wait each; the same results, bit for bit */
+MGX_API int mgx_rw_enact(mgx_rw_t p, const int* starts, int count, int walks_per_start, int length, uint32_t seed, int weighted, float p_ret,
+                         float q_inout, float restart, int want_paths, int want_visits, int64_t* stats);
+/* the last run's paths, int32[walkers][length + 1]; MGX_E_INVALID when it kept none.  The device pointer stays valid until the
+ * next run or free */
+MGX_API int mgx_rw_paths(mgx_rw_t p, int* host);
+MGX_API int mgx_rw_paths_device(mgx_rw_t p, const int** d_paths);
+/* the last run's last vertex and steps taken per walker, host int32[walkers] */
+MGX_API int mgx_rw_ends(mgx_rw_t p, int* host);
+MGX_API int mgx_rw_lengths(mgx_rw_t p, int* host);
+/* the last run's visits, int64[n]: the path slots that hold every vertex, slot 0 included; MGX_E_INVALID when it kept none */
+MGX_API int mgx_rw_visits(mgx_rw_t p, int64_t* host);
+MGX_API int mgx_rw_visits_device(mgx_rw_t p, const int64_t** d_visits);
+/* int64[10]: [0] - [3] the rows without entries / a lane's / a wave's / segmented of the handle's last setup launch, [4] the
+ * segments of the latter (zeros before any setup), [5] - [9] MGX_RW_SHORT_MAX, _WAVE_MAX, _SEG, _TRIES and _TILE as read */
+MGX_API int mgx_rw_bins(mgx_rw_t p, int64_t* out);
+/* timing (measurement tools; off by default): mgx_rw_phase_ms gives out[2] = ms of the last fused run's setup and walk */
+MGX_API int mgx_rw_set_timing(mgx_rw_t p, int on);
+MGX_API int mgx_rw_phase_ms(mgx_rw_t p, double* out);
 
 /* ---- segmented sort (mgpu::segmented_sort, lspar_enactor.hxx:85; mgx/segsort.hpp) ----
  * Sorts d_keys[0, count) (and d_vals with them; NULL: keys only) in place, stably, ascending or descending, within segments:

@@ -74,6 +74,12 @@ inline const env_switch_t* env_switches(int* count) {
     {"MGX_MSBFS_WAVE_MAX", "longer rows of at most N entries take a wave each, the rest go out as (vertex, segment) items (default 1024)"},
     {"MGX_MSBFS_SEG", "entries of a segmented row one wave takes (default 1024)"},
     {"MGX_MSBFS_PULL_DIV", "0 / N: every level pushes / a level pulls when its front's out-entries x N >= m (default 8; 2^30: whenever the front has an out-entry)"},
+    // ---- random walks (rw_opts_t::from_env: read once per handle; the three cuts are unmeasured guesses)
+    {"MGX_RW_TRIES", "candidates a weighted or second-order step draws before it falls back to the row's first maximum-weight entry (default 64)"},
+    {"MGX_RW_TILE", "path slots a workgroup stages in LDS before it stores them transposed, a power of two in [1, 64] (default 16; 1: every slot on its own)"},
+    {"MGX_RW_SHORT_MAX", "the setup finds the maximum weight of rows of at most N entries a lane each (default 32)"},
+    {"MGX_RW_WAVE_MAX", "longer rows of at most N entries take a wave each, the rest go out as (vertex, segment) items (default 1024)"},
+    {"MGX_RW_SEG", "entries of a segmented row one wave takes (default 1024)"},
     // ---- betweenness centrality (bc_opts_t::from_env: read once per handle; all four defaults are unmeasured guesses)
     {"MGX_BC_LANE_MAX", "rows of at most N entries are folded by one lane (default 16)"},
     {"MGX_BC_HUGE_MIN", "rows of at least N entries are cut into segments folded by several workgroups, the rest by a wave (default 8192)"},

@@ -320,6 +320,19 @@ SIGNATURES = {
     "mgx_msbfs_bins": [_vp, _pi64],
     "mgx_msbfs_set_timing": [_vp, _i],
     "mgx_msbfs_phase_ms": [_vp, C.POINTER(C.c_double)],
+    "mgx_rw_create": [_vp, _pvp],
+    "mgx_rw_free": [_vp],
+    "mgx_rw_run": [_vp, _vp, _i, _i, _i, C.c_uint32, _i, C.c_float, C.c_float, C.c_float, _i, _i, _pi64],
+    "mgx_rw_enact": [_vp, _vp, _i, _i, _i, C.c_uint32, _i, C.c_float, C.c_float, C.c_float, _i, _i, _pi64],
+    "mgx_rw_paths": [_vp, _vp],
+    "mgx_rw_paths_device": [_vp, _pvp],
+    "mgx_rw_ends": [_vp, _vp],
+    "mgx_rw_lengths": [_vp, _vp],
+    "mgx_rw_visits": [_vp, _vp],
+    "mgx_rw_visits_device": [_vp, _pvp],
+    "mgx_rw_bins": [_vp, _pi64],
+    "mgx_rw_set_timing": [_vp, _i],
+    "mgx_rw_phase_ms": [_vp, C.POINTER(C.c_double)],
     "mgx_modularity": [_vp, _vp, _i, C.POINTER(C.c_uint64)],
     "mgx_rmat_edges": [_vp, _i, _i64, _i64, _u64, _i, _vp, _vp, _vp],
 }

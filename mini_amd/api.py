@@ -1352,6 +1352,118 @@ class MsBfsProblem:
             self._h = None
 
 
+class RandomWalkProblem:
+    """Random walks and node2vec sampling: DeepWalk / node2vec corpora, Monte-Carlo personalised PageRank, walk-based
+    sampling.  run() is the fused path (one launch, a lane per walker), enact() the operator path (a filter per step); the getters
+    describe the last run of either, and both give the same results bit for bit.  Every draw is a pure function of (seed, walker,
+    step, draw): walker w's path does not depend on which other walkers run.  The fine print of the definition:
+      * a pick is a position in the row's STORED order: two uploads of one graph with differently ordered rows walk differently;
+      * a position in a row of d entries is the high word of a 32-bit draw times d: a position's probability is off 1 / d by at
+        most 2^-32, a row's total bias at most d / 2^32;
+      * weighted and second-order (p, q) steps sample by rejection; after MGX_RW_TRIES (64) rejected candidates a step takes the
+        row's first maximum-weight entry and counts a fallback: the sampled distribution is the intended one exactly where
+        stats["fallbacks"] == 0; the expected tries per step are wmax * max(1/p, 1, 1/q) / mean(w * b);
+      * walks follow the OUT-entries: on a directed graph "prev has an entry to c" is asked of prev's out-row, and a vertex without
+        out-entries ends the walk (restart > 0: it jumps to its start instead)."""
+
+    KEYS = ("walkers", "length", "steps", "dead_ends", "restarts", "tries", "fallbacks", "sorted_copy", "launches", "host_waits")
+    PHASES = ("setup", "walk")
+    BINS = ("none", "short", "wave", "long", "segments", "short_max", "wave_max", "seg", "tries", "tile")
+
+    def __init__(self, graph):
+        h = C.c_void_p()
+        check(lib.mgx_rw_create(graph._h, C.byref(h)))
+        self.graph, self._h = graph, h
+        self._walkers = self._length = 0
+
+    def _go(self, fn, starts, length, walks_per_start, seed, weighted, p, q, restart, paths, visits):
+        st = (C.c_int64 * 10)()
+        if starts is None:
+            src, ptr, count = None, None, 0
+        else:
+            src = _np_i32(np.asarray(starts))
+            ptr, count = _ptr(src), len(src)
+            if count == 0:
+                src = np.zeros(1, dtype=np.int32)                # (NULL would mean every vertex)
+                ptr = _ptr(src)
+        check(fn(self._h, ptr, count, int(walks_per_start), int(length), int(seed) & 0xFFFFFFFF, int(bool(weighted)), float(p), float(q),
+                 float(restart), int(bool(paths)), int(bool(visits)), st))
+        out = dict(zip(self.KEYS, (int(x) for x in st)))
+        self._walkers, self._length = out["walkers"], out["length"]
+        return out
+
+    def run(self, starts=None, length=80, walks_per_start=1, seed=1, weighted=False, p=1.0, q=1.0, restart=0.0, paths=True, visits=False):
+        """fused path from `starts` (None: every vertex) -> the stats dict of KEYS"""
+        return self._go(lib.mgx_rw_run, starts, length, walks_per_start, seed, weighted, p, q, restart, paths, visits)
+
+    def enact(self, starts=None, length=80, walks_per_start=1, seed=1, weighted=False, p=1.0, q=1.0, restart=0.0, paths=True, visits=False):
+        """operator path (a filter over the live walkers per step); the same results"""
+        return self._go(lib.mgx_rw_enact, starts, length, walks_per_start, seed, weighted, p, q, restart, paths, visits)
+
+    def paths(self):
+        """int32[walkers, length + 1] of the last run with paths=True: slot 0 the start, -1 behind a walk's end"""
+        w, k = self._walkers, self._length + 1
+        out = np.zeros(max(w * k, 1), dtype=np.int32)
+        check(lib.mgx_rw_paths(self._h, _ptr(out)))
+        return out[:w * k].reshape(w, k)
+
+    def _per_walker(self, fn):
+        out = np.zeros(max(self._walkers, 1), dtype=np.int32)
+        check(fn(self._h, _ptr(out)))
+        return out[:self._walkers]
+
+    def ends(self):
+        """int32[walkers]: the last vertex of every walk"""
+        return self._per_walker(lib.mgx_rw_ends)
+
+    def lengths(self):
+        """int32[walkers]: the steps every walk took"""
+        return self._per_walker(lib.mgx_rw_lengths)
+
+    def visits(self):
+        """int64[n] of the last run with visits=True: the path slots that hold every vertex, the starts included"""
+        n = self.graph.num_nodes
+        out = np.zeros(max(n, 1), dtype=np.int64)
+        check(lib.mgx_rw_visits(self._h, _ptr(out)))
+        return out[:n]
+
+    def ppr(self):
+        """float64[n]: visits / visits.sum(), the Monte-Carlo personalised PageRank estimate of a run with restart > 0"""
+        v = self.visits().astype(np.float64)
+        total = v.sum()
+        return v / total if total > 0 else v
+
+    def paths_device_ptr(self):
+        d = C.c_void_p()
+        check(lib.mgx_rw_paths_device(self._h, C.byref(d)))
+        return d.value
+
+    def visits_device_ptr(self):
+        d = C.c_void_p()
+        check(lib.mgx_rw_visits_device(self._h, C.byref(d)))
+        return d.value
+
+    def bins(self):
+        """rows per body of the handle's last setup launch (zeros before any), their segments, the switches as read"""
+        out = (C.c_int64 * 10)()
+        check(lib.mgx_rw_bins(self._h, out))
+        return dict(zip(self.BINS, (int(x) for x in out)))
+
+    def set_timing(self, on):
+        """measurement tools: a run() keeps the device time of its setup and of its walk"""
+        check(lib.mgx_rw_set_timing(self._h, int(bool(on))))
+
+    def phase_ms(self):
+        out = (C.c_double * 2)()
+        check(lib.mgx_rw_phase_ms(self._h, out))
+        return dict(zip(self.PHASES, (float(x) for x in out)))
+
+    def close(self):
+        if self._h:
+            lib.mgx_rw_free(self._h)
+            self._h = None
+
+
 def modularity(graph, labels, symmetric=False):
     """Modularity of any labelling (labels in [0, n): a numpy array, a torch tensor on the device or a device address) ->
     (Q, S_in, S_sq, W); Q = S_in / W - S_sq / W^2 in double from the three integers the library returns (0.0 when W == 0)."""

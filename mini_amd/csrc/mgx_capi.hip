@@ -1,6 +1,6 @@
 // mgx_capi.hip -- implementation of the C-ABI declared in include/mgx.h.
 // Pre-instantiates the operator templates of include/gunrock/*.hxx for the in-scope functors (BFS, SSSP, PR, k-core, colouring,
-// lspar, CC, TC, BC, PageRank, MST), exposes the building blocks and runs the fused paths of include/mgx/*_fused.hpp.
+// lspar, CC, TC, BC, PageRank, MST, random walks), exposes the building blocks and runs the fused paths of include/mgx/*_fused.hpp.
 // Every algorithm's handle is an mgx_problem_s (its graph) plus what its two paths keep; the entry points share enter() (device
 // and stream current, context and graph), create_handle / free_handle, require_run ("no run yet"), read_back (a result to the
 // host) and put_stats.  Built with
@@ -23,6 +23,7 @@
 #include "gunrock/mst/mst_enactor.hxx"
 #include "gunrock/pagerank/pagerank_enactor.hxx"
 #include "gunrock/pr/pr_enactor.hxx"
+#include "gunrock/rw/rw_enactor.hxx"
 #include "gunrock/kcore/kcore_enactor.hxx"
 #include "gunrock/sssp/sssp_enactor.hxx"
 #include "gunrock/tc/tc_enactor.hxx"
@@ -42,6 +43,7 @@
 #include "mgx/env.hpp"
 #include "mgx/sssp_dist.hpp"
 #include "mgx/rmat.hpp"
+#include "mgx/rw_fused.hpp"
 #include "mgx/sssp_fused.hpp"
 #include "mgx/sssp_preds.hpp"
 #include "mgx/tc_fused.hpp"
@@ -202,6 +204,18 @@ struct mgx_msbfs_s : mgx_problem_s {
   std::unique_ptr<msbfs::msbfs_enactor_t> e;
   int last = 0;                                                   // 0: no run yet; 1: the fused path's results; 2: the operator path's
   long long count = 0;                                            // sources of the last run
+};
+
+struct mgx_rw_s : mgx_problem_s {
+  std::unique_ptr<mgx::rw_setup_state_t> setup;                   // lazily: the rows' maxima and the sorted copy, shared by both paths
+  std::unique_ptr<mgx::rw_fused_state_t> fused;                   // lazily: the fused path's results
+  std::unique_ptr<rw::rw_state_t> op_state;                       // lazily: the operator path's arrays
+  std::shared_ptr<rw::rw_problem_t> p;
+  std::unique_ptr<rw::rw_enactor_t> e;
+  int last = 0;                                                   // 0: no run yet; 1: the fused path's results; 2: the operator path's
+  long long walkers = 0, length = 0;                              // of the last run
+  bool kept_paths = false, kept_visits = false;
+  bool timing = false;
 };
 
 struct mgx_dbfs_s {
@@ -3578,6 +3592,167 @@ int mgx_msbfs_phase_ms(mgx_msbfs_t p, double* out) {
   MGX_REQUIRE(p && out, "NULL argument");
   require_run(p->fused && p->fused->launches >= 0, "mgx_msbfs_phase_ms");
   for (int i = 0; i < 4; ++i) out[i] = p->fused->phase_ms[i];
+  MGX_CATCH
+}
+
+// ---- random walks and node2vec sampling --------------------------------------------
+// a run's arguments, checked before any device work (the parameters first: their messages do not need a handle)
+static mgx::rw_request_t rw_check(mgx_rw_t p, const int* starts, int count, int walks_per_start, int length, uint32_t seed, int weighted,
+                                  float p_ret, float q_inout, float restart, int want_paths, int want_visits, const char* who) {
+  const std::string w(who);
+  MGX_REQUIRE(count >= 0 || !starts, w + ": count must not be negative");
+  MGX_REQUIRE(length >= 0, w + ": length must not be negative");
+  MGX_REQUIRE(walks_per_start >= 1, w + ": walks_per_start must be at least 1");
+  MGX_REQUIRE(std::isfinite(p_ret) && p_ret > 0.f && std::isfinite(q_inout) && q_inout > 0.f, w + ": p and q must be finite and positive");
+  MGX_REQUIRE(restart >= 0.f && restart < 1.f, w + ": restart must lie in [0, 1)");
+  MGX_REQUIRE(p, "NULL argument");
+  const int n = p->graph().num_nodes;
+  mgx::rw_request_t r;
+  r.h_starts = starts;
+  r.starts = starts ? count : n;
+  if (starts) for (int i = 0; i < count; ++i) MGX_REQUIRE(starts[i] >= 0 && starts[i] < n, w + ": start out of range");
+  r.per_start = walks_per_start; r.length = length; r.seed = seed;
+  if (r.walkers() >= (1ll << 31)) throw mgx::mgx_error(MGX_E_FRONTIER_OVERFLOW, w + ": 2^31 walkers or more");
+  r.weighted = weighted != 0;
+  r.second = !(p_ret == 1.f && q_inout == 1.f);
+  r.ip = 1.0f / p_ret; r.iq = 1.0f / q_inout; r.restart = restart;
+  r.want_paths = want_paths != 0; r.want_visits = want_visits != 0;
+  return r;
+}
+static void rw_finish(mgx_rw_t p, int path, const mgx::rw_request_t& r) {
+  p->last = path;
+  p->walkers = r.walkers(); p->length = r.length;
+  p->kept_paths = r.want_paths; p->kept_visits = r.want_visits;
+}
+static const mgx::rw_results_t& rw_results(mgx_rw_t p, const char* who) {
+  MGX_REQUIRE(p, "NULL argument");
+  require_run(p->last != 0, who);
+  return p->last == 1 ? p->fused->res : p->op_state->res;
+}
+int mgx_rw_create(mgx_graph_t g, mgx_rw_t* out) { return create_handle(g, out); }
+int mgx_rw_free(mgx_rw_t p) { return free_handle(p); }
+int mgx_rw_run(mgx_rw_t p, const int* starts, int count, int walks_per_start, int length, uint32_t seed, int weighted, float p_ret,
+               float q_inout, float restart, int want_paths, int want_visits, int64_t* stats) {
+  MGX_TRY
+  if (p) p->last = 0;                                        // (a run that is refused leaves nothing to the getters)
+  const mgx::rw_request_t r = rw_check(p, starts, count, walks_per_start, length, seed, weighted, p_ret, q_inout, restart, want_paths,
+                                       want_visits, "mgx_rw_run");
+  auto [ctx, g] = enter(p);
+  if (!p->setup) p->setup.reset(new mgx::rw_setup_state_t(g.num_nodes, g.num_edges, ctx));
+  if (!p->fused) p->fused.reset(new mgx::rw_fused_state_t(g.num_nodes, ctx));
+  p->fused->timing = p->timing;
+  const std::vector<long long> st = p->fused->run(*p->setup, g.d_row_offsets.data(), g.d_col_indices.data(), g.d_col_values.data(), r, ctx);
+  rw_finish(p, 1, r);
+  put_stats(stats, 10, st);
+  MGX_CATCH
+}
+int mgx_rw_enact(mgx_rw_t p, const int* starts, int count, int walks_per_start, int length, uint32_t seed, int weighted, float p_ret,
+                 float q_inout, float restart, int want_paths, int want_visits, int64_t* stats) {
+  MGX_TRY
+  if (p) p->last = 0;
+  const mgx::rw_request_t r = rw_check(p, starts, count, walks_per_start, length, seed, weighted, p_ret, q_inout, restart, want_paths,
+                                       want_visits, "mgx_rw_enact");
+  auto [ctx, g] = enter(p);
+  const int n = g.num_nodes;
+  const long long W = r.walkers();
+  if (!p->setup) p->setup.reset(new mgx::rw_setup_state_t(n, g.num_edges, ctx));
+  if (!p->op_state) p->op_state.reset(new rw::rw_state_t());
+  std::vector<long long> st = {W, r.length, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (n > 0 && W > 0) {
+    const hipStream_t s = ctx.stream();
+    mgx::rw_setup_state_t& su = *p->setup;
+    rw::rw_state_t& os = *p->op_state;
+    long long launches = 0, waits = 0;
+    su.ensure(g.d_row_offsets.data(), g.d_col_indices.data(), g.d_col_values.data(), r.weighted, r.second, ctx, launches, waits);
+    os.ensure(r, n, ctx);
+    if (starts) { MGX_HIP(mgx::htod(os.res.d_starts.data(), starts, (size_t)r.starts, s)); ++waits; }
+    MGX_HIP(hipMemsetAsync(os.res.counters.data(), 0, mgx::RW_COUNTERS * sizeof(mgx::u64), s));
+    if (r.want_visits) MGX_HIP(hipMemsetAsync(os.res.visits.data(), 0, (size_t)n * sizeof(mgx::u64), s));
+    if (r.want_paths) MGX_HIP(hipMemsetAsync(os.res.paths.data(), 0xff, (size_t)W * ((size_t)r.length + 1) * sizeof(int), s));
+    const rw::rw_problem_t::data_slice_t slice =
+        os.slice(su.graph(g.d_row_offsets.data(), g.d_col_indices.data(), g.d_col_values.data(), r.weighted, r.second), mgx::rw_params_of(r, su.opts), r);
+    if (!p->p) p->p = std::make_shared<rw::rw_problem_t>(p->g->g, slice, ctx);
+    else MGX_HIP(mgx::htod(p->p->d_data_slice.data(), &slice, 1, s));
+    ++waits;
+    if (!p->e) p->e.reset(new rw::rw_enactor_t());
+    p->e->enact(p->p, slice, r, ctx);
+    mgx::u64 c[mgx::RW_COUNTERS];
+    MGX_HIP(mgx::dtoh(c, (const mgx::u64*)os.res.counters.data(), mgx::RW_COUNTERS, s));
+    ++waits;
+    st = {W, r.length, (long long)c[mgx::RW_C_STEPS], (long long)c[mgx::RW_C_DEAD], (long long)c[mgx::RW_C_RESTARTS], (long long)c[mgx::RW_C_TRIES],
+          (long long)c[mgx::RW_C_FALLBACKS], su.unsorted && r.second ? 1 : 0, launches + p->e->calls, waits + p->e->waits};
+  }
+  rw_finish(p, 2, r);
+  put_stats(stats, 10, st);
+  MGX_CATCH
+}
+int mgx_rw_paths(mgx_rw_t p, int* host) {
+  MGX_TRY
+  const mgx::rw_results_t& res = rw_results(p, "mgx_rw_paths");
+  MGX_REQUIRE(host, "NULL argument");
+  MGX_REQUIRE(p->kept_paths, "mgx_rw_paths: the last run kept no paths (want_paths = 0)");
+  if (p->walkers && p->n()) read_back(p, host, (const int*)res.paths.data(), (size_t)p->walkers * ((size_t)p->length + 1));
+  MGX_CATCH
+}
+int mgx_rw_paths_device(mgx_rw_t p, const int** d_paths) {
+  MGX_TRY
+  const mgx::rw_results_t& res = rw_results(p, "mgx_rw_paths_device");
+  MGX_REQUIRE(d_paths, "NULL argument");
+  MGX_REQUIRE(p->kept_paths, "mgx_rw_paths_device: the last run kept no paths (want_paths = 0)");
+  *d_paths = p->walkers && p->n() ? res.paths.data() : nullptr;
+  MGX_CATCH
+}
+int mgx_rw_ends(mgx_rw_t p, int* host) {
+  MGX_TRY
+  const mgx::rw_results_t& res = rw_results(p, "mgx_rw_ends");
+  MGX_REQUIRE(host, "NULL argument");
+  if (p->walkers && p->n()) read_back(p, host, (const int*)res.ends.data(), (size_t)p->walkers);
+  MGX_CATCH
+}
+int mgx_rw_lengths(mgx_rw_t p, int* host) {
+  MGX_TRY
+  const mgx::rw_results_t& res = rw_results(p, "mgx_rw_lengths");
+  MGX_REQUIRE(host, "NULL argument");
+  if (p->walkers && p->n()) read_back(p, host, (const int*)res.lengths.data(), (size_t)p->walkers);
+  MGX_CATCH
+}
+int mgx_rw_visits(mgx_rw_t p, int64_t* host) {
+  MGX_TRY
+  const mgx::rw_results_t& res = rw_results(p, "mgx_rw_visits");
+  MGX_REQUIRE(host, "NULL argument");
+  MGX_REQUIRE(p->kept_visits, "mgx_rw_visits: the last run kept no visits (want_visits = 0)");
+  if (p->walkers == 0) std::fill(host, host + p->n(), 0);     // (a run without walkers touches no device array)
+  else read_back(p, host, (const int64_t*)res.visits.data(), p->n());
+  MGX_CATCH
+}
+int mgx_rw_visits_device(mgx_rw_t p, const int64_t** d_visits) {
+  MGX_TRY
+  const mgx::rw_results_t& res = rw_results(p, "mgx_rw_visits_device");
+  MGX_REQUIRE(d_visits, "NULL argument");
+  MGX_REQUIRE(p->kept_visits, "mgx_rw_visits_device: the last run kept no visits (want_visits = 0)");
+  *d_visits = p->walkers && p->n() ? (const int64_t*)res.visits.data() : nullptr;
+  MGX_CATCH
+}
+int mgx_rw_bins(mgx_rw_t p, int64_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->last != 0 && p->setup, "mgx_rw_bins");
+  const mgx::rw_setup_state_t& su = *p->setup;
+  for (int i = 0; i < mgx::RW_BINS; ++i) out[i] = su.bins[i];
+  out[5] = su.opts.short_max; out[6] = su.opts.wave_max; out[7] = su.opts.seg; out[8] = su.opts.tries; out[9] = su.opts.tile;
+  MGX_CATCH
+}
+int mgx_rw_set_timing(mgx_rw_t p, int on) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  p->timing = on != 0;
+  MGX_CATCH
+}
+int mgx_rw_phase_ms(mgx_rw_t p, double* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->last == 1, "mgx_rw_phase_ms");
+  out[0] = p->fused->phase_ms[0]; out[1] = p->fused->phase_ms[1];
   MGX_CATCH
 }
 
