@@ -54,6 +54,7 @@ typedef struct mgx_scc_s* mgx_scc_t;
 typedef struct mgx_lpa_s* mgx_lpa_t;
 typedef struct mgx_msbfs_s* mgx_msbfs_t;
 typedef struct mgx_rw_s* mgx_rw_t;
+typedef struct mgx_louvain_s* mgx_louvain_t;
 typedef struct mgx_dbfs_s* mgx_dbfs_t;
 typedef struct mgx_dbfs2_s* mgx_dbfs2_t;
 typedef struct mgx_dsssp_s* mgx_dsssp_t;
@@ -1009,6 +1010,56 @@ MGX_API int mgx_rw_bins(mgx_rw_t p, int64_t* out);
 /* timing (measurement tools; off by default): mgx_rw_phase_ms gives out[2] = ms of the last fused run's setup and walk */
 MGX_API int mgx_rw_set_timing(mgx_rw_t p, int on);
 MGX_API int mgx_rw_phase_ms(mgx_rw_t p, double* out);
+
+/* ---- Louvain community detection (include/mgx/louvain_fused.hpp, include/mgx/louvain_aggregate.hpp) ----
+ * Levels of local moves that raise the modularity, each followed by a contraction of the communities into the next level's
+ * weighted graph.  Level 0 takes the votes of mgx_lpa_* and mgx_modularity: symmetric != 0 (the caller's word that every entry has
+ * its reverse): every CSR entry (v, u), u != v, is weight 1 from v to u; symmetric == 0: every entry gives weight 1 to both ends,
+ * which needs the graph's genuine CSC (mgx_graph_build_csc, or one uploaded) and is MGX_E_INVALID without one.  Self-loops are
+ * dropped, duplicate entries add, float edge values are not used, an attached layout is ignored.
+ * An iteration scores for every vertex its own label and its neighbours' (s(c) = k_vc W - (Sigma_c - [c is its own] k_v) k_v),
+ * takes the best (ties: the current label, then the smaller color_key(c, seed)) and moves there when the key falls (even
+ * iterations) or rises (odd ones); the moved labelling is accepted iff a vertex moved and Qnum = S_in W - S_sq grew by more than
+ * (int64) ceil(tol * W * W).  A level ends after two consecutive rejected iterations or at max_iter; a level that accepted nothing
+ * ends the run, as does max_levels.  All of it is integer arithmetic: the run and tests/louvain_model.py agree bit for bit.
+ * max_iter in [0, 2^20], max_levels in [0, 64], tol in [0, 1] and not NaN, else MGX_E_INVALID before any device work; more than
+ * 2^30 entries, or 2^30 - 1 and more with symmetric == 0 (the contraction addresses the votes by int32): MGX_E_FRONTIER_OVERFLOW,
+ * before any device work as well.
+ * stats, int64[10] (may be NULL): [0] communities, [1] the largest one's vertices, [2] its id, [3] levels aggregated, [4] S_in,
+ * [5] S_sq, [6] W of the final labels (Q = S_in / W - S_sq / W^2 is the caller's division; 0 when W == 0), [7] host waits,
+ * [8] launches of the levels' chains, [9] iterations over all levels.
+ * The state is allocated at the first run, bounded by the graph's vertices and entries: a repeat run allocates nothing (a later
+ * run does only when it asks for more iterations than any before, or is the handle's first with symmetric == 0).  A run that fails leaves no result: the getters return MGX_E_INVALID until
+ * a run succeeds.  mgx_louvain_enact is the operator path (include/gunrock/louvain/): the same results and stats, [8] being its
+ * operator calls; every vertex every iteration, a host wait per operator.  _step_kinds, _bins and _phase_ms describe fused runs
+ * only (MGX_E_INVALID behind an operator run). */
+/* how many device arrays the library has allocated in this process so far: equal before and after a call that allocates nothing */
+MGX_API long long mgx_device_allocations(void);
+MGX_API int mgx_louvain_create(mgx_graph_t g, mgx_louvain_t* out);
+MGX_API int mgx_louvain_free(mgx_louvain_t p);
+MGX_API int mgx_louvain_run(mgx_louvain_t p, int symmetric, uint32_t seed, int max_iter, int max_levels, double tol, int64_t* stats);
+MGX_API int mgx_louvain_enact(mgx_louvain_t p, int symmetric, uint32_t seed, int max_iter, int max_levels, double tol, int64_t* stats);
+/* labels of the last run.  level == -1: the composition of the levels' maps, n labels in [0, communities).  0 <= level < levels:
+ * that level's map, as many labels as the level has vertices (mgx_louvain_levels), in [0, its communities).  The device pointer
+ * stays valid until the next run or free. */
+MGX_API int mgx_louvain_labels(mgx_louvain_t p, int level, int* host_labels);
+MGX_API int mgx_louvain_labels_device(mgx_louvain_t p, int level, const int** d_labels);
+/* the levels that ran, the last one that accepted nothing included: (vertices, entries, iterations, accepted iterations,
+ * communities, Qnum) each; *levels_run: how many there are, at most cap sextuples are written */
+MGX_API int mgx_louvain_levels(mgx_louvain_t p, int64_t* host_sextuples, int cap, int64_t* levels_run);
+/* (moved, accepted, Qnum of the moved labelling) per iteration, the levels one behind the other */
+MGX_API int mgx_louvain_trace(mgx_louvain_t p, int64_t* host_triples, int cap, int64_t* iterations);
+/* the launches of the levels' chains, each level up to its first DONE: 1 setup, 2 evaluate, 3 long rows into their tables, 4 long
+ * rows' tables scored, 5 apply, 6 Qnum, 7 done.  *launches: how many there are; min(*launches, cap) kinds are written.  Of a
+ * level of more than 65 536 launches only the first 65 536 are kept: its list then ends without its 7. */
+MGX_API int mgx_louvain_step_kinds(mgx_louvain_t p, int* host_kinds, int cap, int64_t* launches);
+/* int64[8]: [0] - [3] vertices without entries / a lane's / a wave's / long, summed over the levels; [4] - [6]
+ * MGX_LOUVAIN_SHORT_MAX, _WAVE_MAX and _SEG as read; [7] the long rows' (vertex, segment) items over all iterations */
+MGX_API int mgx_louvain_bins(mgx_louvain_t p, int64_t* out);
+/* timing (measurement tools; off by default): mgx_louvain_phase_ms gives out[6] = ms of the last run's setup, evaluations, long
+ * rows, applies, Qnum launches (device clock) and aggregation (host clock, waits included) */
+MGX_API int mgx_louvain_set_timing(mgx_louvain_t p, int on);
+MGX_API int mgx_louvain_phase_ms(mgx_louvain_t p, double* out);
 
 /* ---- segmented sort (mgpu::segmented_sort, lspar_enactor.hxx:85; mgx/segsort.hpp) ----
  * Sorts d_keys[0, count) (and d_vals with them; NULL: keys only) in place, stably, ascending or descending, within segments:

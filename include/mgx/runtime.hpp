@@ -128,6 +128,11 @@ inline void frontier_touched() { frontier_generation().fetch_add(1, std::memory_
 // ---------------------------------------------------------------------------
 // mem_t<T>: RAII device array (may also borrow an external device pointer)
 // ---------------------------------------------------------------------------
+// how many device arrays mem_t has allocated in this process (mgx_device_allocations: the tests' check that a repeat run allocates nothing)
+inline std::atomic<long long>& device_allocations() {
+  static std::atomic<long long> n{0};
+  return n;
+}
 template <typename T>
 class mem_t {
   T* _ptr = nullptr;
@@ -137,7 +142,10 @@ class mem_t {
  public:
   mem_t() {}
   mem_t(size_t count, context_t&) : _size(count) {
-    if (count) MGX_HIP(hipMalloc((void**)&_ptr, count * sizeof(T)));
+    if (count) {
+      MGX_HIP(hipMalloc((void**)&_ptr, count * sizeof(T)));
+      device_allocations().fetch_add(1, std::memory_order_relaxed);
+    }
   }
   // borrow: the caller keeps ownership (used by mgx_graph_wrap_device)
   static mem_t borrow(T* p, size_t count) {

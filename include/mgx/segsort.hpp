@@ -282,10 +282,34 @@ __global__ __launch_bounds__(BLOCK) void k_segsort_copy_back(segsort_args_t<K, V
   }
 }
 
+// Buffers a caller may own so that a sort allocates nothing: sized once for the largest count and number of segments it will sort
+template <typename K, typename V>
+struct segsort_workspace_t {
+  long long count_cap = 0;
+  int segs_cap = 0;
+  mem_t<int> short_list, mid_list, cnt;
+  mem_t<int2> tile_list;
+  mem_t<K> ktmp;
+  mem_t<V> vtmp;
+  segsort_workspace_t() {}
+  segsort_workspace_t(long long count, int num_segments, context_t& ctx) : count_cap(count), segs_cap(num_segments + 1) {
+    constexpr bool HAS_V = !std::is_same<V, segsort_no_value_t>::value;
+    short_list = mem_t<int>((size_t)segs_cap, ctx);
+    mid_list = mem_t<int>((size_t)segs_cap, ctx);
+    cnt = mem_t<int>(4, ctx);
+    tile_list = mem_t<int2>((size_t)(2 * (count / SEGSORT_TILE) + 2), ctx);
+    ktmp = mem_t<K>((size_t)std::max<long long>(count, 1), ctx);
+    vtmp = mem_t<V>(HAS_V ? (size_t)std::max<long long>(count, 1) : 0, ctx);
+  }
+};
+
 // Host side.  Sorts keys[0, count) (and vals with them, unless V is segsort_no_value_t) in place on the context's stream.
-// One host wait (the list sizes); the scratch is allocated per call.  Returns the number of merge passes it ran.
+// One host wait for the list sizes; without a workspace the lists and the scratch copy are allocated per call and a second wait
+// precedes their release.  With one (large enough, else MGX_E_INVALID) nothing is allocated and the sort returns behind the one
+// wait, its last launches still on the stream.  Returns the number of merge passes it ran.
 template <typename K, typename V, typename C>
-int segmented_sort_impl(K* keys, V* vals, long long count, const int* heads, int num_segments, C comp, standard_context_t& ctx) {
+int segmented_sort_impl(K* keys, V* vals, long long count, const int* heads, int num_segments, C comp, standard_context_t& ctx,
+                        segsort_workspace_t<K, V>* ws = nullptr) {
   static_assert(sizeof(K) <= 8 && std::is_trivially_copyable<K>::value, "segmented_sort: keys are trivially copyable, at most 8 bytes");
   constexpr bool HAS_V = !std::is_same<V, segsort_no_value_t>::value;
   if (count < 0 || count > INT_MAX || num_segments < 0) throw mgx_error(MGX_E_INVALID, "segmented_sort: count must fit int32");
@@ -293,17 +317,24 @@ int segmented_sort_impl(K* keys, V* vals, long long count, const int* heads, int
   const hipStream_t st = ctx.stream();
   const int segs = num_segments + 1;
   const long long tile_cap = 2 * (count / SEGSORT_TILE) + 2;
-  mem_t<int> short_list((size_t)segs, ctx), mid_list((size_t)segs, ctx), cnt(4, ctx);
-  mem_t<int2> tile_list((size_t)tile_cap, ctx);
-  MGX_HIP(hipMemsetAsync(cnt.data(), 0, 4 * sizeof(int), st));
+  if (ws && (count > ws->count_cap || segs > ws->segs_cap)) throw mgx_error(MGX_E_INVALID, "segmented_sort: the workspace is too small");
+  segsort_workspace_t<K, V> own;
+  if (!ws) {
+    own.short_list = mem_t<int>((size_t)segs, ctx);
+    own.mid_list = mem_t<int>((size_t)segs, ctx);
+    own.cnt = mem_t<int>(4, ctx);
+    own.tile_list = mem_t<int2>((size_t)tile_cap, ctx);
+  }
+  segsort_workspace_t<K, V>& w = ws ? *ws : own;
+  MGX_HIP(hipMemsetAsync(w.cnt.data(), 0, 4 * sizeof(int), st));
   segsort_args_t<K, V> a;
   a.keys = keys; a.vals = vals; a.keys_tmp = nullptr; a.vals_tmp = nullptr;
   a.count = (int)count; a.heads = heads; a.num_segments = num_segments;
-  a.short_list = short_list.data(); a.mid_list = mid_list.data(); a.tile_list = tile_list.data(); a.cnt = cnt.data();
+  a.short_list = w.short_list.data(); a.mid_list = w.mid_list.data(); a.tile_list = w.tile_list.data(); a.cnt = w.cnt.data();
   const int max_blocks = std::max(ctx.num_cus, 1) * 8;
   hipLaunchKernelGGL((k_segsort_classify<K, V>), dim3(grid_for(segs, BLOCK, max_blocks)), dim3(BLOCK), 0, st, a);
   int h[4];
-  MGX_HIP(hipMemcpyAsync(h, cnt.data(), sizeof(h), hipMemcpyDeviceToHost, st));
+  MGX_HIP(hipMemcpyAsync(h, w.cnt.data(), sizeof(h), hipMemcpyDeviceToHost, st));
   MGX_HIP(hipStreamSynchronize(st));
   if (h[0] > 0)
     hipLaunchKernelGGL((k_segsort_wave<K, V, C>), dim3(grid_for(h[0], WAVES_PER_BLOCK, max_blocks)), dim3(BLOCK), 0, st, a, comp);
@@ -312,25 +343,24 @@ int segmented_sort_impl(K* keys, V* vals, long long count, const int* heads, int
   int passes = 0;
   if (h[2] > 0) {
     hipLaunchKernelGGL((k_segsort_block<K, V, C, true>), dim3(std::min(h[2], max_blocks)), dim3(BLOCK), 0, st, a, comp);
-    mem_t<K> ktmp((size_t)count, ctx);
-    mem_t<V> vtmp(HAS_V ? (size_t)count : 0, ctx);
-    a.keys_tmp = ktmp.data();
-    a.vals_tmp = HAS_V ? vtmp.data() : nullptr;
+    if (!ws) {
+      own.ktmp = mem_t<K>((size_t)count, ctx);
+      own.vtmp = mem_t<V>(HAS_V ? (size_t)count : 0, ctx);
+    }
+    a.keys_tmp = w.ktmp.data();
+    a.vals_tmp = HAS_V ? w.vtmp.data() : nullptr;
     K* src_k = keys; V* src_v = vals; K* dst_k = a.keys_tmp; V* dst_v = a.vals_tmp;
-    for (long long w = SEGSORT_TILE; w < h[3]; w *= 2) {
+    for (long long wd = SEGSORT_TILE; wd < h[3]; wd *= 2) {
       hipLaunchKernelGGL((k_segsort_merge<K, V, C>), dim3(std::min(h[2], max_blocks)), dim3(BLOCK), 0, st, a, src_k, src_v, dst_k,
-                         dst_v, (int)w, comp);
+                         dst_v, (int)wd, comp);
       std::swap(src_k, dst_k);
       std::swap(src_v, dst_v);
       ++passes;
     }
     if (passes & 1) hipLaunchKernelGGL((k_segsort_copy_back<K, V>), dim3(std::min(h[2], max_blocks)), dim3(BLOCK), 0, st, a);
-    MGX_CHECK_LAUNCH("segmented_sort");
-    MGX_HIP(hipStreamSynchronize(st));                     // (the scratch copy and the lists are freed on return)
-    return passes;
   }
   MGX_CHECK_LAUNCH("segmented_sort");
-  MGX_HIP(hipStreamSynchronize(st));
+  if (!ws) MGX_HIP(hipStreamSynchronize(st));              // (the scratch copy and the lists are freed on return)
   return passes;
 }
 

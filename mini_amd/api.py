@@ -1229,6 +1229,112 @@ class LpaProblem:
             self._h = None
 
 
+class LouvainProblem:
+    """Louvain community detection: levels of local moves that raise the modularity, each contracted into the next
+    level's weighted graph.  Integer arithmetic throughout: the run agrees with tests/louvain_model.py bit for bit.
+    symmetric=True is the caller's word that every entry has its reverse; symmetric=False counts every entry at both of its ends
+    and needs the graph's genuine CSC."""
+
+    SEED = 0x9E3779B9
+    KEYS = ("communities", "largest", "largest_id", "levels", "s_in", "s_sq", "w", "host_waits", "launches", "iterations")
+    LEVEL_KEYS = ("vertices", "entries", "iterations", "accepted", "communities", "qnum")
+    STEP_KINDS = {1: "setup", 2: "evaluate", 3: "long_fill", 4: "long_scan", 5: "apply", 6: "qnum", 7: "done"}
+    PHASES = ("setup", "evaluate", "long_rows", "apply", "qnum", "aggregate")
+    BINS = ("rows_none", "rows_short", "rows_wave", "rows_long", "short_max", "wave_max", "seg", "long_items")
+
+    def __init__(self, graph):
+        h = C.c_void_p()
+        check(lib.mgx_louvain_create(graph._h, C.byref(h)))
+        self.graph, self._h = graph, h
+        self._stats = None
+
+    def _go(self, fn, symmetric, seed, max_iter, max_levels, tol):
+        st = (C.c_int64 * 10)()
+        self._stats = None
+        check(fn(self._h, int(bool(symmetric)), int(seed) & 0xFFFFFFFF, int(max_iter), int(max_levels), float(tol), st))
+        self._stats = dict(zip(self.KEYS, (int(x) for x in st)))
+        return dict(self._stats)
+
+    def run(self, symmetric=True, seed=SEED, max_iter=100, max_levels=32, tol=0.0):
+        """fused path -> the stats dict of KEYS"""
+        return self._go(lib.mgx_louvain_run, symmetric, seed, max_iter, max_levels, tol)
+
+    def enact(self, symmetric=True, seed=SEED, max_iter=100, max_levels=32, tol=0.0):
+        """operator path (gathering advances, the segmented sort, a scanning and an applying filter per iteration); the same
+        stats, `launches` being its operator calls"""
+        return self._go(lib.mgx_louvain_enact, symmetric, seed, max_iter, max_levels, tol)
+
+    def levels(self):
+        """the levels that ran, the last one that accepted nothing included: a dict of LEVEL_KEYS each"""
+        n = C.c_int64()
+        check(lib.mgx_louvain_levels(self._h, None, 0, C.byref(n)))
+        out = np.empty((n.value, 6), dtype=np.int64)
+        check(lib.mgx_louvain_levels(self._h, _ptr(out), n.value, C.byref(n)))
+        return [dict(zip(self.LEVEL_KEYS, (int(x) for x in row))) for row in out]
+
+    def labels(self, level=None):
+        """level=None: the final communities of the n vertices; else the map of that aggregated level's vertices"""
+        if level is None:
+            count, level = self.graph.num_nodes, -1
+        else:
+            count = self.levels()[level]["vertices"]
+        out = np.empty(count, dtype=np.int32)
+        check(lib.mgx_louvain_labels(self._h, int(level), _ptr(out)))
+        return out
+
+    def labels_device_ptr(self, level=None):
+        p = C.c_void_p()
+        check(lib.mgx_louvain_labels_device(self._h, -1 if level is None else int(level), C.byref(p)))
+        return p.value
+
+    def dendrogram(self):
+        """the aggregated levels' maps, bottom up: composing them gives labels()"""
+        return [self.labels(level) for level in range(self._stats["levels"])] if self._stats else []
+
+    def modularity(self):
+        """Q of the last run's final labels; the division is done here"""
+        s = self._stats
+        if not s or s["w"] == 0:
+            return 0.0
+        return s["s_in"] / s["w"] - s["s_sq"] / (s["w"] * s["w"])
+
+    def trace(self):
+        """int64[iterations, 3] of the last run, the levels one behind the other: moved, accepted, Qnum of the moved labelling"""
+        n = C.c_int64()
+        check(lib.mgx_louvain_trace(self._h, None, 0, C.byref(n)))
+        out = np.empty((n.value, 3), dtype=np.int64)
+        check(lib.mgx_louvain_trace(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def step_kinds(self):
+        """what every launch of the last run's chains was, each level up to its first `done`: codes of STEP_KINDS"""
+        n = C.c_int64()
+        check(lib.mgx_louvain_step_kinds(self._h, None, 0, C.byref(n)))
+        out = np.empty(n.value, dtype=np.int32)
+        check(lib.mgx_louvain_step_kinds(self._h, _ptr(out), len(out), C.byref(n)))
+        return out
+
+    def bins(self):
+        """the last run: vertices per body over the levels, the switches as read, the long rows' items over all iterations"""
+        out = (C.c_int64 * 8)()
+        check(lib.mgx_louvain_bins(self._h, out))
+        return dict(zip(self.BINS, (int(x) for x in out)))
+
+    def set_timing(self, on):
+        """measurement tools: every launch of a run() keeps the device's wall clock per phase"""
+        check(lib.mgx_louvain_set_timing(self._h, int(bool(on))))
+
+    def phase_ms(self):
+        out = (C.c_double * 6)()
+        check(lib.mgx_louvain_phase_ms(self._h, out))
+        return dict(zip(self.PHASES, (float(x) for x in out)))
+
+    def close(self):
+        if self._h:
+            lib.mgx_louvain_free(self._h)
+            self._h = None
+
+
 class MsBfsProblem:
     """Bit-parallel multi-source BFS: BFS depths from many sources at once, 64 traversals to a 64-bit word per vertex,
     and what follows from them -- reach, farness, eccentricity, harmonic and closeness centrality per source, and per vertex how

@@ -18,6 +18,7 @@
 #include "gunrock/lspar/lspar_enactor.hxx"
 #include "gunrock/ktruss/ktruss_enactor.hxx"
 #include "gunrock/scc/scc_enactor.hxx"
+#include "gunrock/louvain/louvain_enactor.hxx"
 #include "gunrock/lpa/lpa_enactor.hxx"
 #include "gunrock/msbfs/msbfs_enactor.hxx"
 #include "gunrock/mst/mst_enactor.hxx"
@@ -36,6 +37,7 @@
 #include "mgx/lspar_fused.hpp"
 #include "mgx/ktruss_fused.hpp"
 #include "mgx/scc_fused.hpp"
+#include "mgx/louvain_fused.hpp"
 #include "mgx/lpa_fused.hpp"
 #include "mgx/msbfs_fused.hpp"
 #include "mgx/mst_fused.hpp"
@@ -216,6 +218,16 @@ struct mgx_rw_s : mgx_problem_s {
   long long walkers = 0, length = 0;                              // of the last run
   bool kept_paths = false, kept_visits = false;
   bool timing = false;
+};
+
+struct mgx_louvain_s : mgx_problem_s {
+  std::unique_ptr<mgx::louvain_fused_state_t> fused;              // lazily: the fused path's labels, tables, level graphs and state words
+  std::unique_ptr<louvain::louvain_state_t> op_state;             // lazily: the operator path's arrays, its contraction, its stats
+  std::unique_ptr<mgx::louvain_aggregate_t> op_agg;
+  std::unique_ptr<louvain::louvain_enactor_t> e;
+  std::unique_ptr<mgx::lpa_label_stats_t> label_stats;
+  long long op_entries = 0;                                       // what op_state is sized for
+  int last = 0;                                                   // 0: no result; 1: the fused path's; 2: the operator path's
 };
 
 struct mgx_dbfs_s {
@@ -3753,6 +3765,149 @@ int mgx_rw_phase_ms(mgx_rw_t p, double* out) {
   MGX_REQUIRE(p && out, "NULL argument");
   require_run(p->last == 1, "mgx_rw_phase_ms");
   out[0] = p->fused->phase_ms[0]; out[1] = p->fused->phase_ms[1];
+  MGX_CATCH
+}
+
+
+// ---- Louvain community detection ---------------------------------------------------
+static void louvain_check_args(const graph_device_t& g, int symmetric, int max_iter, int max_levels, double tol, const char* who) {
+  MGX_REQUIRE(max_iter >= 0 && max_iter <= mgx::LV_MAX_ITER_MAX, std::string(who) + ": max_iter must be in [0, 2^20]");
+  MGX_REQUIRE(max_levels >= 0 && max_levels <= mgx::LV_MAX_LEVELS_MAX, std::string(who) + ": max_levels must be in [0, 64]");
+  MGX_REQUIRE(tol >= 0.0 && tol <= 1.0, std::string(who) + ": tol must be in [0, 1]");      // (false for a NaN)
+  MGX_REQUIRE(symmetric || !g.csc_is_csr, std::string(who) + ": symmetric = 0 needs the graph's genuine CSC (mgx_graph_build_csc)");
+  if ((long long)g.num_edges > (1ll << 30)) throw mgx::mgx_error(MGX_E_FRONTIER_OVERFLOW, std::string(who) + ": more than 2^30 entries");
+  // (the contraction addresses the votes, W <= the entries or twice as many, by int32)
+  if (!symmetric && (long long)g.num_edges >= (1ll << 30) - 1)
+    throw mgx::mgx_error(MGX_E_FRONTIER_OVERFLOW, std::string(who) + ": symmetric = 0 takes fewer than 2^30 - 1 entries");
+}
+long long mgx_device_allocations(void) { return mgx::device_allocations().load(); }
+int mgx_louvain_create(mgx_graph_t g, mgx_louvain_t* out) { return create_handle(g, out); }
+int mgx_louvain_free(mgx_louvain_t p) { return free_handle(p); }
+int mgx_louvain_run(mgx_louvain_t p, int symmetric, uint32_t seed, int max_iter, int max_levels, double tol, int64_t* stats) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  p->last = 0;                                               // (a run that is refused leaves nothing to the getters either)
+  louvain_check_args(p->graph(), symmetric, max_iter, max_levels, tol, "mgx_louvain_run");
+  auto [ctx, g] = enter(p);
+  if (!p->fused) p->fused.reset(new mgx::louvain_fused_state_t(g.num_nodes, g.num_edges, ctx));
+  const std::vector<long long> st = p->fused->run(g.d_row_offsets.data(), g.d_col_indices.data(), g.d_col_offsets.data(),
+                                                  g.d_row_indices.data(), symmetric, seed, max_iter, max_levels, tol, ctx);
+  p->last = 1;
+  put_stats(stats, 10, st);
+  MGX_CATCH
+}
+int mgx_louvain_enact(mgx_louvain_t p, int symmetric, uint32_t seed, int max_iter, int max_levels, double tol, int64_t* stats) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  p->last = 0;
+  louvain_check_args(p->graph(), symmetric, max_iter, max_levels, tol, "mgx_louvain_enact");
+  auto [ctx, g] = enter(p);
+  const int n = g.num_nodes;
+  if (!p->e) p->e.reset(new louvain::louvain_enactor_t(ctx, n, g.num_edges));
+  if (n <= 0) {
+    p->e->levels.clear(); p->e->trace.clear(); p->e->map_off.assign(1, 0);
+    p->last = 2;
+    put_stats(stats, 10, {0, 0, 0, 0, 0, 0, 0, 0, 0, 0});
+    return MGX_OK;
+  }
+  const long long entries = symmetric ? (long long)g.num_edges : 2ll * g.num_edges;
+  if (!p->op_state || p->op_entries < entries) {
+    ctx.synchronize();
+    p->op_state.reset(new louvain::louvain_state_t(n, entries, ctx));
+    p->op_agg.reset(new mgx::louvain_aggregate_t(n, entries, ctx));
+    p->op_entries = entries;
+  }
+  if (!p->label_stats) p->label_stats.reset(new mgx::lpa_label_stats_t(n, ctx));
+  louvain::louvain_enactor_t& e = *p->e;
+  e.enact(p->g->g, *p->op_state, *p->op_agg, symmetric != 0, seed, max_iter, max_levels, tol, ctx);
+  const std::vector<long long> st = p->label_stats->run(p->op_state->d_final.data(), n, ctx);
+  p->last = 2;
+  put_stats(stats, 10, {st[0], st[1], st[2], (long long)e.map_off.size() - 1, e.s_in, e.s_sq, e.w, e.waits + 1, e.calls, e.iterations});
+  MGX_CATCH
+}
+// the labels of `level` of the last run: where they are and how many
+static const int* louvain_level(mgx_louvain_t p, int level, size_t* count, const char* who) {
+  require_run(p->last != 0, who);
+  const std::vector<long long>& off = p->last == 1 ? p->fused->map_off : p->e->map_off;
+  const int levels = (int)off.size() - 1;
+  MGX_REQUIRE(level >= -1 && level < levels, std::string(who) + ": level must be -1 or below the levels aggregated");
+  if (level < 0) { *count = p->n(); return p->last == 1 ? p->fused->final_lab.data() : p->op_state->d_final.data(); }
+  *count = (size_t)(off[level + 1] - off[level]);
+  return (p->last == 1 ? p->fused->maps.data() : p->op_state->d_maps.data()) + off[level];
+}
+int mgx_louvain_labels(mgx_louvain_t p, int level, int* host) {
+  MGX_TRY
+  MGX_REQUIRE(p && host, "NULL argument");
+  size_t count = 0;
+  const int* const src = louvain_level(p, level, &count, "mgx_louvain_labels");
+  read_back(p, host, src, count);
+  MGX_CATCH
+}
+int mgx_louvain_labels_device(mgx_louvain_t p, int level, const int** out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  size_t count = 0;
+  *out = louvain_level(p, level, &count, "mgx_louvain_labels_device");
+  MGX_CATCH
+}
+int mgx_louvain_levels(mgx_louvain_t p, int64_t* host_sextuples, int cap, int64_t* levels_run) {
+  MGX_TRY
+  MGX_REQUIRE(p && levels_run && cap >= 0 && (host_sextuples || cap == 0), "bad argument");
+  require_run(p->last != 0, "mgx_louvain_levels");
+  if (p->last == 2) {
+    const std::vector<long long>& l = p->e->levels;
+    *levels_run = (int64_t)l.size() / 6;
+    std::copy(l.begin(), l.begin() + 6 * std::min<size_t>(l.size() / 6, (size_t)cap), host_sextuples);
+    return MGX_OK;
+  }
+  const std::vector<mgx::lv_level_t>& l = p->fused->levels;
+  *levels_run = (int64_t)l.size();
+  for (size_t i = 0; i < std::min<size_t>(l.size(), (size_t)cap); ++i) {
+    int64_t* const o = host_sextuples + 6 * i;
+    o[0] = l[i].vertices; o[1] = l[i].entries; o[2] = l[i].iterations; o[3] = l[i].accepted; o[4] = l[i].communities; o[5] = l[i].q;
+  }
+  MGX_CATCH
+}
+int mgx_louvain_trace(mgx_louvain_t p, int64_t* host_triples, int cap, int64_t* iterations) {
+  MGX_TRY
+  MGX_REQUIRE(p && iterations && cap >= 0 && (host_triples || cap == 0), "bad argument");
+  require_run(p->last != 0, "mgx_louvain_trace");
+  const std::vector<long long>& t = p->last == 1 ? p->fused->h_trace : p->e->trace;
+  const long long have = (long long)t.size() / 3;
+  *iterations = have;
+  std::copy(t.begin(), t.begin() + 3 * std::min<long long>(have, cap), host_triples);
+  MGX_CATCH
+}
+int mgx_louvain_step_kinds(mgx_louvain_t p, int* host_kinds, int cap, int64_t* launches) {
+  MGX_TRY
+  MGX_REQUIRE(p && launches && cap >= 0 && (host_kinds || cap == 0), "bad argument");
+  require_run(p->last == 1, "mgx_louvain_step_kinds");
+  const std::vector<int>& k = p->fused->kinds;
+  *launches = (int64_t)k.size();
+  std::copy(k.begin(), k.begin() + std::min<size_t>(k.size(), (size_t)cap), host_kinds);
+  MGX_CATCH
+}
+int mgx_louvain_bins(mgx_louvain_t p, int64_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->last == 1, "mgx_louvain_bins");
+  const mgx::louvain_fused_state_t& f = *p->fused;
+  for (int i = 0; i < 4; ++i) out[i] = f.bins[i];
+  out[4] = f.opts.short_max; out[5] = f.opts.wave_max; out[6] = f.opts.seg; out[7] = f.long_items;
+  MGX_CATCH
+}
+int mgx_louvain_set_timing(mgx_louvain_t p, int on) {
+  MGX_TRY
+  auto [ctx, g] = enter(p);
+  if (!p->fused) p->fused.reset(new mgx::louvain_fused_state_t(g.num_nodes, g.num_edges, ctx));
+  p->fused->timing = on != 0;
+  MGX_CATCH
+}
+int mgx_louvain_phase_ms(mgx_louvain_t p, double* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->last == 1, "mgx_louvain_phase_ms");
+  for (int i = 0; i < 6; ++i) out[i] = p->fused->phase_ms[i];
   MGX_CATCH
 }
 
