@@ -21,10 +21,8 @@
 //   MINI    a front of at most KCORE_MINI_MAX entries: ONE workgroup runs expand / filter / expand ... with its own barrier
 //           between them and the lists in LDS (entries spread over the threads by a search in the rows' running sum), until
 //           the front is empty or has outgrown it -- most passes are this small, and a launch costs more than they do.
-// Which kind a launch performs is decided on the device: launch i reads the state word ring[i % 4] that launch i - 1 left
-// (what it was, its k, what it counted), derives its own kind, leaves ring[(i + 1) % 4] for the next and clears
-// ring[(i + 2) % 4].  No launch is idle until the run is over; launches behind the end return at once, so the host
-// enqueues them in batches and waits once per batch.
+// Which kind a launch performs is decided on the device, from the word the launch before left (what it was, its k, what it
+// counted): the ring, the log and the host's batches are launch_chain.hpp's.  No launch is idle until the run is over.
 // The front is two lists: short rows (a thread each, the wave walking its rows in step) and (vertex, segment) items of
 // KCORE_SEG entries for the long ones (a wave each) -- late passes are a few hubs with rows of 10^4 - 10^5 entries.
 // List appends go through wave-private LDS stages (128 short rows, 64 long ones) behind one returning add each, and that
@@ -36,6 +34,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "launch_chain.hpp"
 #include "runtime.hpp"
 #include "wave.hpp"
 #include "worklist.hpp"
@@ -47,9 +46,6 @@ constexpr int KCORE_SEG = KCORE_UNROLL * WAVE;      // entries of a long row one
 constexpr int KCORE_LONG_MIN = 32;       // rows of at least this many entries are long
 constexpr int KCORE_STAGE = 2 * WAVE;
 constexpr int KCORE_MINI_MAX = 2048;     // entries of a front one workgroup peels on its own
-constexpr int KCORE_BATCH_MIN = 64;      // launches per host wait: 64, 128, 256, 256 ... (those behind the end are 2.3 us each)
-constexpr int KCORE_BATCH_MAX = 256;
-constexpr int KCORE_LOG_CAP = 1 << 16;   // launches whose kind is kept for mgx_kcore_step_kinds
 
 enum kcore_kind_t : int { KCORE_INIT = 0, KCORE_MIN = 1, KCORE_LIST = 2, KCORE_EXPAND = 3, KCORE_FILTER = 4, KCORE_DONE = 5, KCORE_MINI = 6 };
 
@@ -72,11 +68,7 @@ struct kcore_totals_t {
 };
 
 // the run's words in device memory, behind one pointer (the kernel's scalar registers are counted)
-struct kcore_control_t {
-  kcore_word_t ring[4];
-  kcore_totals_t totals;
-  int log[KCORE_LOG_CAP];        // the kind of every launch (the first KCORE_LOG_CAP)
-};
+using kcore_control_t = chain_control_t<kcore_word_t, kcore_totals_t>;
 
 struct kcore_step_args_t {
   const int* ro;
@@ -253,15 +245,12 @@ __device__ __forceinline__ void kcore_mini(const kcore_step_args_t& a, const kco
 
 // launch: the launch's number in the run
 __global__ __launch_bounds__(BLOCK) void k_kcore_step(kcore_step_args_t a, unsigned launch) {
-  const kcore_word_t prev = a.ctl->ring[launch & 3];
-  kcore_word_t* const next = a.ctl->ring + ((launch + 1) & 3);
+  const kcore_word_t prev = a.ctl->left_by_prev(launch);
+  kcore_word_t* const next = a.ctl->for_next(launch);
   const unsigned gtid = blockIdx.x * (unsigned)BLOCK + threadIdx.x;      // (the host launches at most 4 workgroups a CU)
   const unsigned gthreads = gridDim.x * (unsigned)BLOCK;
   const bool first_thread = gtid == 0;
-  if (first_thread) {
-    kcore_word_t* const z = a.ctl->ring + ((launch + 2) & 3);     // read by launch i - 2 last, written by launch i + 1 next
-    z->kind = 0; z->k = 0; z->n_cand = 0; z->min_enc = 0; z->shorts = 0; z->items = 0;
-  }
+  if (first_thread) a.ctl->clear_ahead(launch);
 
   // what this launch is, from what the one before it left
   const int front_work = kcore_hi(prev.shorts) + kcore_hi(prev.items);
@@ -294,7 +283,7 @@ __global__ __launch_bounds__(BLOCK) void k_kcore_step(kcore_step_args_t a, unsig
   if (first_thread) {
     next->kind = kind == KCORE_MINI ? KCORE_FILTER : kind;
     next->k = k;
-    if (launch < (unsigned)KCORE_LOG_CAP) a.ctl->log[launch] = kind;
+    a.ctl->log_kind(launch, kind);
     if (new_level && kind != KCORE_DONE) a.ctl->totals.levels += 1;
     if (kind == KCORE_EXPAND) a.ctl->totals.passes += 1;         // (MINI adds its own)
     if (kind == KCORE_DONE) a.ctl->totals.done = 1;
@@ -443,8 +432,7 @@ struct kcore_fused_state_t {
     kcore_totals_t zero{};
     zero.largest = -1;
     h_totals[0] = zero;
-    MGX_HIP(hipMemcpyAsync(&ctl.data()->totals, h_totals.data(), sizeof(kcore_totals_t), hipMemcpyHostToDevice, st));
-    MGX_HIP(hipMemsetAsync(ctl.data()->ring, 0, 4 * sizeof(kcore_word_t), st));
+    kcore_control_t::reset(ctl.data(), h_totals.data(), st);
     kcore_step_args_t a;
     a.ro = ro; a.ci = ci; a.deg = deg; a.core = core;
     a.cand = lists.data(); a.f_items = f_items.data();
@@ -452,19 +440,15 @@ struct kcore_fused_state_t {
     const int blocks = grid_for(n, BLOCK, std::max(ctx.num_cus, 1) * 4);
     long long waits = 0;
     launches = 0;
-    int batch = KCORE_BATCH_MIN;
     // every vertex leaves in a pass of its own at worst: 2 n + 2 launches per level kind, and then the end
     const long long most = 4ll * std::max(n, 1) + 8;
-    for (;;) {
-      for (int j = 0; j < batch; ++j, ++launches)
-        hipLaunchKernelGGL(k_kcore_step, dim3(blocks), dim3(BLOCK), 0, st, a, (unsigned)(launches & 0xffffffffll));
-      MGX_CHECK_LAUNCH("mgx kcore step");
-      h_totals.fetch(&ctl.data()->totals, 1, st);
-      ++waits;
-      if (h_totals->done) break;
-      if (launches > most) throw mgx_error(MGX_E_HIP, "mgx kcore: the run did not end");
-      batch = std::min(batch * 2, KCORE_BATCH_MAX);
-    }
+    launches = run_launch_chain(
+        [&](long long i) { hipLaunchKernelGGL(k_kcore_step, dim3(blocks), dim3(BLOCK), 0, st, a, (unsigned)i); },
+        [&]() {
+          h_totals.fetch(&ctl.data()->totals, 1, st);
+          return h_totals->done != 0;
+        },
+        most, "mgx kcore step", &waits);
     largest = h_totals->largest;
     return {h_totals->levels, h_totals->passes, h_totals->expanded, h_totals->removed, h_totals->stranded, waits};
   }

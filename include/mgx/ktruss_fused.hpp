@@ -25,10 +25,8 @@
 //
 // The supports: the three count kernels of tc_fused.hpp with EDGES = true: the adds go to the three entries of a triangle.
 //
-// The peel: a chain of launches of k_ktruss_step.  Launch i reads the word ring[i % 4] that launch i - 1 left (its kind, its k,
-// the range of `order` it worked on, what it appended and listed), derives its own kind, leaves ring[(i + 1) % 4] and clears
-// ring[(i + 2) % 4].  Launches behind the end return at once; the host enqueues batches (64, 128, 256, 256 ...) and waits once per
-// batch.
+// The peel: a chain of launches of k_ktruss_step (launch_chain.hpp: the ring, the log, the host's batches).  A launch derives its
+// kind from the word the launch before left: its kind, its k, the range of `order` it worked on, what it appended and listed.
 //   MIN     over all edges: the smallest sup of an alive edge (a level begins), or nobody is alive: DONE
 //   LIST    over all edges: the alive ones at sup <= k - 2 are appended to `order`
 //   SEAL    over the front just expanded (none behind a LIST): truss = k, state removed, atomicMax on vtruss of both ends; over what
@@ -52,6 +50,7 @@
 #include <vector>
 
 #include "env.hpp"
+#include "launch_chain.hpp"
 #include "runtime.hpp"
 #include "scan.hpp"
 #include "segsort.hpp"
@@ -65,9 +64,6 @@ namespace mgx {
 constexpr int KTRUSS_SHORT_MAX_DEFAULT = 16;   // shorter rows of at most this many entries: a lane per edge
 constexpr int KTRUSS_SEG_DEFAULT = 512;        // entries of the shorter row one wave takes
 constexpr int KTRUSS_STAGE = 2 * WAVE;         // a wave's LDS stage of list appends
-constexpr int KTRUSS_BATCH_MIN = 64;           // launches per host wait: 64, 128, 256, 256 ...
-constexpr int KTRUSS_BATCH_MAX = 256;
-constexpr int KTRUSS_LOG_CAP = 1 << 16;        // launches whose kind is kept for mgx_ktruss_step_kinds
 
 enum ktruss_kind_t : int { KTRUSS_INIT = 0, KTRUSS_MIN = 1, KTRUSS_LIST = 2, KTRUSS_EXPAND = 3, KTRUSS_SEAL = 4, KTRUSS_DONE = 5 };
 enum : int { KTRUSS_ALIVE = 0, KTRUSS_FRONT = 1, KTRUSS_REMOVED = 2 };
@@ -100,11 +96,7 @@ struct ktruss_totals_t {
   int largest, done;
 };
 
-struct ktruss_control_t {
-  ktruss_word_t ring[4];
-  ktruss_totals_t totals;
-  int log[KTRUSS_LOG_CAP];
-};
+using ktruss_control_t = chain_control_t<ktruss_word_t, ktruss_totals_t>;
 
 struct ktruss_adj_args_t {
   const int* dag_ro;
@@ -230,15 +222,12 @@ __device__ __forceinline__ void ktruss_wave_range(const ktruss_step_args_t& a, i
 
 // launch: the launch's number in the run
 __global__ __launch_bounds__(BLOCK) void k_ktruss_step(ktruss_step_args_t a, unsigned launch) {
-  const ktruss_word_t prev = a.ctl->ring[launch & 3];
-  ktruss_word_t* const next = a.ctl->ring + ((launch + 1) & 3);
+  const ktruss_word_t prev = a.ctl->left_by_prev(launch);
+  ktruss_word_t* const next = a.ctl->for_next(launch);
   const unsigned gtid = blockIdx.x * (unsigned)BLOCK + threadIdx.x;
   const unsigned gthreads = gridDim.x * (unsigned)BLOCK;
   const bool first_thread = gtid == 0;
-  if (first_thread) {
-    ktruss_word_t* const z = a.ctl->ring + ((launch + 2) & 3);      // read by launch i - 2 last, written by launch i + 1 next
-    z->kind = 0; z->k = 0; z->lo = 0; z->hi = 0; z->base = 0; z->app = 0; z->min_enc = 0; z->n_short = 0; z->n_items = 0; z->n_whole = 0;
-  }
+  if (first_thread) a.ctl->clear_ahead(launch);
 
   // what this launch is, from what the one before it left
   const int cur_n = prev.base + prev.app;                    // entries of `order` now
@@ -263,7 +252,7 @@ __global__ __launch_bounds__(BLOCK) void k_ktruss_step(ktruss_step_args_t a, uns
     next->lo = lo;
     next->hi = hi;
     next->base = cur_n;
-    if (launch < (unsigned)KTRUSS_LOG_CAP) a.ctl->log[launch] = kind;
+    a.ctl->log_kind(launch, kind);
     if (kind == KTRUSS_LIST) a.ctl->totals.levels += 1;
     if (kind == KTRUSS_EXPAND) a.ctl->totals.passes += 1;
     if (kind == KTRUSS_DONE && prev.kind != KTRUSS_DONE) {
@@ -492,7 +481,7 @@ struct ktruss_state_t {
     MGX_HIP(hipMemsetAsync(g.truss.data(), 0, M * sizeof(int), st));
     MGX_HIP(hipMemsetAsync(vtruss.data(), 0, N * sizeof(int), st));
     MGX_HIP(hipMemsetAsync(hist.data(), 0, (N + 1) * sizeof(int), st));
-    MGX_HIP(hipMemsetAsync(ctl.data(), 0, sizeof(ktruss_word_t) * 4 + sizeof(ktruss_totals_t), st));
+    ktruss_control_t::reset(ctl.data(), st);
     tc.launches += 6;
   }
 
@@ -530,19 +519,15 @@ struct ktruss_state_t {
     a.stat = d.stat.data(); a.ctl = ctl.data(); a.n = n; a.m = g.m;
     a.short_max = opts.short_max; a.seg = opts.seg; a.item_cap = g.item_cap;
     const int blocks = grid_for(std::max(g.m, 1), BLOCK, std::max(ctx.num_cus, 1) * 4);
-    int batch = KTRUSS_BATCH_MIN;
     // every edge leaves in a pass of its own and a level of its own at worst: MIN, LIST, SEAL, EXPAND, SEAL each, and then the end
     const long long most = 5ll * std::max(g.m, 1) + 8;
-    for (;;) {
-      for (int j = 0; j < batch; ++j, ++peel_launches)
-        hipLaunchKernelGGL(k_ktruss_step, dim3(blocks), dim3(BLOCK), 0, st, a, (unsigned)(peel_launches & 0xffffffffll));
-      MGX_CHECK_LAUNCH("mgx ktruss step");
-      h_totals.fetch(&ctl.data()->totals, 1, st);
-      ++tc.waits;
-      if (h_totals->done) break;
-      if (peel_launches > most) throw mgx_error(MGX_E_HIP, "mgx ktruss: the run did not end");
-      batch = std::min(batch * 2, KTRUSS_BATCH_MAX);
-    }
+    peel_launches = run_launch_chain(
+        [&](long long i) { hipLaunchKernelGGL(k_ktruss_step, dim3(blocks), dim3(BLOCK), 0, st, a, (unsigned)i); },
+        [&]() {
+          h_totals.fetch(&ctl.data()->totals, 1, st);
+          return h_totals->done != 0;
+        },
+        most, "mgx ktruss step", &tc.waits);
     log_launches = peel_launches;
     last_fused = true;
     if (timing) {

@@ -17,9 +17,9 @@
 //              consecutive rejected iterations or at max_iter.
 //   levels     a level that accepted nothing ends the run, as does level == max_levels; else the level is contracted.
 //
-// A level is a chain of launches of k_louvain_step (launch_chain.hpp): launch i reads the word ring[i % 4] that launch i - 1 left,
-// derives its kind -- every thread the same, from that word and from sums no thread of the launch changes --, leaves
-// ring[(i + 1) % 4] and clears ring[(i + 2) % 4].
+// A level is a chain of launches of k_louvain_step (launch_chain.hpp: the ring, the log, the clock, the host's batches; the control
+// is reset and the log read back per level).  A launch derives its kind -- every thread the same -- from the word the launch
+// before left and from sums no thread of the launch changes.
 //   SETUP      over all vertices: lab = own id, k_v, Sigma = k, W, the identity's S_in and S_sq; the rows per body; a long row gets
 //              its table in device memory (a returning add on one cursor) and its (vertex, segment) items, once per level
 //   EVAL       over all vertices, by the entries of the row: up to short_max (at most 16) a lane, labels and weights in registers,
@@ -71,8 +71,6 @@ constexpr int LV_WAVE_CAP = 512;              // entries a wave's table holds (2
 constexpr int LV_SEG_MIN = 64;
 constexpr int LV_SEG_CAP = 1024;
 constexpr int LV_QNUM_LANE_MAX = 32;          // QNUM and SETUP: rows of at most this many entries are summed by their lane
-constexpr int LV_LOG_CAP = 1 << 16;           // launches of a level whose kind is kept for mgx_louvain_step_kinds: a longer level's
-                                              // list ends there, without its DONE
 constexpr int LV_MAX_ITER_MAX = 1 << 20;
 constexpr int LV_MAX_LEVELS_MAX = 64;
 constexpr int LV_EMPTY = -1;                  // a free table slot (labels are >= 0)
@@ -115,8 +113,7 @@ struct lv_totals_t {
   long long q;                 // of the level's labels at its end
   u64 s_in, s_sq;
   long long bins[4];           // vertices per body: no entries, short, wave, long
-  long long clock[5];          // wall clock ticks per LV_T_* (timed runs)
-  long long last_tick;
+  chain_clock_t<5> timed;      // wall clock ticks per LV_T_* (timed runs)
   unsigned long long cursor;   // SETUP: the table slots handed out
   int n_items;                 // SETUP: the long rows' (vertex, segment) items
   int cur, iterations, accepted;
@@ -124,11 +121,8 @@ struct lv_totals_t {
   int pad;
 };
 
-struct lv_control_t {
-  lv_word_t ring[4];
-  lv_totals_t totals;
-  int log[LV_LOG_CAP];
-};
+// (the log holds a level's first CHAIN_LOG_CAP launches: a longer level's list of kinds ends there, without its DONE)
+using lv_control_t = chain_control_t<lv_word_t, lv_totals_t>;
 
 struct lv_trace_t { long long moved, accepted, q; };
 
@@ -301,15 +295,12 @@ __device__ __forceinline__ void lv_block_add2(u64 x, u64 y, u64* px, u64* py, lv
 
 // launch: the launch's number in the level's chain
 __global__ __launch_bounds__(BLOCK) void k_louvain_step(lv_args_t a, unsigned launch) {
-  const lv_word_t prev = a.ctl->ring[launch & 3];
-  lv_word_t* const next = a.ctl->ring + ((launch + 1) & 3);
+  const lv_word_t prev = a.ctl->left_by_prev(launch);
+  lv_word_t* const next = a.ctl->for_next(launch);
   const unsigned gtid = blockIdx.x * (unsigned)BLOCK + threadIdx.x;
   const unsigned gthreads = gridDim.x * (unsigned)BLOCK;
   const bool first_thread = gtid == 0;
-  if (first_thread) {
-    lv_word_t* const z = a.ctl->ring + ((launch + 2) & 3);      // read by launch i - 2 last, written by launch i + 1 next
-    z->kind = 0; z->t = 0; z->cur = 0; z->rejects = 0; z->accepted = 0; z->moved = 0; z->q = 0; z->s_in = 0; z->s_sq = 0;
-  }
+  if (first_thread) a.ctl->clear_ahead(launch);
 
   // what this launch is, from what the one before it left.  totals.w and totals.n_items are SETUP's: nothing changes them later
   const long long W = prev.kind == LV_INIT ? 0 : (long long)a.ctl->totals.w;
@@ -341,10 +332,10 @@ __global__ __launch_bounds__(BLOCK) void k_louvain_step(lv_args_t a, unsigned la
     kind = LV_DONE;
   }
   if (first_thread) {
-    const lv_word_t* const pw = a.ctl->ring + (launch & 3);
+    const lv_word_t* const pw = a.ctl->left_by_prev_at(launch);
     next->kind = kind; next->t = t; next->cur = cur; next->rejects = rejects; next->accepted = accepted; next->q = q;
     lv_totals_t& tot = a.ctl->totals;
-    if (launch < (unsigned)LV_LOG_CAP) a.ctl->log[launch] = kind;
+    a.ctl->log_kind(launch, kind);
     if (kind == LV_QNUM) atomicAdd(&next->moved, pw->moved);      // (the iteration's movers go on through QNUM)
     if (pw->kind == LV_SETUP) { tot.s_in = pw->s_in; tot.s_sq = pw->s_sq; }
     if (pw->kind == LV_QNUM) {
@@ -355,11 +346,7 @@ __global__ __launch_bounds__(BLOCK) void k_louvain_step(lv_args_t a, unsigned la
       tot.q = q; tot.cur = cur; tot.iterations = t; tot.accepted = accepted;
       tot.done |= 1;
     }
-    if (a.timing && pw->kind != LV_DONE) {                   // the time since the launch before began is that launch's
-      const long long now = (long long)wall_clock64();
-      if (pw->kind != LV_INIT) tot.clock[lv_clock_of(pw->kind)] += now - tot.last_tick;
-      tot.last_tick = now;
-    }
+    tot.timed.tick(a.timing, pw->kind, LV_DONE, lv_clock_of(pw->kind));
   }
   if (kind == LV_DONE) return;
 
@@ -649,7 +636,6 @@ struct louvain_fused_state_t {
   long long bins[4] = {0, 0, 0, 0}, long_items = 0, waits = 0;
   bool timing = false;
   double phase_ms[6] = {0, 0, 0, 0, 0, 0};
-  int clock_khz = 0;
 
   louvain_fused_state_t(int n_, long long m_, context_t&) : n(n_), m(m_), opts(lv_opts_t::from_env()) {}
 
@@ -721,7 +707,7 @@ struct louvain_fused_state_t {
     int level = 0;
     for (;; ++level) {
       const bool sums_only = level >= max_levels;             // (max_levels == 0: SETUP alone, for W and the identity's sums)
-      MGX_HIP(hipMemsetAsync(ctl.data(), 0, sizeof(lv_word_t) * 4 + sizeof(lv_totals_t), st));
+      lv_control_t::reset(ctl.data(), st);
       a.g = g;
       a.max_iter = sums_only ? 0 : max_iter;
       const int blocks = grid_for(g.n, BLOCK, std::max(ctx.num_cus, 1) * 4);
@@ -739,7 +725,7 @@ struct louvain_fused_state_t {
       if (level == 0) { W = tot.w; s_in = tot.s_in; s_sq = tot.s_sq; }
       if (W == 0 || sums_only) break;                          // (no votes: identity labels, no level)
       {                                                      // the level's launches up to its DONE, and its trace
-        const size_t have = (size_t)std::min<long long>(enqueued, LV_LOG_CAP);
+        const size_t have = (size_t)std::min<long long>(enqueued, CHAIN_LOG_CAP);
         std::vector<int> log(have);
         MGX_HIP(dtoh(log.data(), (const int*)ctl.data()->log, have, st));
         for (size_t i = 0; i < have; ++i) {
@@ -750,14 +736,8 @@ struct louvain_fused_state_t {
         MGX_HIP(dtoh(tr.data(), (const lv_trace_t*)trace.data(), tr.size(), st));
         for (const lv_trace_t& x : tr) { h_trace.push_back(x.moved); h_trace.push_back(x.accepted); h_trace.push_back(x.q); }
       }
-      if (timing) {
-        if (clock_khz == 0) {
-          int dev = 0;
-          MGX_HIP(hipGetDevice(&dev));
-          MGX_HIP(hipDeviceGetAttribute(&clock_khz, hipDeviceAttributeWallClockRate, dev));
-        }
-        for (int i = 0; i < 5; ++i) phase_ms[i] += clock_khz > 0 ? (double)tot.clock[i] / (double)clock_khz : 0.0;
-      }
+      if (timing)
+        for (int i = 0; i < 5; ++i) phase_ms[i] += chain_ticks_ms(tot.timed.clock[i]);
       for (int b = 0; b < 4; ++b) bins[b] += tot.bins[b];
       long_items += (long long)tot.n_items * tot.iterations;
       iterations += tot.iterations;

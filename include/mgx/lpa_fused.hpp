@@ -16,8 +16,7 @@
 //   kinds      iteration t runs over A_t (LIST) when list_div > 0 and |A_t| <= n / list_div (integer division), over all vertices
 //              (DENSE) otherwise: a function of |A_t|, n and MGX_LPA_LIST_DIV alone (0: always DENSE; 1: always LIST).
 //
-// The run is a chain of launches of k_lpa_step.  Launch i reads the word ring[i % 4] that launch i - 1 left, derives its own kind,
-// leaves ring[(i + 1) % 4] and clears ring[(i + 2) % 4]; launches behind the end return at once.
+// The run is a chain of launches of k_lpa_step (launch_chain.hpp: the ring, the log, the clock, the host's batches).
 //   SETUP   over all vertices: lab = own id, stamp = 0; who has a vote is A_0 (listed); the rows per body are counted
 //   EVAL    over all vertices or over A_t: want[v] from lab_t, by the number of entries of v's rows (self-loops included: an upper
 //           bound of its votes) --
@@ -70,7 +69,6 @@ constexpr int LPA_TABLE_MIN = 32;
 constexpr int LPA_APPLY_LANE_MAX = 32;        // a mover's rows of at most this many entries are marked by its lane
 constexpr int LPA_SEG = 256;                  // entries of a mover's longer rows one wave marks
 constexpr int LPA_STAGE = 2 * WAVE;           // a wave's LDS stage of listed vertices
-constexpr int LPA_LOG_CAP = 1 << 16;          // launches whose kind is kept for mgx_lpa_step_kinds
 constexpr int LPA_MAX_ITER_MAX = 1 << 20;
 constexpr int LPA_EMPTY = -1;                 // a free table slot (labels are >= 0)
 
@@ -115,18 +113,13 @@ struct lpa_word_t {
 struct lpa_totals_t {
   long long rows, overflowed;  // rows evaluated and rows that overflowed, over the run
   long long bins[4];           // vertices per body: no entries, short, wave, long
-  long long clock[4];          // wall clock ticks per LPA_T_* (timed runs)
-  long long last_tick;
+  chain_clock_t<4> timed;      // wall clock ticks per LPA_T_* (timed runs)
   int n_list[2];               // the vertices listed in the lists' halves: [t & 1] is |A_t| once APPLY and MARK of t - 1 are over
   int iterations, converged, unstable;
   int done;                    // bit 0: the run is over
 };
 
-struct lpa_control_t {
-  lpa_word_t ring[4];
-  lpa_totals_t totals;
-  int log[LPA_LOG_CAP];
-};
+using lpa_control_t = chain_control_t<lpa_word_t, lpa_totals_t>;
 
 struct lpa_trace_t { long long unstable, changed, evaluated; };
 
@@ -330,15 +323,12 @@ __device__ __forceinline__ int lpa_clock_of(int kind) {
 
 // launch: the launch's number in the run
 __global__ __launch_bounds__(BLOCK) void k_lpa_step(lpa_step_args_t a, unsigned launch) {
-  const lpa_word_t prev = a.ctl->ring[launch & 3];
-  lpa_word_t* const next = a.ctl->ring + ((launch + 1) & 3);
+  const lpa_word_t prev = a.ctl->left_by_prev(launch);
+  lpa_word_t* const next = a.ctl->for_next(launch);
   const unsigned gtid = blockIdx.x * (unsigned)BLOCK + threadIdx.x;
   const unsigned gthreads = gridDim.x * (unsigned)BLOCK;
   const bool first_thread = gtid == 0;
-  if (first_thread) {
-    lpa_word_t* const z = a.ctl->ring + ((launch + 2) & 3);      // read by launch i - 2 last, written by launch i + 1 next
-    z->kind = 0; z->t = 0; z->dense = 0; z->n_act = 0; z->n_items = 0; z->n_long = 0; z->unstable = 0; z->changed = 0; z->overflowed = 0;
-  }
+  if (first_thread) a.ctl->clear_ahead(launch);
 
   // what this launch is, from what the one before it left
   const bool was_eval = prev.kind == LPA_EVAL_DENSE || prev.kind == LPA_EVAL_LIST;
@@ -362,13 +352,13 @@ __global__ __launch_bounds__(BLOCK) void k_lpa_step(lpa_step_args_t a, unsigned 
     kind = LPA_DONE;
   }
   if (first_thread) {
-    const lpa_word_t* const pw = a.ctl->ring + (launch & 3);     // (read again here: the scalar registers are counted)
+    const lpa_word_t* const pw = a.ctl->left_by_prev_at(launch);   // (read again here: the scalar registers are counted)
     next->kind = kind;
     next->t = t;
     next->dense = dense;
     next->n_act = n_act;
     lpa_totals_t& tot = a.ctl->totals;
-    if (launch < (unsigned)LPA_LOG_CAP) a.ctl->log[launch] = kind;
+    a.ctl->log_kind(launch, kind);
     if (kind == LPA_LONG) atomicAdd(&next->unstable, pw->unstable);      // (the iteration's count goes on through LONG)
     if (kind == LPA_EVAL_DENSE || kind == LPA_EVAL_LIST) tot.n_list[(t + 1) & 1] = 0;      // (A_{t-1}'s half: APPLY and MARK of t fill it)
     if (pw->kind == LPA_LONG) tot.overflowed += pw->overflowed;
@@ -385,11 +375,7 @@ __global__ __launch_bounds__(BLOCK) void k_lpa_step(lpa_step_args_t a, unsigned 
       if (kind == LPA_DONE) { tot.converged = pw->unstable == 0 ? 1 : 0; tot.done |= 1; }
     }
     if (was_apply && pw->t < a.trace_cap) a.trace[pw->t].changed = pw->changed;
-    if (a.timing && pw->kind != LPA_DONE) {                  // the time since the launch before began is that launch's
-      const long long now = (long long)wall_clock64();
-      if (pw->kind != LPA_INIT) tot.clock[lpa_clock_of(pw->kind)] += now - tot.last_tick;
-      tot.last_tick = now;
-    }
+    tot.timed.tick(a.timing, pw->kind, LPA_DONE, lpa_clock_of(pw->kind));
   }
   if (kind == LPA_DONE) return;
 
@@ -400,7 +386,7 @@ __global__ __launch_bounds__(BLOCK) void k_lpa_step(lpa_step_args_t a, unsigned 
   __shared__ lpa_lds_t lds;
 
   if (kind == LPA_LONG) {                                    // a workgroup per listed row
-    const int n_long = min(a.ctl->ring[launch & 3].n_long, a.long_cap);
+    const int n_long = min(a.ctl->left_by_prev_at(launch)->n_long, a.long_cap);
     int unstable = 0, overflowed = 0;
     for (int i = blockIdx.x; i < n_long; i += gridDim.x) {
       const int v = a.long_rows()[i];
@@ -447,7 +433,7 @@ __global__ __launch_bounds__(BLOCK) void k_lpa_step(lpa_step_args_t a, unsigned 
   if (kind == LPA_MARK) {                                    // a wave per (vertex, segment) item of the movers' long rows
     list.out = a.list_of(t + 1);
     list.counter = &a.ctl->totals.n_list[(t + 1) & 1];
-    const int n_items = min(a.ctl->ring[launch & 3].n_items, a.item_cap);
+    const int n_items = min(a.ctl->left_by_prev_at(launch)->n_items, a.item_cap);
     const int tag = t + 1;
     for (int it = wave; it < n_items; it += waves) {
       const int2 item = a.items[it];
@@ -622,7 +608,6 @@ struct lpa_fused_state_t {
   long long bins[4] = {0, 0, 0, 0}, overflowed = 0;
   bool timing = false;
   double phase_ms[4] = {0.0, 0.0, 0.0, 0.0};   // the last timed run: setup, evaluate, long rows, apply
-  int clock_khz = 0;
 
   lpa_fused_state_t(int n_, long long m_, context_t& ctx) : n(n_), m(m_), opts(lpa_opts_t::from_env()), label_stats(n_, ctx) {
     const size_t N = (size_t)std::max(n, 1);
@@ -652,7 +637,7 @@ struct lpa_fused_state_t {
       trace = mem_t<lpa_trace_t>((size_t)max_iter + 1, ctx);
       trace_cap = max_iter + 1;
     }
-    MGX_HIP(hipMemsetAsync(ctl.data(), 0, sizeof(lpa_word_t) * 4 + sizeof(lpa_totals_t), st));
+    lpa_control_t::reset(ctl.data(), st);
     lpa_step_args_t a;
     a.ro = ro; a.ci = ci; a.co = co; a.ri = ri;
     a.vert = vert.data(); a.items = items.data();
@@ -672,14 +657,8 @@ struct lpa_fused_state_t {
           return (h_totals->done & 1) != 0;
         },
         most, "mgx lpa step", &waits);
-    if (timing) {
-      if (clock_khz == 0) {
-        int dev = 0;
-        MGX_HIP(hipGetDevice(&dev));
-        MGX_HIP(hipDeviceGetAttribute(&clock_khz, hipDeviceAttributeWallClockRate, dev));
-      }
-      for (int i = 0; i < 4; ++i) phase_ms[i] = clock_khz > 0 ? (double)h_totals->clock[i] / (double)clock_khz : 0.0;
-    }
+    if (timing)
+      for (int i = 0; i < 4; ++i) phase_ms[i] = chain_ticks_ms(h_totals->timed.clock[i]);
     const lpa_totals_t tot = *h_totals.data();
     const std::vector<long long> ls = label_stats.run(vert.data(), n, ctx);
     ++waits;

@@ -19,8 +19,8 @@
 //              per vertex: reach_in[v] = the sources (with their multiplicity) that have v at depth >= 1, far_in[v] = the sum of
 //              those depths.  On request the depths, int32[count][n], -1 where unreached.
 //
-// The run is a chain of launches of k_msbfs_step.  Launch i reads the word ring[i % 4] that launch i - 1 left, derives its own
-// kind, leaves ring[(i + 1) % 4] and clears ring[(i + 2) % 4]; launches behind the end return at once.
+// The run is a chain of launches of k_msbfs_step (launch_chain.hpp: the ring, the clock, the host's batches; the log is kept by
+// level here, not by launch).
 //   RESET     over all vertices: the batch's seen, front and next are zeroed (the first batch: the per-vertex sums too, and the
 //             rows per body are counted); the batch's per-source results and the level counts are zeroed
 //   SEED      64 threads: the sources' bits (atomicOr: duplicates share a word), A_0 = the distinct sources, e_0, depth 0
@@ -72,7 +72,6 @@ constexpr int MSBFS_CUT_MAX = 1 << 20;          // largest short_max, wave_max a
 constexpr int MSBFS_PULL_DIV_MAX = 1 << 30;     // always pull
 constexpr int MSBFS_STAGE = 8 * WAVE;           // a wave's LDS stage of listed vertices: a dense level lists every vertex, one returning add per stage
 constexpr int MSBFS_CNT_COPIES = 32;            // copies of the level counts, a workgroup adds to copy blockIdx % 32: adders on one row serialise
-constexpr int MSBFS_LOG_CAP = 1 << 16;          // levels whose kind is kept for mgx_msbfs_level_kinds
 
 enum msbfs_kind_t : int {
   MSBFS_INIT = 0, MSBFS_RESET = 1, MSBFS_SEED = 2, MSBFS_PUSH = 3, MSBFS_PULL = 4, MSBFS_LONG = 5, MSBFS_FINALIZE = 6, MSBFS_DONE = 7
@@ -107,18 +106,15 @@ struct msbfs_word_t {
 
 struct msbfs_totals_t {
   long long bins[MSBFS_BINS];
-  long long clock[4];          // wall clock ticks per MSBFS_T_* (timed runs)
-  long long last_tick;
+  chain_clock_t<4> timed;      // wall clock ticks per MSBFS_T_* (timed runs)
   long long push_levels, pull_levels;
   int deepest;                 // levels of the deepest batch
   int done;                    // bit 0: the run is over
 };
 
-struct msbfs_control_t {
-  msbfs_word_t ring[4];
-  msbfs_totals_t totals;
+// (the log: PULL per (batch, level), the first CHAIN_LOG_CAP levels of a run)
+struct msbfs_control_t : chain_control_t<msbfs_word_t, msbfs_totals_t> {
   u64 cnt[3][MSBFS_CNT_COPIES][WAVE];      // the vertices found per bit at depth d, in the copies of cnt[d % 3]
-  int log[MSBFS_LOG_CAP];      // PULL per (batch, level)
 };
 
 struct msbfs_args_t {
@@ -173,15 +169,12 @@ __device__ __forceinline__ int msbfs_clock_of(int kind) {
 
 // launch: the launch's number in the run
 __global__ __launch_bounds__(BLOCK) void k_msbfs_step(msbfs_args_t a, unsigned launch) {
-  const msbfs_word_t prev = a.ctl->ring[launch & 3];
-  msbfs_word_t* const next = a.ctl->ring + ((launch + 1) & 3);
+  const msbfs_word_t prev = a.ctl->left_by_prev(launch);
+  msbfs_word_t* const next = a.ctl->for_next(launch);
   const unsigned gtid = blockIdx.x * (unsigned)BLOCK + threadIdx.x;
   const unsigned gthreads = gridDim.x * (unsigned)BLOCK;
   const bool first_thread = gtid == 0;
-  if (first_thread) {
-    msbfs_word_t* const z = a.ctl->ring + ((launch + 2) & 3);      // read by launch i - 2 last, written by launch i + 1 next
-    z->kind = 0; z->batch = 0; z->t = 0; z->pull = 0; z->n_act = 0; z->n_items = 0; z->e = 0;
-  }
+  if (first_thread) a.ctl->clear_ahead(launch);
 
   // what this launch is, from what the one before it left
   int kind, batch = prev.batch, t = prev.t, pull = prev.pull;
@@ -210,16 +203,12 @@ __global__ __launch_bounds__(BLOCK) void k_msbfs_step(msbfs_args_t a, unsigned l
     msbfs_totals_t& tot = a.ctl->totals;
     if (kind == MSBFS_PUSH || kind == MSBFS_PULL) {
       const long long level = tot.push_levels + tot.pull_levels;
-      if (level < MSBFS_LOG_CAP) a.ctl->log[level] = pull;
+      if (level < CHAIN_LOG_CAP) a.ctl->log[level] = pull;
       if (pull) ++tot.pull_levels; else ++tot.push_levels;
       tot.deepest = max(tot.deepest, t + 1);
     }
     if (kind == MSBFS_DONE) tot.done |= 1;
-    if (a.timing && prev.kind != MSBFS_DONE) {                   // the time since the launch before began is that launch's
-      const long long now = (long long)wall_clock64();
-      if (prev.kind != MSBFS_INIT) tot.clock[msbfs_clock_of(prev.kind)] += now - tot.last_tick;
-      tot.last_tick = now;
-    }
+    tot.timed.tick(a.timing, prev.kind, MSBFS_DONE, msbfs_clock_of(prev.kind));
   }
   if (kind == MSBFS_DONE) return;
 
@@ -498,7 +487,6 @@ struct msbfs_fused_state_t {
   long long bins[MSBFS_BINS] = {0};
   bool timing = false;
   double phase_ms[4] = {0.0, 0.0, 0.0, 0.0};   // the last timed run: push, pull, long rows, finalize
-  int clock_khz = 0;
 
   msbfs_fused_state_t(int n_, long long m_, context_t& ctx) : n(n_), m(m_), opts(msbfs_opts_t::from_env()) {
     const size_t N = (size_t)std::max(n, 1);
@@ -551,7 +539,7 @@ struct msbfs_fused_state_t {
     }
     if (h_sources) MGX_HIP(htod(d_sources.data(), h_sources, (size_t)cnt, st));
     if (want_depths) MGX_HIP(hipMemsetAsync(depth.data(), 0xff, (size_t)cnt * (size_t)n * sizeof(int), st));
-    MGX_HIP(hipMemsetAsync(ctl.data(), 0, sizeof(msbfs_word_t) * 4 + sizeof(msbfs_totals_t), st));
+    msbfs_control_t::reset(ctl.data(), st);
     msbfs_args_t a;
     a.ro = ro; a.ci = ci; a.io = io; a.ia = ia;
     a.words = words.data(); a.list = list.data(); a.items = items.data();
@@ -576,14 +564,8 @@ struct msbfs_fused_state_t {
     const msbfs_totals_t tot = *h_totals.data();
     MGX_HIP(dtoh(h_per_src.data(), (const long long*)per_src.data(), 4 * (size_t)src_cap, st));
     ++waits;
-    if (timing) {
-      if (clock_khz == 0) {
-        int dev = 0;
-        MGX_HIP(hipGetDevice(&dev));
-        MGX_HIP(hipDeviceGetAttribute(&clock_khz, hipDeviceAttributeWallClockRate, dev));
-      }
-      for (int i = 0; i < 4; ++i) phase_ms[i] = clock_khz > 0 ? (double)tot.clock[i] / (double)clock_khz : 0.0;
-    }
+    if (timing)
+      for (int i = 0; i < 4; ++i) phase_ms[i] = chain_ticks_ms(tot.timed.clock[i]);
     for (int b = 0; b < MSBFS_BINS; ++b) bins[b] = tot.bins[b];
     long long sum_reach = 0;
     for (long long s = 0; s < cnt; ++s) sum_reach += reach()[s];

@@ -15,9 +15,8 @@
 // A root is the smallest id that reaches it, and its whole component reaches it: col is already the canonical label; only the
 // pivot's component needs a minimum of its own.
 //
-// The run is a chain of launches of k_scc_step.  Launch i reads the word ring[i % 4] that launch i - 1 left (its kind, the phase,
-// who is alive, the sizes of the front it made), derives its own kind, leaves ring[(i + 1) % 4] and clears ring[(i + 2) % 4].
-// Launches behind the end return at once; the host enqueues batches (64, 128, 256, 256 ...) and waits once per batch.
+// The run is a chain of launches of k_scc_step (launch_chain.hpp: the ring, the log, the clock, the host's batches).  A launch
+// derives its kind from the word the launch before left: its kind, the phase, who is alive, the sizes of the front it made.
 //   DEGINIT  over all vertices: both degrees (row lengths minus self entries; a long row is counted by its wave), everybody alive
 //   LIST     over all vertices: whoever has a degree of 0 leaves (label = own id) and is the first trim front
 //   EXPAND   over a front of vertices that have left -- a trim front, the pivot's component, a round's components: one returning
@@ -78,7 +77,6 @@ namespace mgx {
 constexpr int SCC_LONG_MIN_DEFAULT = 32;    // rows of at least this many entries are long
 constexpr int SCC_SEG_DEFAULT = 256;        // entries of a long row one wave takes
 constexpr int SCC_STAGE = 2 * WAVE;         // a wave's LDS stage of front vertices
-constexpr int SCC_LOG_CAP = 1 << 16;        // launches whose kind is kept for mgx_scc_step_kinds
 constexpr int SCC_NONE = 0x7fffffff;        // col of a vertex the pivot has not reached
 
 enum scc_kind_t : int {
@@ -115,17 +113,12 @@ struct scc_word_t {
 
 struct scc_totals_t {
   long long trimmed, pivot_size, rounds;
-  long long clock[4];          // wall clock ticks per SCC_T_* (timed runs)
-  long long last_tick;
+  chain_clock_t<4> timed;      // wall clock ticks per SCC_T_* (timed runs)
   int pivot_min;               // the smallest id BWD has claimed in the pivot phase
   int done;                    // bit 0: the run is over; bit 1: a fixpoint did not end and the host ends the run (a bug: `streak` in k_scc_step)
 };
 
-struct scc_control_t {
-  scc_word_t ring[4];
-  scc_totals_t totals;
-  int log[SCC_LOG_CAP];
-};
+using scc_control_t = chain_control_t<scc_word_t, scc_totals_t>;
 
 // what the run keeps per vertex, in one place: a sweep that meets u looks at its state, colour and stamp together
 struct alignas(32) scc_vertex_t {
@@ -297,15 +290,12 @@ __device__ __forceinline__ int scc_clock_of(int kind, int phase) {
 
 // launch: the launch's number in the run
 __global__ __launch_bounds__(BLOCK) void k_scc_step(scc_step_args_t a, unsigned launch) {
-  const scc_word_t prev = a.ctl->ring[launch & 3];
-  scc_word_t* const next = a.ctl->ring + ((launch + 1) & 3);
+  const scc_word_t prev = a.ctl->left_by_prev(launch);
+  scc_word_t* const next = a.ctl->for_next(launch);
   const unsigned gtid = blockIdx.x * (unsigned)BLOCK + threadIdx.x;
   const unsigned gthreads = gridDim.x * (unsigned)BLOCK;
   const bool first_thread = gtid == 0;
-  if (first_thread) {
-    scc_word_t* const z = a.ctl->ring + ((launch + 2) & 3);      // read by launch i - 2 last, written by launch i + 1 next
-    z->best = 0; z->kind = 0; z->phase = 0; z->alive = 0; z->tag = 0; z->pivot_enc = 0; z->n_rows = 0; z->n_items = 0; z->streak = 0;
-  }
+  if (first_thread) a.ctl->clear_ahead(launch);
 
   // what this launch is, from what the one before it left
   const bool removing = prev.kind == SCC_LIST || prev.kind == SCC_EXPAND || prev.kind == SCC_SEAL;     // (its front is who left)
@@ -347,16 +337,12 @@ __global__ __launch_bounds__(BLOCK) void k_scc_step(scc_step_args_t a, unsigned 
     next->streak = streak;
     scc_totals_t& t = a.ctl->totals;
     if (kind != SCC_DONE && streak > a.n + 2) t.done |= 2;
-    if (launch < (unsigned)SCC_LOG_CAP) a.ctl->log[launch] = kind;
+    a.ctl->log_kind(launch, kind);
     if (prev.kind == SCC_LIST || prev.kind == SCC_EXPAND) t.trimmed += prev.n_rows;
     if (prev.kind == SCC_SEAL && prev.phase == SCC_PH_PIVOT) t.pivot_size = prev.n_rows;
     if (kind == SCC_RINIT && !pivot_phase) t.rounds += 1;
     if (kind == SCC_RINIT && pivot_phase) t.pivot_min = 0x7fffffff - prev.pivot_enc;      // (PPICK left the pivot)
-    if (a.timing && prev.kind != SCC_DONE) {                  // the time since the launch before began is that launch's
-      const long long now = (long long)wall_clock64();
-      if (prev.kind != SCC_INIT) t.clock[scc_clock_of(prev.kind, prev.phase)] += now - t.last_tick;
-      t.last_tick = now;
-    }
+    t.timed.tick(a.timing, prev.kind, SCC_DONE, scc_clock_of(prev.kind, prev.phase));
     if (kind == SCC_DONE) t.done |= 1;
   }
   if (kind == SCC_DONE) return;
@@ -391,7 +377,7 @@ __global__ __launch_bounds__(BLOCK) void k_scc_step(scc_step_args_t a, unsigned 
   }
   if (kind == SCC_PMAX || kind == SCC_PPICK) {
     // PMAX: the largest product; PPICK: INT_MAX - (the smallest id that has it), so that a cleared word says "nobody"
-    const u64 at_best = a.ctl->ring[launch & 3].best;          // (read here, not kept from the launch's start: the scalar registers are counted)
+    const u64 at_best = a.ctl->left_by_prev_at(launch)->best;         // (read here, not kept from the launch's start: the scalar registers are counted)
     u64 best = 0;
     for (unsigned base = (unsigned)wave * WAVE; base < (unsigned)a.n; base += (unsigned)waves * WAVE) {
       const int v = (int)(base + lane);
@@ -415,7 +401,7 @@ __global__ __launch_bounds__(BLOCK) void k_scc_step(scc_step_args_t a, unsigned 
     // who joins the front, and which of its rows the front's consumer walks
     const int sides = kind == SCC_RINIT ? SCC_OUT : (kind == SCC_ROOTS ? SCC_IN : (SCC_OUT | SCC_IN));
     const int pivot_label = (kind == SCC_SEAL && pivot_phase) ? a.ctl->totals.pivot_min : -1;
-    const int pivot = 0x7fffffff - a.ctl->ring[launch & 3].pivot_enc;      // (RINIT of the pivot phase: PPICK left it; read here, as at_best is)
+    const int pivot = 0x7fffffff - a.ctl->left_by_prev_at(launch)->pivot_enc;     // (RINIT of the pivot phase: PPICK left it; read here, as at_best is)
     for (unsigned base = (unsigned)wave * WAVE; base < (unsigned)a.n; base += (unsigned)waves * WAVE) {
       const int v = (int)(base + lane);
       const bool is_alive = base + lane < (unsigned)a.n && a.vert[v].state == SCC_ALIVE;
@@ -442,7 +428,7 @@ __global__ __launch_bounds__(BLOCK) void k_scc_step(scc_step_args_t a, unsigned 
     return;
   }
   {                                                          // EXPAND, FWD, BWD: over the front the launch before made
-    const scc_word_t* const made = a.ctl->ring + (launch & 3);   // (the front's sizes are read here: the scalar registers are counted)
+    const scc_word_t* const made = a.ctl->left_by_prev_at(launch);  // (the front's sizes are read here: the scalar registers are counted)
     const int n_rows = made->n_rows, n_items = made->n_items;
     scc_visit_t w;
     w.stamp = kind == SCC_BWD ? tag : (int)(launch + 1);
@@ -469,7 +455,6 @@ struct scc_fused_state_t {
   long long launches = -1;                     // of the last run, the idle ones behind its end included (-1: no run yet)
   bool timing = false;                         // mgx_scc_set_timing: the launches keep the device's wall clock per phase
   double phase_ms[4] = {0.0, 0.0, 0.0, 0.0};   // the last timed run: init, trim, pivot, rounds
-  int clock_khz = 0;
 
   scc_fused_state_t(int n_, long long m, context_t& ctx) : n(n_), opts(scc_opts_t::from_env()), label_stats(n_, ctx) {
     const size_t N = (size_t)std::max(n, 1);
@@ -493,7 +478,7 @@ struct scc_fused_state_t {
       launches = 0;
       return {0, 0, 0, 0, 0, 0, 0, 0};
     }
-    MGX_HIP(hipMemsetAsync(ctl.data(), 0, sizeof(scc_word_t) * 4 + sizeof(scc_totals_t), st));
+    scc_control_t::reset(ctl.data(), st);
     scc_step_args_t a;
     a.ro = ro; a.ci = ci; a.co = co; a.ri = ri;
     a.vert = vert.data(); a.label = label.data(); a.items = items.data();
@@ -511,14 +496,8 @@ struct scc_fused_state_t {
           return h_totals->done != 0;
         },
         most, "mgx scc step", &waits);
-    if (timing) {
-      if (clock_khz == 0) {
-        int dev = 0;
-        MGX_HIP(hipGetDevice(&dev));
-        MGX_HIP(hipDeviceGetAttribute(&clock_khz, hipDeviceAttributeWallClockRate, dev));
-      }
-      for (int i = 0; i < 4; ++i) phase_ms[i] = clock_khz > 0 ? (double)h_totals->clock[i] / (double)clock_khz : 0.0;
-    }
+    if (timing)
+      for (int i = 0; i < 4; ++i) phase_ms[i] = chain_ticks_ms(h_totals->timed.clock[i]);
     const std::vector<long long> ls = label_stats.run(label.data(), n, ctx);      // (the stats CC reports, by CC's kernels)
     ++waits;
     launches = enqueued;

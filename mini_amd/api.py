@@ -31,6 +31,36 @@ def _dev_ptr(x):
     return C.c_void_p(int(x))
 
 
+CHAIN_LOG_CAP = 1 << 16     # include/mgx/launch_chain.hpp: the launches (MsBfsProblem: levels) of a run whose kind is kept
+
+
+class _StepKinds:
+    """A fused path that is a chain of launches (include/mgx/launch_chain.hpp).  `_C` is the handle's C prefix; the class says what
+    its STEP_KINDS are."""
+
+    def step_kinds(self):
+        """what every launch of the last run() was, in order (the first CHAIN_LOG_CAP): codes of STEP_KINDS"""
+        n = C.c_int64()
+        out = np.empty(CHAIN_LOG_CAP, dtype=np.int32)
+        check(getattr(lib, self._C + "_step_kinds")(self._h, _ptr(out), len(out), C.byref(n)))
+        return out[:min(n.value, len(out))].copy()
+
+
+class _Timed:
+    """A fused path that times its phases on the device when asked.  `_C` is the handle's C prefix; the class says what its PHASES
+    are."""
+
+    def set_timing(self, on):
+        """measurement tools: every run() keeps the time of each of PHASES"""
+        check(getattr(lib, self._C + "_set_timing")(self._h, int(bool(on))))
+
+    def phase_ms(self):
+        """ms per entry of PHASES of the last timed run()"""
+        out = (C.c_double * len(self.PHASES))()
+        check(getattr(lib, self._C + "_phase_ms")(self._h, out))
+        return dict(zip(self.PHASES, (float(x) for x in out)))
+
+
 class Context:
     """standard_context_t: one device, one stream, scratch arena (tests/bfs/test_bfs.cu:22)."""
 
@@ -567,8 +597,10 @@ class PrProblem:
             self._h = None
 
 
-class KcoreProblem:
+class KcoreProblem(_StepKinds):
     """kcore_problem_t + kcore_enactor_t (gunrock/src/kcore/)."""
+
+    _C = "mgx_kcore"
 
     def __init__(self, graph):
         h = C.c_void_p()
@@ -595,13 +627,6 @@ class KcoreProblem:
                                "host_waits": st[5]}
 
     STEP_KINDS = {1: "min", 2: "list", 3: "expand", 4: "filter", 5: "idle", 6: "mini"}
-
-    def step_kinds(self):
-        """what every launch of the last run() was, in order (the first 65536): codes of STEP_KINDS"""
-        n = C.c_int64()
-        out = np.empty(1 << 16, dtype=np.int32)
-        check(lib.mgx_kcore_step_kinds(self._h, _ptr(out), len(out), C.byref(n)))
-        return out[:min(n.value, len(out))].copy()
 
     def num_cores(self):
         out = np.empty(self.graph.num_nodes, dtype=np.int32)
@@ -951,12 +976,15 @@ class TcProblem:
             self._h = None
 
 
-class KtrussProblem:
+class KtrussProblem(_StepKinds, _Timed):
     """k-truss decomposition: ktruss_problem_t + ktruss_enactor_t, and the fused path beside them, on the underlying
-    simple undirected graph, in original ids.  The getters describe the last run of either path."""
+    simple undirected graph, in original ids.  The getters describe the last run of either path.  step_kinds() are the launches of
+    the last run()'s peel; a timed run() records events round its support launches and its peel."""
 
+    _C = "mgx_ktruss"
     KEYS = ("max_truss", "edges", "triangles", "levels", "passes", "built", "host_waits", "launches")
     STEP_KINDS = {1: "min", 2: "list", 3: "expand", 4: "seal", 5: "idle"}
+    PHASES = ("support", "peel")
 
     def __init__(self, graph):
         h = C.c_void_p()
@@ -1044,23 +1072,6 @@ class KtrussProblem:
         """(src, dst, truss) in the order of the oriented graph's entries: what the edge ids of order() and adjacency() index"""
         return self._raw_edges()
 
-    def step_kinds(self):
-        """what every launch of the last run()'s peel was, in order (the first 65536): codes of STEP_KINDS"""
-        n = C.c_int64()
-        out = np.empty(1 << 16, dtype=np.int32)
-        check(lib.mgx_ktruss_step_kinds(self._h, _ptr(out), len(out), C.byref(n)))
-        return out[:min(n.value, len(out))].copy()
-
-    def set_timing(self, on):
-        """measurement tools: every run() records events round its support launches and its peel"""
-        check(lib.mgx_ktruss_set_timing(self._h, int(bool(on))))
-
-    def phase_ms(self):
-        """ms of the support launches and of the peel of the last timed run()"""
-        out = (C.c_double * 2)()
-        check(lib.mgx_ktruss_phase_ms(self._h, out))
-        return {"support": out[0], "peel": out[1]}
-
     def truss_edges(self, k):
         """(u, v) of the edges of trussness >= k: the k-truss with its isolated vertices dropped"""
         u, v, t = self.edges()
@@ -1083,11 +1094,13 @@ class KtrussProblem:
             self._h = None
 
 
-class SccProblem:
+class SccProblem(_StepKinds, _Timed):
     """Strongly connected components: scc_problem_t + scc_enactor_t, and the fused path beside them, on the directed
     graph of the CSR entries, which needs its genuine CSC (Graph.build_csc, or one uploaded with the graph).  labels() describes
-    the last run of either path: label[v] = the smallest vertex id of v's strongly connected component."""
+    the last run of either path: label[v] = the smallest vertex id of v's strongly connected component.  PHASES: the degree init,
+    the trims, the pivot phase and the rounds, by the device's wall clock in every launch of a timed run()."""
 
+    _C = "mgx_scc"
     KEYS = ("components", "largest", "largest_label", "trimmed", "pivot_size", "rounds", "host_waits", "launches")
     STEP_KINDS = {1: "degrees", 2: "list", 3: "expand", 4: "pivot_max", 5: "pivot_pick", 6: "round_init", 7: "forward", 8: "roots",
                   9: "backward", 10: "seal", 11: "idle"}
@@ -1122,34 +1135,19 @@ class SccProblem:
         check(lib.mgx_scc_labels_device(self._h, C.byref(p)))
         return p.value
 
-    def step_kinds(self):
-        """what every launch of the last run() was, in order (the first 65536): codes of STEP_KINDS"""
-        n = C.c_int64()
-        out = np.empty(1 << 16, dtype=np.int32)
-        check(lib.mgx_scc_step_kinds(self._h, _ptr(out), len(out), C.byref(n)))
-        return out[:min(n.value, len(out))].copy()
-
-    def set_timing(self, on):
-        """measurement tools: every launch of a run() keeps the device's wall clock per phase"""
-        check(lib.mgx_scc_set_timing(self._h, int(bool(on))))
-
-    def phase_ms(self):
-        """ms of the degree init, the trims, the pivot phase and the rounds of the last timed run()"""
-        out = (C.c_double * 4)()
-        check(lib.mgx_scc_phase_ms(self._h, out))
-        return dict(zip(self.PHASES, (float(x) for x in out)))
-
     def close(self):
         if self._h:
             lib.mgx_scc_free(self._h)
             self._h = None
 
 
-class LpaProblem:
+class LpaProblem(_StepKinds, _Timed):
     """Label propagation: lpa_problem_t + lpa_enactor_t, and the fused path beside them.  Every vertex takes the label
     most of its votes carry; labels() describes the last run of either path.  symmetric=True is the caller's word that every
-    entry has its reverse; symmetric=False counts every entry at both of its ends and needs the graph's genuine CSC."""
+    entry has its reverse; symmetric=False counts every entry at both of its ends and needs the graph's genuine CSC.  PHASES are
+    timed by the device's wall clock in every launch of a timed run()."""
 
+    _C = "mgx_lpa"
     SYNC, LAZY = _lib.MGX_LPA_SYNC, _lib.MGX_LPA_LAZY
     SEED = 15485863
     KEYS = ("communities", "largest", "largest_label", "iterations", "converged", "unstable", "evaluated", "overflowed", "host_waits",
@@ -1197,27 +1195,11 @@ class LpaProblem:
         check(lib.mgx_lpa_trace(self._h, _ptr(out), n.value, C.byref(n)))
         return out
 
-    def step_kinds(self):
-        """what every launch of the last run() was, in order (the first 65536): codes of STEP_KINDS"""
-        n = C.c_int64()
-        out = np.empty(1 << 16, dtype=np.int32)
-        check(lib.mgx_lpa_step_kinds(self._h, _ptr(out), len(out), C.byref(n)))
-        return out[:min(n.value, len(out))].copy()
-
     def bins(self):
         """the last run(): vertices per body, the switches as read, rows that overflowed their table"""
         out = (C.c_int64 * 9)()
         check(lib.mgx_lpa_bins(self._h, out))
         return dict(zip(self.BINS, (int(x) for x in out)))
-
-    def set_timing(self, on):
-        """measurement tools: every launch of a run() keeps the device's wall clock per phase"""
-        check(lib.mgx_lpa_set_timing(self._h, int(bool(on))))
-
-    def phase_ms(self):
-        out = (C.c_double * 4)()
-        check(lib.mgx_lpa_phase_ms(self._h, out))
-        return dict(zip(self.PHASES, (float(x) for x in out)))
 
     def modularity(self):
         """(Q, S_in, S_sq, W) of the last run's labels, with the votes of that run's `symmetric`"""
@@ -1229,12 +1211,14 @@ class LpaProblem:
             self._h = None
 
 
-class LouvainProblem:
+class LouvainProblem(_Timed):
     """Louvain community detection: levels of local moves that raise the modularity, each contracted into the next
     level's weighted graph.  Integer arithmetic throughout: the run agrees with tests/louvain_model.py bit for bit.
     symmetric=True is the caller's word that every entry has its reverse; symmetric=False counts every entry at both of its ends
-    and needs the graph's genuine CSC."""
+    and needs the graph's genuine CSC.  PHASES are timed by the device's wall clock in every launch of a timed run(), the
+    aggregation by the host's."""
 
+    _C = "mgx_louvain"
     SEED = 0x9E3779B9
     KEYS = ("communities", "largest", "largest_id", "levels", "s_in", "s_sq", "w", "host_waits", "launches", "iterations")
     LEVEL_KEYS = ("vertices", "entries", "iterations", "accepted", "communities", "qnum")
@@ -1320,22 +1304,13 @@ class LouvainProblem:
         check(lib.mgx_louvain_bins(self._h, out))
         return dict(zip(self.BINS, (int(x) for x in out)))
 
-    def set_timing(self, on):
-        """measurement tools: every launch of a run() keeps the device's wall clock per phase"""
-        check(lib.mgx_louvain_set_timing(self._h, int(bool(on))))
-
-    def phase_ms(self):
-        out = (C.c_double * 6)()
-        check(lib.mgx_louvain_phase_ms(self._h, out))
-        return dict(zip(self.PHASES, (float(x) for x in out)))
-
     def close(self):
         if self._h:
             lib.mgx_louvain_free(self._h)
             self._h = None
 
 
-class MsBfsProblem:
+class MsBfsProblem(_Timed):
     """Bit-parallel multi-source BFS: BFS depths from many sources at once, 64 traversals to a 64-bit word per vertex,
     and what follows from them -- reach, farness, eccentricity, harmonic and closeness centrality per source, and per vertex how
     many sources reach it and the sum of their depths.  run() is the fused path, enact() the operator path; the getters describe
@@ -1344,6 +1319,7 @@ class MsBfsProblem:
     to get that).  symmetric=True is the caller's word that every entry has its reverse, which lets the dense levels pull over
     the rows themselves; symmetric=False pulls over the graph's genuine CSC where it has one and pushes every level where not."""
 
+    _C = "mgx_msbfs"
     KEYS = ("sources", "batches", "deepest", "reach", "push_levels", "pull_levels", "host_waits", "launches", "csc", "depths")
     PUSH, PULL = _lib.MGX_MSBFS_PUSH, _lib.MGX_MSBFS_PULL
     PHASES = ("push", "pull", "long_rows", "finalize")
@@ -1433,9 +1409,9 @@ class MsBfsProblem:
         """PUSH or PULL per (batch, level) of the last run(), the batches behind each other (the first 65536)"""
         n = C.c_int64()
         check(lib.mgx_msbfs_level_kinds(self._h, None, 0, C.byref(n)))
-        out = np.zeros(max(min(n.value, 1 << 16), 1), dtype=np.int32)
+        out = np.zeros(max(min(n.value, CHAIN_LOG_CAP), 1), dtype=np.int32)
         check(lib.mgx_msbfs_level_kinds(self._h, _ptr(out), len(out), C.byref(n)))
-        return out[:min(n.value, 1 << 16)].copy()
+        return out[:min(n.value, CHAIN_LOG_CAP)].copy()
 
     def bins(self):
         """the last run(): out- and in-rows per body, their segments, the switches as read"""
@@ -1443,22 +1419,13 @@ class MsBfsProblem:
         check(lib.mgx_msbfs_bins(self._h, out))
         return dict(zip(self.BINS, (int(x) for x in out)))
 
-    def set_timing(self, on):
-        """measurement tools: every launch of a run() keeps the device's wall clock per phase"""
-        check(lib.mgx_msbfs_set_timing(self._h, int(bool(on))))
-
-    def phase_ms(self):
-        out = (C.c_double * 4)()
-        check(lib.mgx_msbfs_phase_ms(self._h, out))
-        return dict(zip(self.PHASES, (float(x) for x in out)))
-
     def close(self):
         if self._h:
             lib.mgx_msbfs_free(self._h)
             self._h = None
 
 
-class RandomWalkProblem:
+class RandomWalkProblem(_Timed):
     """Random walks and node2vec sampling: DeepWalk / node2vec corpora, Monte-Carlo personalised PageRank, walk-based
     sampling.  run() is the fused path (one launch, a lane per walker), enact() the operator path (a filter per step); the getters
     describe the last run of either, and both give the same results bit for bit.  Every draw is a pure function of (seed, walker,
@@ -1472,6 +1439,7 @@ class RandomWalkProblem:
       * walks follow the OUT-entries: on a directed graph "prev has an entry to c" is asked of prev's out-row, and a vertex without
         out-entries ends the walk (restart > 0: it jumps to its start instead)."""
 
+    _C = "mgx_rw"
     KEYS = ("walkers", "length", "steps", "dead_ends", "restarts", "tries", "fallbacks", "sorted_copy", "launches", "host_waits")
     PHASES = ("setup", "walk")
     BINS = ("none", "short", "wave", "long", "segments", "short_max", "wave_max", "seg", "tries", "tile")
@@ -1554,15 +1522,6 @@ class RandomWalkProblem:
         out = (C.c_int64 * 10)()
         check(lib.mgx_rw_bins(self._h, out))
         return dict(zip(self.BINS, (int(x) for x in out)))
-
-    def set_timing(self, on):
-        """measurement tools: a run() keeps the device time of its setup and of its walk"""
-        check(lib.mgx_rw_set_timing(self._h, int(bool(on))))
-
-    def phase_ms(self):
-        out = (C.c_double * 2)()
-        check(lib.mgx_rw_phase_ms(self._h, out))
-        return dict(zip(self.PHASES, (float(x) for x in out)))
 
     def close(self):
         if self._h:

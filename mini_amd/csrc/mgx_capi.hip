@@ -323,6 +323,37 @@ static void put_stats(int64_t* stats, size_t count, const std::vector<long long>
   MGX_REQUIRE(v.size() == count, "internal: a run's stats do not have the size the header states");
   if (stats) std::copy(v.begin(), v.end(), stats);
 }
+// What the chains of launches (mgx/launch_chain.hpp) share at this boundary.  `state`: the handle's lazily made state; `ran`: its
+// count of the last run's launches, below 0 while the log holds no run.
+// the kinds of the last run's launches: all of them counted, the first min(cap, CHAIN_LOG_CAP) written
+template <typename H, typename S>
+static int chain_step_kinds(H* p, std::unique_ptr<S> H::*state, long long S::*ran, const char* who, int* host_kinds, int cap,
+                            int64_t* launches) {
+  MGX_TRY
+  MGX_REQUIRE(p && launches && cap >= 0 && (host_kinds || cap == 0), "bad argument");
+  const S* st = (p->*state).get();
+  require_run(st && st->*ran >= 0, who);
+  *launches = st->*ran;
+  read_back(p, host_kinds, (const int*)st->ctl.data()->log, (size_t)std::min<long long>({st->*ran, (long long)cap, (long long)mgx::CHAIN_LOG_CAP}));
+  MGX_CATCH
+}
+template <typename H, typename S>
+static int chain_set_timing(H* p, std::unique_ptr<S> H::*state, int on) {
+  MGX_TRY
+  auto [ctx, g] = enter(p);
+  if (!(p->*state)) (p->*state).reset(new S(g.num_nodes, g.num_edges, ctx));
+  (p->*state)->timing = on != 0;
+  MGX_CATCH
+}
+template <typename H, typename S, int K>
+static int chain_phase_ms(H* p, std::unique_ptr<S> H::*state, long long S::*ran, double (S::*ms)[K], const char* who, double* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  const S* st = (p->*state).get();
+  require_run(st && st->*ran >= 0, who);
+  std::copy(st->*ms, st->*ms + K, out);
+  MGX_CATCH
+}
 
 // neighbourhood reduce with a plain per-vertex gather as the functor
 namespace {
@@ -2333,15 +2364,7 @@ int mgx_kcore_run(mgx_kcore_t p, int* largest_k_core, int64_t* stats) {
   MGX_CATCH
 }
 int mgx_kcore_step_kinds(mgx_kcore_t p, int* host_kinds, int cap, int64_t* launches) {
-  MGX_TRY
-  MGX_REQUIRE(p && launches && cap >= 0 && (host_kinds || cap == 0), "bad argument");
-  MGX_REQUIRE(p->fused, "mgx_kcore_step_kinds: no fused run yet");
-  use_device(p->g->c);
-  p->g->c->ctx->synchronize();
-  *launches = p->fused->launches;
-  const long long have = std::min<long long>(std::min<long long>(p->fused->launches, mgx::KCORE_LOG_CAP), cap);
-  MGX_HIP(mgx::dtoh(host_kinds, p->fused->ctl.data()->log, (size_t)have));
-  MGX_CATCH
+  return chain_step_kinds(p, &mgx_kcore_s::fused, &mgx::kcore_fused_state_t::launches, "mgx_kcore_step_kinds", host_kinds, cap, launches);
 }
 int mgx_kcore_num_cores(mgx_kcore_t p, int* host) {
   MGX_TRY
@@ -3196,13 +3219,7 @@ int mgx_ktruss_vertex_truss_device(mgx_ktruss_t p, const int** out) {
   MGX_CATCH
 }
 int mgx_ktruss_step_kinds(mgx_ktruss_t p, int* host_kinds, int cap, int64_t* launches) {
-  MGX_TRY
-  MGX_REQUIRE(p && launches && cap >= 0 && (host_kinds || cap == 0), "bad argument");
-  require_run(p->st && p->st->log_launches >= 0, "mgx_ktruss_step_kinds");
-  *launches = p->st->log_launches;
-  const long long have = std::min<long long>(std::min<long long>(p->st->log_launches, mgx::KTRUSS_LOG_CAP), cap);
-  read_back(p, host_kinds, (const int*)p->st->ctl.data()->log, (size_t)have);
-  MGX_CATCH
+  return chain_step_kinds(p, &mgx_ktruss_s::st, &mgx::ktruss_state_t::log_launches, "mgx_ktruss_step_kinds", host_kinds, cap, launches);
 }
 int mgx_ktruss_set_timing(mgx_ktruss_t p, int on) {
   MGX_TRY
@@ -3211,12 +3228,7 @@ int mgx_ktruss_set_timing(mgx_ktruss_t p, int on) {
   MGX_CATCH
 }
 int mgx_ktruss_phase_ms(mgx_ktruss_t p, double* out) {
-  MGX_TRY
-  MGX_REQUIRE(p && out, "NULL argument");
-  require_run(p->st && p->st->log_launches >= 0, "mgx_ktruss_phase_ms");
-  out[0] = p->st->phase_ms[0];
-  out[1] = p->st->phase_ms[1];
-  MGX_CATCH
+  return chain_phase_ms(p, &mgx_ktruss_s::st, &mgx::ktruss_state_t::log_launches, &mgx::ktruss_state_t::phase_ms, "mgx_ktruss_phase_ms", out);
 }
 
 // ---- strongly connected components --------------------------------------------------
@@ -3273,27 +3285,11 @@ int mgx_scc_labels_device(mgx_scc_t p, const int** out) {
   MGX_CATCH
 }
 int mgx_scc_step_kinds(mgx_scc_t p, int* host_kinds, int cap, int64_t* launches) {
-  MGX_TRY
-  MGX_REQUIRE(p && launches && cap >= 0 && (host_kinds || cap == 0), "bad argument");
-  require_run(p->fused && p->fused->launches >= 0, "mgx_scc_step_kinds");
-  *launches = p->fused->launches;
-  const long long have = std::min<long long>(std::min<long long>(p->fused->launches, mgx::SCC_LOG_CAP), cap);
-  read_back(p, host_kinds, (const int*)p->fused->ctl.data()->log, (size_t)have);
-  MGX_CATCH
+  return chain_step_kinds(p, &mgx_scc_s::fused, &mgx::scc_fused_state_t::launches, "mgx_scc_step_kinds", host_kinds, cap, launches);
 }
-int mgx_scc_set_timing(mgx_scc_t p, int on) {
-  MGX_TRY
-  auto [ctx, g] = enter(p);
-  if (!p->fused) p->fused.reset(new mgx::scc_fused_state_t(g.num_nodes, g.num_edges, ctx));
-  p->fused->timing = on != 0;
-  MGX_CATCH
-}
+int mgx_scc_set_timing(mgx_scc_t p, int on) { return chain_set_timing(p, &mgx_scc_s::fused, on); }
 int mgx_scc_phase_ms(mgx_scc_t p, double* out) {
-  MGX_TRY
-  MGX_REQUIRE(p && out, "NULL argument");
-  require_run(p->fused && p->fused->launches >= 0, "mgx_scc_phase_ms");
-  for (int i = 0; i < 4; ++i) out[i] = p->fused->phase_ms[i];
-  MGX_CATCH
+  return chain_phase_ms(p, &mgx_scc_s::fused, &mgx::scc_fused_state_t::launches, &mgx::scc_fused_state_t::phase_ms, "mgx_scc_phase_ms", out);
 }
 
 // ---- label propagation and modularity ----------------------------------------------
@@ -3394,13 +3390,7 @@ int mgx_lpa_trace(mgx_lpa_t p, int64_t* host_triples, int cap, int64_t* iteratio
   MGX_CATCH
 }
 int mgx_lpa_step_kinds(mgx_lpa_t p, int* host_kinds, int cap, int64_t* launches) {
-  MGX_TRY
-  MGX_REQUIRE(p && launches && cap >= 0 && (host_kinds || cap == 0), "bad argument");
-  require_run(p->fused && p->fused->launches >= 0, "mgx_lpa_step_kinds");
-  *launches = p->fused->launches;
-  const long long have = std::min<long long>(std::min<long long>(p->fused->launches, mgx::LPA_LOG_CAP), cap);
-  read_back(p, host_kinds, (const int*)p->fused->ctl.data()->log, (size_t)have);
-  MGX_CATCH
+  return chain_step_kinds(p, &mgx_lpa_s::fused, &mgx::lpa_fused_state_t::launches, "mgx_lpa_step_kinds", host_kinds, cap, launches);
 }
 int mgx_lpa_bins(mgx_lpa_t p, int64_t* out) {
   MGX_TRY
@@ -3412,19 +3402,9 @@ int mgx_lpa_bins(mgx_lpa_t p, int64_t* out) {
   out[8] = f.overflowed;
   MGX_CATCH
 }
-int mgx_lpa_set_timing(mgx_lpa_t p, int on) {
-  MGX_TRY
-  auto [ctx, g] = enter(p);
-  if (!p->fused) p->fused.reset(new mgx::lpa_fused_state_t(g.num_nodes, g.num_edges, ctx));
-  p->fused->timing = on != 0;
-  MGX_CATCH
-}
+int mgx_lpa_set_timing(mgx_lpa_t p, int on) { return chain_set_timing(p, &mgx_lpa_s::fused, on); }
 int mgx_lpa_phase_ms(mgx_lpa_t p, double* out) {
-  MGX_TRY
-  MGX_REQUIRE(p && out, "NULL argument");
-  require_run(p->fused && p->fused->launches >= 0, "mgx_lpa_phase_ms");
-  for (int i = 0; i < 4; ++i) out[i] = p->fused->phase_ms[i];
-  MGX_CATCH
+  return chain_phase_ms(p, &mgx_lpa_s::fused, &mgx::lpa_fused_state_t::launches, &mgx::lpa_fused_state_t::phase_ms, "mgx_lpa_phase_ms", out);
 }
 int mgx_modularity(mgx_graph_t g, const int* d_labels, int symmetric, uint64_t* out) {
   MGX_TRY
@@ -3579,7 +3559,7 @@ int mgx_msbfs_level_kinds(mgx_msbfs_t p, int* host_kinds, int cap, int64_t* leve
   MGX_REQUIRE(p && levels && cap >= 0 && (host_kinds || cap == 0), "bad argument");
   require_run(p->fused && p->fused->launches >= 0, "mgx_msbfs_level_kinds");
   *levels = p->fused->levels;
-  const long long have = std::min<long long>(std::min<long long>(p->fused->levels, mgx::MSBFS_LOG_CAP), cap);
+  const long long have = std::min<long long>(std::min<long long>(p->fused->levels, mgx::CHAIN_LOG_CAP), cap);
   read_back(p, host_kinds, (const int*)p->fused->ctl.data()->log, (size_t)have);
   MGX_CATCH
 }
@@ -3592,19 +3572,9 @@ int mgx_msbfs_bins(mgx_msbfs_t p, int64_t* out) {
   out[10] = f.opts.short_max; out[11] = f.opts.wave_max; out[12] = f.opts.seg; out[13] = f.opts.pull_div;
   MGX_CATCH
 }
-int mgx_msbfs_set_timing(mgx_msbfs_t p, int on) {
-  MGX_TRY
-  auto [ctx, g] = enter(p);
-  if (!p->fused) p->fused.reset(new mgx::msbfs_fused_state_t(g.num_nodes, g.num_edges, ctx));
-  p->fused->timing = on != 0;
-  MGX_CATCH
-}
+int mgx_msbfs_set_timing(mgx_msbfs_t p, int on) { return chain_set_timing(p, &mgx_msbfs_s::fused, on); }
 int mgx_msbfs_phase_ms(mgx_msbfs_t p, double* out) {
-  MGX_TRY
-  MGX_REQUIRE(p && out, "NULL argument");
-  require_run(p->fused && p->fused->launches >= 0, "mgx_msbfs_phase_ms");
-  for (int i = 0; i < 4; ++i) out[i] = p->fused->phase_ms[i];
-  MGX_CATCH
+  return chain_phase_ms(p, &mgx_msbfs_s::fused, &mgx::msbfs_fused_state_t::launches, &mgx::msbfs_fused_state_t::phase_ms, "mgx_msbfs_phase_ms", out);
 }
 
 // ---- random walks and node2vec sampling --------------------------------------------
@@ -3896,13 +3866,7 @@ int mgx_louvain_bins(mgx_louvain_t p, int64_t* out) {
   out[4] = f.opts.short_max; out[5] = f.opts.wave_max; out[6] = f.opts.seg; out[7] = f.long_items;
   MGX_CATCH
 }
-int mgx_louvain_set_timing(mgx_louvain_t p, int on) {
-  MGX_TRY
-  auto [ctx, g] = enter(p);
-  if (!p->fused) p->fused.reset(new mgx::louvain_fused_state_t(g.num_nodes, g.num_edges, ctx));
-  p->fused->timing = on != 0;
-  MGX_CATCH
-}
+int mgx_louvain_set_timing(mgx_louvain_t p, int on) { return chain_set_timing(p, &mgx_louvain_s::fused, on); }
 int mgx_louvain_phase_ms(mgx_louvain_t p, double* out) {
   MGX_TRY
   MGX_REQUIRE(p && out, "NULL argument");

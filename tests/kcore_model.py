@@ -63,7 +63,7 @@ def check_against_enactor(st, est):
 MINI_MAX = 2048          # KCORE_MINI_MAX: entries of a front one workgroup peels on its own
 LONG_MIN = 32            # KCORE_LONG_MIN: rows of at least this many entries are long
 SEG = 256                # KCORE_SEG: entries of a (vertex, segment) item
-BATCH_MIN = 64           # KCORE_BATCH_MIN, KCORE_BATCH_MAX: launches per host wait, doubling
+BATCH_MIN = 64           # CHAIN_BATCH_MIN, CHAIN_BATCH_MAX (launch_chain.hpp): launches per host wait, doubling
 BATCH_MAX = 256
 # the codes of mini_amd.KcoreProblem.STEP_KINDS (kcore_kind_t)
 MIN, LIST, EXPAND, FILTER, IDLE, MINI = 1, 2, 3, 4, 5, 6

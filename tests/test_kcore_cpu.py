@@ -139,9 +139,9 @@ def test_model_rmat(oracle, scale, ef, seed):
 
 # ---- the launch plan ----
 def _header_constants():
-    """the constexpr ints of include/mgx/kcore_fused.hpp and wave.hpp by name, products of names and numbers evaluated"""
+    """the constexpr ints of include/mgx/kcore_fused.hpp, launch_chain.hpp and wave.hpp by name, products of names and numbers evaluated"""
     vals = {}
-    for name in ("wave.hpp", "kcore_fused.hpp"):
+    for name in ("wave.hpp", "launch_chain.hpp", "kcore_fused.hpp"):
         text = open(os.path.join(ROOT, "include", "mgx", name)).read()
         for m in re.finditer(r"constexpr int (\w+) = ([^;]+);", text):
             total = 1
@@ -161,7 +161,7 @@ def test_plan_constants_are_the_headers(built):
     assert c["KCORE_MINI_MAX"] == model.MINI_MAX == 2048
     assert c["KCORE_LONG_MIN"] == model.LONG_MIN == 32
     assert c["KCORE_SEG"] == model.SEG == 256
-    assert (c["KCORE_BATCH_MIN"], c["KCORE_BATCH_MAX"]) == (model.BATCH_MIN, model.BATCH_MAX) == (64, 256)
+    assert (c["CHAIN_BATCH_MIN"], c["CHAIN_BATCH_MAX"]) == (model.BATCH_MIN, model.BATCH_MAX) == (64, 256)
     # what the cases' sizes lean on: the stages flush at 128 short and 64 long rows, a scan covers 256 ids a wave
     assert c["KCORE_STAGE"] == 128 and c["WAVE"] == 64 and c["BLOCK"] == 256
     text = open(os.path.join(ROOT, "include", "mgx", "kcore_fused.hpp")).read()
