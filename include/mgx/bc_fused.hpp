@@ -40,6 +40,7 @@
 // No atomics, no grid barrier, no cooperative launch, no inline assembly.  A run waits for the host ONCE of its own, at the end.
 #pragma once
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <utility>
 #include <vector>
@@ -67,10 +68,10 @@ struct bc_opts_t {
   int chain = 1024;       // MGX_BC_CHAIN: a level of at most this many vertices is small (0: no chain)
   static bc_opts_t from_env() {
     bc_opts_t o;
-    if (const char* e = env("MGX_BC_LANE_MAX")) o.lane_max = std::max(atoi(e), 0);
-    if (const char* e = env("MGX_BC_HUGE_MIN")) o.huge_min = std::max(atoi(e), 1);
-    if (const char* e = env("MGX_BC_SEG")) o.seg = std::max(atoi(e), 1);
-    if (const char* e = env("MGX_BC_CHAIN")) o.chain = std::max(atoi(e), 0);
+    o.lane_max = env_int("MGX_BC_LANE_MAX", 0, INT_MAX, o.lane_max);
+    o.huge_min = env_int("MGX_BC_HUGE_MIN", 1, INT_MAX, o.huge_min);
+    o.seg = env_int("MGX_BC_SEG", 1, INT_MAX, o.seg);
+    o.chain = env_int("MGX_BC_CHAIN", 0, INT_MAX, o.chain);
     return o;
   }
   int row_class(int len) const { return len <= lane_max ? BC_LANE : (len >= huge_min ? BC_HUGE : BC_WAVE); }

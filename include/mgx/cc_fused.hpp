@@ -122,8 +122,7 @@ __global__ __launch_bounds__(BLOCK) void k_cc_sample(const int* comp, int n, uns
   u64 best = 0;                                              // (count << 32) | ~root: the largest count, then the smallest root
   for (int i = threadIdx.x; i < CC_SAMPLE_SLOTS; i += BLOCK)
     if (counts[i]) best = max(best, ((u64)counts[i] << 32) | (u32)~keys[i]);
-#pragma unroll
-  for (int d = WAVE / 2; d > 0; d >>= 1) best = max(best, (u64)__shfl_xor(best, d, WAVE));
+  best = wave_max(best);
   if (lane_id() == 0) best_of_wave[threadIdx.x / WAVE] = best;
   __syncthreads();
   if (threadIdx.x == 0) {

@@ -64,8 +64,7 @@ __device__ __forceinline__ bool color_uncoloured(const unsigned* bm, int u) { re
 
 // one wave: after a round's decisions, the largest colour any of its lanes gave (one atomic per wave, if any)
 __device__ __forceinline__ void color_note_max(int* max_colour, int mine) {
-#pragma unroll
-  for (int d = WAVE / 2; d > 0; d >>= 1) mine = max(mine, __shfl_xor(mine, d, WAVE));
+  mine = wave_max(mine);
   if (lane_id() == 0 && mine > 0 && __hip_atomic_load(max_colour, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < mine)
     atomicMax(max_colour, mine);
 }

@@ -133,4 +133,12 @@ inline const char* env(const char* name) {
   return (e && *e) ? e : nullptr;
 }
 
+// an integer switch: `fallback` when unset or empty, else its value clamped to [lo, hi] (no digits: 0, then clamped)
+inline int env_int(const char* name, int lo, int hi, int fallback) {
+  const char* e = env(name);
+  if (!e) return fallback;
+  const long long v = std::strtoll(e, nullptr, 10);
+  return (int)(v < lo ? lo : (v > hi ? hi : v));
+}
+
 }  // namespace mgx

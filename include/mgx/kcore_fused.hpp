@@ -370,8 +370,7 @@ __global__ __launch_bounds__(BLOCK) void k_kcore_step(kcore_step_args_t a, unsig
       if (lane == 0 && stranded) atomicAdd((unsigned long long*)&a.ctl->totals.stranded, (unsigned long long)stranded);
     }
     if (kind == KCORE_MIN) {                                 // one add a workgroup, if it would change anything
-#pragma unroll
-      for (int d = WAVE / 2; d > 0; d >>= 1) best = min(best, __shfl_xor(best, d, WAVE));
+      best = wave_min(best);
       if (lane == 0) block_best[threadIdx.x / WAVE] = best;
       __syncthreads();
       if (threadIdx.x == 0) {
@@ -398,8 +397,7 @@ __global__ __launch_bounds__(BLOCK) void k_kcore_step(kcore_step_args_t a, unsig
     const int beg = in ? a.ro[v] : 0;
     const int len = in ? a.ro[v + 1] - beg : 0;
     int longest = len;
-#pragma unroll
-    for (int d = WAVE / 2; d > 0; d >>= 1) longest = max(longest, __shfl_xor(longest, d, WAVE));
+    longest = wave_max(longest);
     for (int j = 0; j < longest; j += KCORE_UNROLL) kcore_take(a, next, beg + j, 1, beg + len, k, stage, fill);
   }
   wave_stage_flush(stage, fill, a.cand, &next->n_cand);

@@ -47,6 +47,7 @@
 // dropping removed entries from the adjacency at level boundaries.
 #pragma once
 #include <algorithm>
+#include <climits>
 #include <vector>
 
 #include "env.hpp"
@@ -72,8 +73,8 @@ struct ktruss_opts_t {
   int short_max = KTRUSS_SHORT_MAX_DEFAULT, seg = KTRUSS_SEG_DEFAULT;
   static ktruss_opts_t from_env() {
     ktruss_opts_t o;
-    if (const char* e = env("MGX_KTRUSS_SHORT_MAX")) o.short_max = (int)std::min<long long>(std::max<long long>(atoll(e), 0), 0x7fffffff);
-    if (const char* e = env("MGX_KTRUSS_SEG")) o.seg = std::max(atoi(e), 1);
+    o.short_max = env_int("MGX_KTRUSS_SHORT_MAX", 0, INT_MAX, o.short_max);
+    o.seg = env_int("MGX_KTRUSS_SEG", 1, INT_MAX, o.seg);
     return o;
   }
 };
@@ -276,8 +277,7 @@ __global__ __launch_bounds__(BLOCK) void k_ktruss_step(ktruss_step_args_t a, uns
     int best = 0x7fffffff;
     for (unsigned e = gtid; e < (unsigned)a.m; e += gthreads)
       if (a.state[e] == KTRUSS_ALIVE) best = min(best, max(a.sup[e], 0));
-#pragma unroll
-    for (int d = WAVE / 2; d > 0; d >>= 1) best = min(best, __shfl_xor(best, d, WAVE));
+    best = wave_min(best);
     if (lane == 0) block_best[threadIdx.x / WAVE] = best;
     __syncthreads();
     if (threadIdx.x == 0) {                                  // one add a workgroup, if it would change anything
@@ -358,8 +358,7 @@ __global__ __launch_bounds__(BLOCK) void k_ktruss_step(ktruss_step_args_t a, uns
       ktruss_rows(a, e, s, sl, l, ll);
     }
     int longest = sl;
-#pragma unroll
-    for (int d = WAVE / 2; d > 0; d >>= 1) longest = max(longest, __shfl_xor(longest, d, WAVE));
+    longest = wave_max(longest);
     for (int j = 0; j < longest; ++j) ktruss_entry(a, j < sl, e, s + j, l, ll, k, out, &next->app, stage, fill);
   }
   wave_stage_flush(stage, fill, out, &next->app);

@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <climits>
 
+#include "row_bodies.hpp"
 #include "runtime.hpp"
 #include "scan.hpp"
 #include "segsort.hpp"
@@ -40,22 +41,8 @@ struct lv_graph_t {
   int n;
 };
 
-struct lv_row_t {
-  int ob, olen, ib, ilen;
-  __device__ __forceinline__ int len() const { return olen + ilen; }
-};
-__device__ __forceinline__ lv_row_t lv_row(const lv_graph_t& g, bool valid, int v) {
-  lv_row_t r = {0, 0, 0, 0};
-  if (valid) {
-    r.ob = g.ro[v];
-    r.olen = g.ro[v + 1] - r.ob;
-    if (g.co) {
-      r.ib = g.co[v];
-      r.ilen = g.co[v + 1] - r.ib;
-    }
-  }
-  return r;
-}
+using lv_row_t = row_pair_t;
+__device__ __forceinline__ lv_row_t lv_row(const lv_graph_t& g, bool valid, int v) { return row_pair_of(g.ro, g.co, g.co != nullptr, valid, v); }
 // entry k of v's row: the neighbour, and its weight (0: a self-loop of level 0)
 __device__ __forceinline__ int lv_entry(const lv_graph_t& g, const lv_row_t& r, int v, int k, unsigned* x) {
   const int u = k < r.olen ? g.ci[r.ob + k] : g.ri[r.ib + (k - r.olen)];
@@ -105,13 +92,8 @@ __global__ __launch_bounds__(BLOCK) void k_lv_fill(lv_graph_t g, const int* __re
         const int u = lv_entry(g, r, v, j, &x);
         if (x) { keys[pos] = map[u]; vals[pos] = x; ++pos; }
       }
-    u64 todo = __ballot(len > LV_AGG_LANE_MAX);
-    while (todo) {
-      const int src = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
-      lv_row_t rr;
-      rr.ob = __shfl(r.ob, src, WAVE); rr.olen = __shfl(r.olen, src, WAVE);
-      rr.ib = __shfl(r.ib, src, WAVE); rr.ilen = __shfl(r.ilen, src, WAVE);
+    for_each_wave_row(len > LV_AGG_LANE_MAX, [&](int src) {
+      const lv_row_t rr = r.of_lane(src);
       const int vv = __shfl(v, src, WAVE);
       int p = __shfl(pos, src, WAVE);
       const int ll = rr.len();
@@ -123,7 +105,7 @@ __global__ __launch_bounds__(BLOCK) void k_lv_fill(lv_graph_t g, const int* __re
         if (x) { keys[p + rank_in_mask(m)] = map[u]; vals[p + rank_in_mask(m)] = x; }
         p += __popcll(m);
       }
-    }
+    });
   }
 }
 

@@ -56,6 +56,7 @@
 #include "launch_chain.hpp"
 #include "louvain_aggregate.hpp"
 #include "lpa_fused.hpp"
+#include "row_bodies.hpp"
 #include "runtime.hpp"
 #include "wave.hpp"
 #include "worklist.hpp"
@@ -78,20 +79,19 @@ constexpr long long LV_THR_MAX = 1ll << 62;
 
 enum lv_kind_t : int { LV_INIT = 0, LV_SETUP = 1, LV_EVAL = 2, LV_LONG_FILL = 3, LV_LONG_SCAN = 4, LV_APPLY = 5, LV_QNUM = 6, LV_DONE = 7 };
 enum : int { LV_T_SETUP = 0, LV_T_EVAL = 1, LV_T_LONG = 2, LV_T_APPLY = 3, LV_T_QNUM = 4, LV_T_AGG = 5 };
-enum : int { LV_B_NONE = 0, LV_B_SHORT = 1, LV_B_WAVE = 2, LV_B_LONG = 3 };
 
 struct lv_opts_t {
-  int short_max = LV_SHORT_MAX_DEFAULT, wave_max = LV_WAVE_MAX_DEFAULT, seg = LV_SEG_DEFAULT;
+  row_cuts_t cuts = {LV_SHORT_MAX_DEFAULT, LV_WAVE_MAX_DEFAULT, LV_SEG_DEFAULT};
   static lv_opts_t from_env() {
     lv_opts_t o;
-    if (const char* e = env("MGX_LOUVAIN_SHORT_MAX")) o.short_max = std::min(std::max(atoi(e), 0), LV_SHORT_CAP);
-    if (const char* e = env("MGX_LOUVAIN_WAVE_MAX")) o.wave_max = std::min(std::max(atoi(e), 0), LV_WAVE_CAP);
+    o.cuts.short_max = env_int("MGX_LOUVAIN_SHORT_MAX", 0, LV_SHORT_CAP, o.cuts.short_max);
+    o.cuts.wave_max = env_int("MGX_LOUVAIN_WAVE_MAX", 0, LV_WAVE_CAP, o.cuts.wave_max);
     if (const char* e = env("MGX_LOUVAIN_SEG")) {
       int s = LV_SEG_MIN;
       while (s < LV_SEG_CAP && s < atoi(e)) s *= 2;          // a power of two in [64, 1024]
-      o.seg = s;
+      o.cuts.seg = s;
     }
-    o.wave_max = std::max(o.wave_max, o.short_max);
+    o.cuts.wave_max = std::max(o.cuts.wave_max, o.cuts.short_max);
     return o;
   }
 };
@@ -138,24 +138,21 @@ struct lv_args_t {
   size_t N;
   long long item_cap;          // table_cap = item_cap x 2 x seg
   double tol;
-  int max_iter, trace_cap, short_max, wave_max, seg, timing;
+  int max_iter, trace_cap, timing;
+  row_cuts_t cuts;
   unsigned seed;
   __device__ __forceinline__ int* lab_of(int b) const { return vert + (size_t)(b & 1) * N; }
   __device__ __forceinline__ unsigned* sigma_of(int b) const { return (unsigned*)vert + (size_t)(2 + (b & 1)) * N; }
   __device__ __forceinline__ unsigned* k() const { return (unsigned*)vert + 4 * N; }
   __device__ __forceinline__ int* best() const { return vert + 5 * N; }
   __device__ __forceinline__ long long* base() const { return (long long*)(vert + 6 * N); }
-  __device__ __forceinline__ size_t table_cap() const { return (size_t)item_cap * 2 * (size_t)seg; }
+  __device__ __forceinline__ size_t table_cap() const { return (size_t)item_cap * 2 * (size_t)cuts.seg; }
   __device__ __forceinline__ int* tkeys() const { return tab; }
   __device__ __forceinline__ unsigned* tsum() const { return (unsigned*)tab + table_cap(); }
   __device__ __forceinline__ int* wlabel() const { return tab + 2 * table_cap(); }
   __device__ __forceinline__ long long* wscore() const { return (long long*)(tab + 2 * table_cap() + 2 * (size_t)((item_cap + 1) / 2)); }
   __device__ __forceinline__ int2* items() const { return (int2*)(wscore() + item_cap); }
 };
-
-__device__ __forceinline__ int lv_body_of(const lv_args_t& a, int len) {
-  return len == 0 ? LV_B_NONE : (len <= a.short_max ? LV_B_SHORT : (len <= a.wave_max ? LV_B_WAVE : LV_B_LONG));
-}
 
 // a candidate: its score and its label.  Wider than one 64-bit word, so the order is a function
 struct lv_best_t { long long score; int label; };
@@ -275,15 +272,10 @@ __device__ __forceinline__ int lv_clock_of(int kind) {
   if (kind == LV_LONG_FILL || kind == LV_LONG_SCAN) return LV_T_LONG;
   return kind == LV_APPLY ? LV_T_APPLY : LV_T_QNUM;
 }
-__device__ __forceinline__ u64 lv_wave_sum64(u64 x) {
-#pragma unroll
-  for (int d = WAVE / 2; d > 0; d >>= 1) x += (u64)__shfl_xor((long long)x, d, WAVE);
-  return x;
-}
 // two sums of a workgroup, one atomic each (all threads call)
 __device__ __forceinline__ void lv_block_add2(u64 x, u64 y, u64* px, u64* py, lv_lds_t& s) {
-  x = lv_wave_sum64(x);
-  y = lv_wave_sum64(y);
+  x = wave_sum(x);
+  y = wave_sum(y);
   if (lane_id() == 0) { s.red[0][threadIdx.x / WAVE] = x; s.red[1][threadIdx.x / WAVE] = y; }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -362,7 +354,7 @@ __global__ __launch_bounds__(BLOCK) void k_louvain_step(lv_args_t a, unsigned la
   unsigned* const sig_o = a.sigma_of(cur ^ 1);
 
   if (kind == LV_SETUP) {
-    long long bins[4] = {0, 0, 0, 0};
+    row_bins_t bins;
     u64 s_in = 0, s_sq = 0, wsum = 0;
     for (unsigned b0 = (unsigned)wave * WAVE; b0 < (unsigned)n; b0 += (unsigned)waves * WAVE) {
       const bool in = b0 + lane < (unsigned)n;
@@ -377,13 +369,8 @@ __global__ __launch_bounds__(BLOCK) void k_louvain_step(lv_args_t a, unsigned la
           kv += x;
           self += u == v ? x : 0u;
         }
-      u64 todo = __ballot(len > LV_QNUM_LANE_MAX);
-      while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        lv_row_t rr;
-        rr.ob = __shfl(r.ob, src, WAVE); rr.olen = __shfl(r.olen, src, WAVE);
-        rr.ib = __shfl(r.ib, src, WAVE); rr.ilen = __shfl(r.ilen, src, WAVE);
+      for_each_wave_row(len > LV_QNUM_LANE_MAX, [&](int src) {
+        const lv_row_t rr = r.of_lane(src);
         const int vv = __shfl(v, src, WAVE);
         u64 c = 0, sf = 0;
         for (int j = lane; j < rr.len(); j += WAVE) {
@@ -392,31 +379,28 @@ __global__ __launch_bounds__(BLOCK) void k_louvain_step(lv_args_t a, unsigned la
           c += x;
           sf += u == vv ? x : 0u;
         }
-        c = lv_wave_sum64(c);
-        sf = lv_wave_sum64(sf);
+        c = wave_sum(c);
+        sf = wave_sum(sf);
         if (lane == src) { kv = c; self = sf; }
-      }
-      const int body = in ? lv_body_of(a, len) : -1;
+      });
+      const int body = in ? a.cuts.body_of(len) : -1;
       if (in) {
         a.lab_of(0)[v] = v;
         a.k()[v] = (unsigned)kv;
         a.sigma_of(0)[v] = (unsigned)kv;
       }
-      if (body == LV_B_LONG) {
-        const unsigned long long room = (unsigned long long)((len + a.seg - 1) / a.seg) * (unsigned long long)(2 * a.seg);
+      if (body == ROW_LONG) {
+        const unsigned long long room = (unsigned long long)a.cuts.segments_of(len) * (unsigned long long)(2 * a.cuts.seg);
         a.base()[v] = (long long)atomicAdd(&a.ctl->totals.cursor, room);
       }
-      if (__ballot(body == LV_B_LONG)) wave_append_segments(body == LV_B_LONG, v, len, a.seg, a.items(), &a.ctl->totals.n_items);
-#pragma unroll
-      for (int b = 0; b < 4; ++b) bins[b] += __popcll(__ballot(body == b));
+      if (__ballot(body == ROW_LONG)) wave_append_segments(body == ROW_LONG, v, len, a.cuts.seg, a.items(), &a.ctl->totals.n_items);
+      bins.count(body);
       s_in += self;
       s_sq += kv * kv;
       wsum += kv;
     }
-    if (lane == 0)
-      for (int b = 0; b < 4; ++b)
-        if (bins[b]) atomicAdd((u64*)&a.ctl->totals.bins[b], (u64)bins[b]);
-    wsum = lv_wave_sum64(wsum);
+    bins.add_to(a.ctl->totals.bins);
+    wsum = wave_sum(wsum);
     if (lane == 0 && wsum) atomicAdd(&a.ctl->totals.w, wsum);
     lv_block_add2(s_in, s_sq, &next->s_in, &next->s_sq, lds);
     return;
@@ -430,8 +414,8 @@ __global__ __launch_bounds__(BLOCK) void k_louvain_step(lv_args_t a, unsigned la
       const int len = r.len();
       const long long tb = a.base()[v];
       const unsigned slots = 2u * (unsigned)len;
-      const int j1 = min(len, (item.y + 1) * a.seg);
-      for (int j = item.y * a.seg + lane; j < j1; j += WAVE) {
+      const int j1 = min(len, (item.y + 1) * a.cuts.seg);
+      for (int j = item.y * a.cuts.seg + lane; j < j1; j += WAVE) {
         unsigned x;
         const int u = lv_entry(a.g, r, v, j, &x);
         if (u == v || !x) continue;
@@ -457,11 +441,11 @@ __global__ __launch_bounds__(BLOCK) void k_louvain_step(lv_args_t a, unsigned la
       const int v = item.x;
       const lv_row_t r = lv_row(a.g, true, v);
       const long long tb = a.base()[v];
-      const long long s1 = min(2ll * r.len(), 2ll * (item.y + 1) * a.seg);
+      const long long s1 = min(2ll * r.len(), 2ll * (item.y + 1) * a.cuts.seg);
       const int c0 = lab_c[v];
       const unsigned kv = a.k()[v];
       lv_best_t best = {lv_score(0, W, sig_c[c0], true, kv), c0};
-      for (long long s = 2ll * item.y * a.seg + lane; s < s1; s += WAVE) {
+      for (long long s = 2ll * item.y * a.cuts.seg + lane; s < s1; s += WAVE) {
         const int c = a.tkeys()[tb + s];
         if (c != LV_EMPTY) {
           const lv_best_t o = {lv_score(a.tsum()[tb + s], W, sig_c[c], c == c0, kv), c};
@@ -472,7 +456,7 @@ __global__ __launch_bounds__(BLOCK) void k_louvain_step(lv_args_t a, unsigned la
       }
       best = lv_wave_best(best, c0, a.seed);
       if (lane == 0) {
-        const long long slot = tb / (2 * a.seg) + item.y;
+        const long long slot = tb / (2 * a.cuts.seg) + item.y;
         a.wscore()[slot] = best.score;
         a.wlabel()[slot] = best.label;
       }
@@ -487,22 +471,16 @@ __global__ __launch_bounds__(BLOCK) void k_louvain_step(lv_args_t a, unsigned la
       const bool in = b0 + lane < (unsigned)n;
       const int v = in ? (int)(b0 + lane) : 0;
       const lv_row_t r = lv_row(a.g, in, v);
-      const int body = in ? lv_body_of(a, r.len()) : LV_B_NONE;
+      const int body = in ? a.cuts.body_of(r.len()) : ROW_NONE;
       const int c0 = in ? lab_c[v] : 0;
       const unsigned kv = in ? a.k()[v] : 0u;
       int w = c0;
-      if (body == LV_B_SHORT) w = lv_short_best(a, r, v, c0, kv, W, lab_c, sig_c);
-      u64 todo = __ballot(body == LV_B_WAVE);
-      while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        lv_row_t rr;
-        rr.ob = __shfl(r.ob, src, WAVE); rr.olen = __shfl(r.olen, src, WAVE);
-        rr.ib = __shfl(r.ib, src, WAVE); rr.ilen = __shfl(r.ilen, src, WAVE);
-        const int ww = lv_wave_row_best(a, rr, __shfl(v, src, WAVE), __shfl(c0, src, WAVE), (unsigned)__shfl((int)kv, src, WAVE), W, lab_c,
+      if (body == ROW_LANE) w = lv_short_best(a, r, v, c0, kv, W, lab_c, sig_c);
+      for_each_wave_row(body == ROW_WAVE, [&](int src) {
+        const int ww = lv_wave_row_best(a, r.of_lane(src), __shfl(v, src, WAVE), __shfl(c0, src, WAVE), (unsigned)__shfl((int)kv, src, WAVE), W, lab_c,
                                         sig_c, keys, sums);
         if (lane == src) w = ww;
-      }
+      });
       if (in) {
         a.best()[v] = w;
         sig_o[v] = sig_c[v];
@@ -517,19 +495,16 @@ __global__ __launch_bounds__(BLOCK) void k_louvain_step(lv_args_t a, unsigned la
       const bool in = b0 + lane < (unsigned)n;
       const int v = in ? (int)(b0 + lane) : 0;
       const lv_row_t r = lv_row(a.g, in, v);
-      const int body = in ? lv_body_of(a, r.len()) : LV_B_NONE;
+      const int body = in ? a.cuts.body_of(r.len()) : ROW_NONE;
       const int c0 = in ? lab_c[v] : 0;
       const unsigned kv = in ? a.k()[v] : 0u;
       int w = in ? a.best()[v] : 0;
-      u64 todo = __ballot(body == LV_B_LONG);                  // a long row's best is the best of its items' slots
-      while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
+      for_each_wave_row(body == ROW_LONG, [&](int src) {      // a long row's best is the best of its items' slots
         const int vv = __shfl(v, src, WAVE);
         const int cc = __shfl(c0, src, WAVE);
         const unsigned kk = (unsigned)__shfl((int)kv, src, WAVE);
-        const int segs = (__shfl(r.len(), src, WAVE) + a.seg - 1) / a.seg;
-        const long long slot0 = a.base()[vv] / (2 * a.seg);
+        const int segs = a.cuts.segments_of(__shfl(r.len(), src, WAVE));
+        const long long slot0 = a.base()[vv] / (2 * a.cuts.seg);
         lv_best_t best = {lv_score(0, W, sig_c[cc], true, kk), cc};
         for (int s = lane; s < segs; s += WAVE) {
           const lv_best_t o = {a.wscore()[slot0 + s], a.wlabel()[slot0 + s]};
@@ -537,7 +512,7 @@ __global__ __launch_bounds__(BLOCK) void k_louvain_step(lv_args_t a, unsigned la
         }
         best = lv_wave_best(best, cc, a.seed);
         if (lane == src) w = best.label;
-      }
+      });
       const unsigned kw = color_key(w, a.seed), kc = color_key(c0, a.seed);
       const bool moves = in && w != c0 && ((t & 1) ? kw > kc : kw < kc);
       if (in) lab_o[v] = moves ? w : c0;
@@ -559,28 +534,23 @@ __global__ __launch_bounds__(BLOCK) void k_louvain_step(lv_args_t a, unsigned la
       const int v = in ? (int)(b0 + lane) : 0;
       const lv_row_t r = lv_row(a.g, in, v);
       const int len = r.len();
-      const int body = in ? lv_body_of(a, len) : LV_B_NONE;
+      const int body = in ? a.cuts.body_of(len) : ROW_NONE;
       const int l = in ? lab_o[v] : 0;
-      if (body != LV_B_LONG && len <= LV_QNUM_LANE_MAX)
+      if (body != ROW_LONG && len <= LV_QNUM_LANE_MAX)
         for (int j = 0; j < len; ++j) {
           unsigned x;
           const int u = lv_entry(a.g, r, v, j, &x);
           s_in += lab_o[u] == l ? x : 0u;
         }
-      u64 todo = __ballot(body != LV_B_LONG && len > LV_QNUM_LANE_MAX);
-      while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        lv_row_t rr;
-        rr.ob = __shfl(r.ob, src, WAVE); rr.olen = __shfl(r.olen, src, WAVE);
-        rr.ib = __shfl(r.ib, src, WAVE); rr.ilen = __shfl(r.ilen, src, WAVE);
+      for_each_wave_row(body != ROW_LONG && len > LV_QNUM_LANE_MAX, [&](int src) {
+        const lv_row_t rr = r.of_lane(src);
         const int vv = __shfl(v, src, WAVE), ll = __shfl(l, src, WAVE);
         for (int j = lane; j < rr.len(); j += WAVE) {
           unsigned x;
           const int u = lv_entry(a.g, rr, vv, j, &x);
           s_in += lab_o[u] == ll ? x : 0u;
         }
-      }
+      });
       if (in) {
         const u64 s = sig_o[v];
         s_sq += s * s;
@@ -591,8 +561,8 @@ __global__ __launch_bounds__(BLOCK) void k_louvain_step(lv_args_t a, unsigned la
       const int v = item.x;
       const lv_row_t r = lv_row(a.g, true, v);
       const int l = lab_o[v];
-      const int j1 = min(r.len(), (item.y + 1) * a.seg);
-      for (int j = item.y * a.seg + lane; j < j1; j += WAVE) {
+      const int j1 = min(r.len(), (item.y + 1) * a.cuts.seg);
+      for (int j = item.y * a.cuts.seg + lane; j < j1; j += WAVE) {
         unsigned x;
         const int u = lv_entry(a.g, r, v, j, &x);
         s_in += lab_o[u] == l ? x : 0u;
@@ -652,9 +622,9 @@ struct louvain_fused_state_t {
     final_lab = mem_t<int>(N, ctx);
     maps = mem_t<int>(2 * N, ctx);
     // rows of more than wave_max entries: an item per seg entries and one more per row; a table of 2 x seg slots per item
-    const long long long_cap = std::min<long long>((long long)N, E / (opts.wave_max + 1) + 1);
-    item_cap = E / opts.seg + long_cap + 1;
-    table_cap = item_cap * 2 * opts.seg;
+    const long long long_cap = std::min<long long>((long long)N, E / (opts.cuts.wave_max + 1) + 1);
+    item_cap = E / opts.cuts.seg + long_cap + 1;
+    table_cap = item_cap * 2 * opts.cuts.seg;
     tab = mem_t<int>(2 * (size_t)table_cap + 2 * (size_t)((item_cap + 1) / 2) + 4 * (size_t)item_cap, ctx);
     for (int i = 0; i < 2; ++i) {
       cro[i] = mem_t<int>(N + 1, ctx);
@@ -699,7 +669,7 @@ struct louvain_fused_state_t {
     lv_args_t a;
     a.vert = vert.data(); a.tab = tab.data(); a.trace = trace.data(); a.ctl = ctl.data();
     a.N = N; a.item_cap = item_cap; a.tol = tol; a.max_iter = max_iter; a.trace_cap = trace_cap;
-    a.short_max = opts.short_max; a.wave_max = opts.wave_max; a.seg = opts.seg; a.timing = timing ? 1 : 0; a.seed = seed;
+    a.cuts = opts.cuts; a.timing = timing ? 1 : 0; a.seed = seed;
     lv_graph_t g = {ro, ci, nullptr, symmetric ? nullptr : co, symmetric ? nullptr : ri, n};
     long long entries = symmetric ? m : 2 * m, total_launches = 0, iterations = 0;
     unsigned long long W = 0, s_in = 0, s_sq = 0;

@@ -45,12 +45,14 @@
 // Not built: weighted votes, Louvain and aggregation, labels renamed to a member, more than one device.
 #pragma once
 #include <algorithm>
+#include <climits>
 #include <vector>
 
 #include "cc_fused.hpp"
 #include "color_hash.hpp"
 #include "env.hpp"
 #include "launch_chain.hpp"
+#include "row_bodies.hpp"
 #include "runtime.hpp"
 #include "wave.hpp"
 #include "worklist.hpp"
@@ -78,20 +80,20 @@ enum lpa_kind_t : int {
 };
 enum : int { LPA_SYNC = 0, LPA_LAZY = 1 };
 enum : int { LPA_T_SETUP = 0, LPA_T_EVAL = 1, LPA_T_LONG = 2, LPA_T_APPLY = 3 };
-enum : int { LPA_B_NONE = 0, LPA_B_SHORT = 1, LPA_B_WAVE = 2, LPA_B_LONG = 3 };
 
 struct lpa_opts_t {
-  int short_max = LPA_SHORT_MAX_DEFAULT, wave_max = LPA_WAVE_MAX_DEFAULT, table = LPA_TABLE_DEFAULT, list_div = LPA_LIST_DIV_DEFAULT;
+  row_cuts_t cuts = {LPA_SHORT_MAX_DEFAULT, LPA_WAVE_MAX_DEFAULT, LPA_SEG};      // (wave_max as read: the kernel's is raised to short_max)
+  int table = LPA_TABLE_DEFAULT, list_div = LPA_LIST_DIV_DEFAULT;
   static lpa_opts_t from_env() {
     lpa_opts_t o;
-    if (const char* e = env("MGX_LPA_SHORT_MAX")) o.short_max = std::min(std::max(atoi(e), 0), LPA_SHORT_CAP);
-    if (const char* e = env("MGX_LPA_WAVE_MAX")) o.wave_max = std::min(std::max(atoi(e), 0), LPA_WAVE_CAP);
+    o.cuts.short_max = env_int("MGX_LPA_SHORT_MAX", 0, LPA_SHORT_CAP, o.cuts.short_max);
+    o.cuts.wave_max = env_int("MGX_LPA_WAVE_MAX", 0, LPA_WAVE_CAP, o.cuts.wave_max);
     if (const char* e = env("MGX_LPA_TABLE")) {
       int t = LPA_TABLE_MIN;
       while (t < LPA_TABLE_CAP && t < atoi(e)) t *= 2;      // a power of two in [32, 2048]
       o.table = t;
     }
-    if (const char* e = env("MGX_LPA_LIST_DIV")) o.list_div = std::max(atoi(e), 0);
+    o.list_div = env_int("MGX_LPA_LIST_DIV", 0, INT_MAX, o.list_div);
     return o;
   }
 };
@@ -135,7 +137,8 @@ struct lpa_step_args_t {
   lpa_control_t* ctl;
   int n, symmetric, mode, max_iter, trace_cap, long_cap, item_cap;
   unsigned seed;
-  int short_max, wave_max, table, list_div, timing;
+  row_cuts_t cuts;  // (seg: LPA_SEG; the kernel uses the constant)
+  int table, list_div, timing;
   __device__ __forceinline__ int* part(int k) const { return vert + (size_t)k * (size_t)max(n, 1); }
   __device__ __forceinline__ int* lab() const { return vert; }
   __device__ __forceinline__ int* want() const { return part(1); }
@@ -145,27 +148,10 @@ struct lpa_step_args_t {
 };
 
 // a vertex's voters: its out-row, and behind it its in-row when the graph is not symmetric
-struct lpa_row_t {
-  int ob, olen, ib, ilen;
-  __device__ __forceinline__ int len() const { return olen + ilen; }
-};
-__device__ __forceinline__ lpa_row_t lpa_row(const lpa_step_args_t& a, bool valid, int v) {
-  lpa_row_t r = {0, 0, 0, 0};
-  if (valid) {
-    r.ob = a.ro[v];
-    r.olen = a.ro[v + 1] - r.ob;
-    if (!a.symmetric) {
-      r.ib = a.co[v];
-      r.ilen = a.co[v + 1] - r.ib;
-    }
-  }
-  return r;
-}
+using lpa_row_t = row_pair_t;
+__device__ __forceinline__ lpa_row_t lpa_row(const lpa_step_args_t& a, bool valid, int v) { return row_pair_of(a.ro, a.co, !a.symmetric, valid, v); }
 __device__ __forceinline__ int lpa_entry(const lpa_step_args_t& a, const lpa_row_t& r, int k) {
   return k < r.olen ? a.ci[r.ob + k] : a.ri[r.ib + (k - r.olen)];
-}
-__device__ __forceinline__ int lpa_body_of(const lpa_step_args_t& a, int len) {
-  return len == 0 ? LPA_B_NONE : (len <= a.short_max ? LPA_B_SHORT : (len <= a.wave_max ? LPA_B_WAVE : LPA_B_LONG));
 }
 
 // the order of the candidates: count, then being the current label, then the smaller label -- larger is better; 0: no votes
@@ -173,11 +159,6 @@ __device__ __forceinline__ u64 lpa_key(int count, int label, int cur) {
   return ((u64)(unsigned)count << 33) | ((u64)(label == cur ? 1u : 0u) << 32) | (u64)(0xffffffffu - (unsigned)label);
 }
 __device__ __forceinline__ int lpa_winner(u64 best, int cur) { return best == 0 ? cur : (int)(0xffffffffu - (unsigned)(best & 0xffffffffull)); }
-__device__ __forceinline__ u64 lpa_wave_max(u64 x) {
-#pragma unroll
-  for (int d = WAVE / 2; d > 0; d >>= 1) x = max(x, (u64)__shfl_xor((long long)x, d, WAVE));
-  return x;
-}
 
 // one vote for `label` into the table of `slots` slots (a power of two); false: every slot holds another label
 __device__ __forceinline__ bool lpa_insert(int* keys, int* counts, int slots, int label, bool* fresh) {
@@ -237,7 +218,7 @@ __device__ __forceinline__ int lpa_wave_want(const lpa_step_args_t& a, const lpa
   for (int s = lane; s < slots; s += WAVE)
     if (keys[s] != LPA_EMPTY) best = max(best, lpa_key(counts[s], keys[s], cur));
   wave_lds_fence();                                          // (the table is cleared again by the next row)
-  return lpa_winner(lpa_wave_max(best), cur);
+  return lpa_winner(wave_max(best), cur);
 }
 
 // what the kernel keeps in LDS: the waves' tables or the workgroup's (never both in one launch), the waves' list stages
@@ -279,7 +260,7 @@ __device__ __forceinline__ int lpa_block_want(const lpa_step_args_t& a, const lp
       if (!failed)
         for (int i = threadIdx.x; i < slots; i += BLOCK)
           if (s.keys[i] != LPA_EMPTY) mine = max(mine, lpa_key(s.counts[i], s.keys[i], cur));
-      mine = lpa_wave_max(mine);
+      mine = wave_max(mine);
       if (lane_id() == 0) s.best[wave] = mine;
       __syncthreads();
 #pragma unroll
@@ -307,12 +288,6 @@ struct lpa_list_t {
   __device__ __forceinline__ void push(bool take, int v) { wave_stage_push<LPA_STAGE>(take, v, stage, fill, out, counter); }
   __device__ __forceinline__ void flush() { wave_stage_flush(stage, fill, out, counter); }
 };
-
-// a mover's long rows as (vertex, segment) items; all lanes call.  Rare, and not inlined: the scan inside it would cost APPLY's loop
-// scalar registers it does not have
-__device__ __noinline__ void lpa_append_items(bool keep, int v, int len, int2* items, int* counter) {
-  wave_append_segments(keep, v, len, LPA_SEG, items, counter);
-}
 
 __device__ __forceinline__ bool lpa_is_dense(int n_act, int n, int list_div) { return !(list_div > 0 && n_act <= n / list_div); }
 __device__ __forceinline__ int lpa_clock_of(int kind) {
@@ -409,7 +384,7 @@ __global__ __launch_bounds__(BLOCK) void k_lpa_step(lpa_step_args_t a, unsigned 
   if (kind == LPA_SETUP) {
     list.out = a.list_of(0);
     list.counter = &a.ctl->totals.n_list[0];
-    long long bins[4] = {0, 0, 0, 0};
+    row_bins_t bins;
     for (unsigned base = (unsigned)wave * WAVE; base < (unsigned)a.n; base += (unsigned)waves * WAVE) {
       const bool in = base + lane < (unsigned)a.n;
       const int v = (int)(base + lane);
@@ -418,15 +393,11 @@ __global__ __launch_bounds__(BLOCK) void k_lpa_step(lpa_step_args_t a, unsigned 
       bool votes = false;
       for (int k = 0; k < len && !votes; ++k) votes = lpa_entry(a, r, k) != v;
       if (in) { a.lab()[v] = v; a.want()[v] = v; a.stamp()[v] = 0; }
-      const int body = lpa_body_of(a, len);
-#pragma unroll
-      for (int b = 0; b < 4; ++b) bins[b] += __popcll(__ballot(in && body == b));
+      bins.count(in ? a.cuts.body_of(len) : -1);
       list.push(in && votes, v);
     }
     list.flush();
-    if (lane == 0)
-      for (int b = 0; b < 4; ++b)
-        if (bins[b]) atomicAdd((u64*)&a.ctl->totals.bins[b], (u64)bins[b]);
+    bins.add_to(a.ctl->totals.bins);
     return;
   }
 
@@ -465,22 +436,16 @@ __global__ __launch_bounds__(BLOCK) void k_lpa_step(lpa_step_args_t a, unsigned 
       const bool in = base + lane < count;
       const int v = in ? (dense ? (int)(base + lane) : act[base + lane]) : 0;
       const lpa_row_t r = lpa_row(a, in, v);
-      const int body = in ? lpa_body_of(a, r.len()) : LPA_B_NONE;
+      const int body = in ? a.cuts.body_of(r.len()) : ROW_NONE;
       const int cur = in ? a.lab()[v] : 0;
       int w = cur;
-      if (body == LPA_B_SHORT) w = lpa_short_want(a, r, v, cur);
-      u64 todo = __ballot(body == LPA_B_WAVE);
-      while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        lpa_row_t rr;
-        rr.ob = __shfl(r.ob, src, WAVE); rr.olen = __shfl(r.olen, src, WAVE);
-        rr.ib = __shfl(r.ib, src, WAVE); rr.ilen = __shfl(r.ilen, src, WAVE);
-        const int ww = lpa_wave_want(a, rr, __shfl(v, src, WAVE), __shfl(cur, src, WAVE), keys, counts);
+      if (body == ROW_LANE) w = lpa_short_want(a, r, v, cur);
+      for_each_wave_row(body == ROW_WAVE, [&](int src) {
+        const int ww = lpa_wave_want(a, r.of_lane(src), __shfl(v, src, WAVE), __shfl(cur, src, WAVE), keys, counts);
         if (lane == src) w = ww;
-      }
-      list.push(body == LPA_B_LONG, v);
-      if (in && body != LPA_B_LONG) {
+      });
+      list.push(body == ROW_LONG, v);
+      if (in && body != ROW_LONG) {
         a.want()[v] = w;
         unstable += w != cur ? 1 : 0;
       }
@@ -512,16 +477,14 @@ __global__ __launch_bounds__(BLOCK) void k_lpa_step(lpa_step_args_t a, unsigned 
       const lpa_row_t r = lpa_row(a, moves, v);
       const int len = r.len();
       const int mine = len <= LPA_APPLY_LANE_MAX ? len : 0;
-      int longest = mine;
-#pragma unroll
-      for (int d = WAVE / 2; d > 0; d >>= 1) longest = max(longest, __shfl_xor(longest, d, WAVE));
+      const int longest = wave_max(mine);
       for (int k = 0; k < longest; ++k) {
         const int u = k < mine ? lpa_entry(a, r, k) : v;
         bool take = u != v && a.stamp()[u] != tag;
         if (take) take = atomicExch(a.stamp() + u, tag) != tag;
         list.push(take, u);
       }
-      if (__ballot(len > LPA_APPLY_LANE_MAX)) lpa_append_items(len > LPA_APPLY_LANE_MAX, v, len, a.items, &next->n_items);      // (the longer ones: MARK's)
+      if (__ballot(len > LPA_APPLY_LANE_MAX)) wave_append_segments_outlined(len > LPA_APPLY_LANE_MAX, v, len, LPA_SEG, a.items, &next->n_items);      // (the longer ones: MARK's)
     }
     list.flush();
     changed = wave_sum(changed);
@@ -612,7 +575,7 @@ struct lpa_fused_state_t {
   lpa_fused_state_t(int n_, long long m_, context_t& ctx) : n(n_), m(m_), opts(lpa_opts_t::from_env()), label_stats(n_, ctx) {
     const size_t N = (size_t)std::max(n, 1);
     // rows of more than wave_max entries: out- and in-entries together are 2 m at most
-    long_cap = (int)std::min<long long>((long long)N, 2 * m / (std::max(opts.wave_max, opts.short_max) + 1) + 1);
+    long_cap = (int)std::min<long long>((long long)N, 2 * m / (std::max(opts.cuts.wave_max, opts.cuts.short_max) + 1) + 1);
     vert = mem_t<int>(5 * N + (size_t)long_cap, ctx);
     // a mover's rows of more than LPA_APPLY_LANE_MAX entries, once an iteration: an item per LPA_SEG entries and one per row
     item_cap = (int)(std::min<long long>((long long)N, 2 * m / (LPA_APPLY_LANE_MAX + 1) + 1) + 2 * m / LPA_SEG + 1);
@@ -644,7 +607,9 @@ struct lpa_fused_state_t {
     a.trace = trace.data(); a.ctl = ctl.data();
     a.n = n; a.symmetric = symmetric ? 1 : 0; a.mode = mode; a.max_iter = max_iter; a.trace_cap = trace_cap; a.long_cap = long_cap; a.item_cap = item_cap;
     a.seed = seed;
-    a.short_max = opts.short_max; a.wave_max = std::max(opts.wave_max, opts.short_max); a.table = opts.table; a.list_div = opts.list_div;
+    a.cuts = opts.cuts;
+    a.cuts.wave_max = std::max(opts.cuts.wave_max, opts.cuts.short_max);
+    a.table = opts.table; a.list_div = opts.list_div;
     a.timing = timing ? 1 : 0;
     const int blocks = grid_for(n, BLOCK, std::max(ctx.num_cus, 1) * 4);
     long long waits = 0;
@@ -675,12 +640,6 @@ struct lpa_fused_state_t {
 // W = all votes: exact in 64 bits (W <= 2 m < 2^32).  acc: [0] S_in, [1] S_sq, [2] W, [3] labels outside [0, n).
 enum : int { MOD_S_IN = 0, MOD_S_SQ = 1, MOD_W = 2, MOD_BAD = 3 };
 
-__device__ __forceinline__ u64 mod_wave_sum(u64 x) {
-#pragma unroll
-  for (int d = WAVE / 2; d > 0; d >>= 1) x += (u64)__shfl_xor((long long)x, d, WAVE);
-  return x;
-}
-
 // over the vertices, a wave over 64 consecutive ones: a lane counts its rows of at most 32 entries, the wave the longer ones
 __global__ __launch_bounds__(BLOCK) void k_mod_votes(const int* __restrict__ ro, const int* __restrict__ ci, const int* __restrict__ co,
                                                      const int* __restrict__ ri, const int* __restrict__ lab, int n, int symmetric,
@@ -707,10 +666,7 @@ __global__ __launch_bounds__(BLOCK) void k_mod_votes(const int* __restrict__ ro,
           votes += u != v ? 1 : 0;
           equal += (side == 0 && u != v && lab[u] == l) ? 1 : 0;
         }
-      u64 todo = __ballot(len > 32);
-      while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
+      for_each_wave_row(len > 32, [&](int src) {
         const int vv = __shfl(v, src, WAVE), b = __shfl(beg, src, WAVE), e = b + __shfl(len, src, WAVE), ll = __shfl(l, src, WAVE);
         u64 c = 0, q = 0;
         for (int k = b + lane; k < e; k += WAVE) {
@@ -718,18 +674,18 @@ __global__ __launch_bounds__(BLOCK) void k_mod_votes(const int* __restrict__ ro,
           c += u != vv ? 1 : 0;
           q += (side == 0 && u != vv && lab[u] == ll) ? 1 : 0;
         }
-        c = mod_wave_sum(c);
-        q = mod_wave_sum(q);
+        c = wave_sum(c);
+        q = wave_sum(q);
         if (lane == src) { votes += c; equal += q; }
-      }
+      });
     }
     if (ok && votes) atomicAdd(tot + l, votes);
     w += votes;
     s_in += symmetric ? equal : 2 * equal;                   // (not symmetric: an entry is a vote at both of its ends)
   }
-  s_in = mod_wave_sum(s_in);
-  w = mod_wave_sum(w);
-  bad = mod_wave_sum(bad);
+  s_in = wave_sum(s_in);
+  w = wave_sum(w);
+  bad = wave_sum(bad);
   if (lane == 0) {
     if (s_in) atomicAdd(acc + MOD_S_IN, s_in);
     if (w) atomicAdd(acc + MOD_W, w);
@@ -741,7 +697,7 @@ __global__ __launch_bounds__(BLOCK) void k_mod_squares(const u64* __restrict__ t
   const unsigned gthreads = gridDim.x * (unsigned)BLOCK;
   u64 s = 0;
   for (unsigned c = gtid; c < (unsigned)n; c += gthreads) s += tot[c] * tot[c];
-  s = mod_wave_sum(s);
+  s = wave_sum(s);
   if (lane_id() == 0 && s) atomicAdd(acc + MOD_S_SQ, s);
 }
 

@@ -57,6 +57,7 @@
 
 #include "env.hpp"
 #include "launch_chain.hpp"
+#include "row_bodies.hpp"
 #include "runtime.hpp"
 #include "wave.hpp"
 #include "worklist.hpp"
@@ -81,14 +82,15 @@ enum : int { MSBFS_T_PUSH = 0, MSBFS_T_PULL = 1, MSBFS_T_LONG = 2, MSBFS_T_FINAL
 enum : int { MSBFS_BINS = 10 };
 
 struct msbfs_opts_t {
-  int short_max = MSBFS_SHORT_MAX_DEFAULT, wave_max = MSBFS_WAVE_MAX_DEFAULT, seg = MSBFS_SEG_DEFAULT, pull_div = MSBFS_PULL_DIV_DEFAULT;
+  row_cuts_t cuts = {MSBFS_SHORT_MAX_DEFAULT, MSBFS_WAVE_MAX_DEFAULT, MSBFS_SEG_DEFAULT};
+  int pull_div = MSBFS_PULL_DIV_DEFAULT;
   static msbfs_opts_t from_env() {
     msbfs_opts_t o;
-    if (const char* e = env("MGX_MSBFS_SHORT_MAX")) o.short_max = std::min(std::max(atoi(e), 0), MSBFS_CUT_MAX);
-    if (const char* e = env("MGX_MSBFS_WAVE_MAX")) o.wave_max = std::min(std::max(atoi(e), 0), MSBFS_CUT_MAX);
-    if (const char* e = env("MGX_MSBFS_SEG")) o.seg = std::min(std::max(atoi(e), 1), MSBFS_CUT_MAX);
-    if (const char* e = env("MGX_MSBFS_PULL_DIV")) o.pull_div = std::min(std::max(atoi(e), 0), MSBFS_PULL_DIV_MAX);
-    o.wave_max = std::max(o.wave_max, o.short_max);
+    o.cuts.short_max = env_int("MGX_MSBFS_SHORT_MAX", 0, MSBFS_CUT_MAX, o.cuts.short_max);
+    o.cuts.wave_max = env_int("MGX_MSBFS_WAVE_MAX", 0, MSBFS_CUT_MAX, o.cuts.wave_max);
+    o.cuts.seg = env_int("MGX_MSBFS_SEG", 1, MSBFS_CUT_MAX, o.cuts.seg);
+    o.pull_div = env_int("MGX_MSBFS_PULL_DIV", 0, MSBFS_PULL_DIV_MAX, o.pull_div);
+    o.cuts.wave_max = std::max(o.cuts.wave_max, o.cuts.short_max);
     return o;
   }
 };
@@ -131,7 +133,8 @@ struct msbfs_args_t {
   msbfs_control_t* ctl;
   long long m;
   int n, count, batches, src_cap, item_cap;
-  int short_max, wave_max, seg, pull_div, timing;
+  row_cuts_t cuts;
+  int pull_div, timing;
   __device__ __forceinline__ u64* part(int k) const { return words + (size_t)k * (size_t)max(n, 1); }
   __device__ __forceinline__ u64* seen() const { return words; }
   __device__ __forceinline__ u64* front() const { return part(1); }
@@ -141,25 +144,12 @@ struct msbfs_args_t {
   __device__ __forceinline__ int source(long long i) const { return sources ? sources[i] : (int)i; }
 };
 
-__device__ __forceinline__ u64 msbfs_wave_or(u64 x) {
-#pragma unroll
-  for (int d = WAVE / 2; d > 0; d >>= 1) x |= (u64)__shfl_xor((long long)x, d, WAVE);
-  return x;
-}
 __device__ __forceinline__ u64 msbfs_uniform(u64 x) {      // a value all lanes hold, into scalar registers
   return ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(x >> 32)) << 32) | (u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)x);
 }
 __device__ __forceinline__ u64 msbfs_full(int count, int batch) {
   const long long valid = min((long long)count - (long long)batch * WAVE, (long long)WAVE);
   return valid >= WAVE ? ~0ull : ((1ull << valid) - 1ull);
-}
-// 0 no entries, 1 a lane's, 2 a wave's, 3 segmented
-__device__ __forceinline__ int msbfs_body_of(const msbfs_args_t& a, int len) {
-  return len == 0 ? 0 : (len <= a.short_max ? 1 : (len <= a.wave_max ? 2 : 3));
-}
-// rare, and not inlined: the scan inside it would cost the EXPAND loops scalar registers
-__device__ __noinline__ void msbfs_append_items(bool keep, int v, int len, int seg, int2* items, int* counter) {
-  wave_append_segments(keep, v, len, seg, items, counter);
 }
 __device__ __forceinline__ int msbfs_clock_of(int kind) {
   if (kind == MSBFS_PUSH) return MSBFS_T_PUSH;
@@ -222,34 +212,28 @@ __global__ __launch_bounds__(BLOCK) void k_msbfs_step(msbfs_args_t a, unsigned l
 
   if (kind == MSBFS_RESET) {
     const bool first_batch = batch == 0;
-    int b_out[4] = {0, 0, 0, 0}, b_in[4] = {0, 0, 0, 0};
+    row_bins_t b_out, b_in;
     long long seg_out = 0, seg_in = 0;
     for (unsigned v = gtid; v < n; v += gthreads) {
       seen[v] = 0; front[v] = 0; nxt[v] = 0;
       if (first_batch) {
         a.reach_in()[v] = 0; a.far_in()[v] = 0;
         const int lo = a.ro[v + 1] - a.ro[v];
-        const int co = msbfs_body_of(a, lo);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) b_out[c] += co == c ? 1 : 0;
-        if (co == 3) seg_out += (lo + a.seg - 1) / a.seg;
+        const int co = a.cuts.body_of(lo);
+        b_out.count(co);
+        if (co == ROW_LONG) seg_out += a.cuts.segments_of(lo);
         if (a.io) {
           const int li = a.io[v + 1] - a.io[v];
-          const int cin = msbfs_body_of(a, li);
-#pragma unroll
-          for (int c = 0; c < 4; ++c) b_in[c] += cin == c ? 1 : 0;
-          if (cin == 3) seg_in += (li + a.seg - 1) / a.seg;
+          const int cin = a.cuts.body_of(li);
+          b_in.count(cin);
+          if (cin == ROW_LONG) seg_in += a.cuts.segments_of(li);
         }
       }
     }
     if (first_batch) {
       long long* const bins = a.ctl->totals.bins;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int so = wave_sum(b_out[c]), si = wave_sum(b_in[c]);
-        if (lane == 0 && so) atomicAdd((u64*)&bins[c], (u64)so);
-        if (lane == 0 && si) atomicAdd((u64*)&bins[5 + c], (u64)si);
-      }
+      b_out.add_to(bins);
+      b_in.add_to(bins + 5);
       seg_out = wave_sum(seg_out); seg_in = wave_sum(seg_in);
       if (lane == 0 && seg_out) atomicAdd((u64*)&bins[4], (u64)seg_out);
       if (lane == 0 && seg_in) atomicAdd((u64*)&bins[9], (u64)seg_in);
@@ -299,17 +283,14 @@ __global__ __launch_bounds__(BLOCK) void k_msbfs_step(msbfs_args_t a, unsigned l
       const int beg = in ? a.ro[v] : 0;
       const int len = in ? a.ro[v + 1] - beg : 0;
       const u64 fv = in ? front[v] : 0;
-      const int body = msbfs_body_of(a, len);
-      if (body == 1)
+      const int body = a.cuts.body_of(len);
+      if (body == ROW_LANE)
         for (int k = 0; k < len; ++k) {
           const int u = a.ci[beg + k];
           const u64 bits = fv & ~seen[u];
           if (bits) atomicOr(nxt + u, bits);
         }
-      u64 todo = __ballot(body == 2);
-      while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
+      for_each_wave_row(body == ROW_WAVE, [&](int src) {
         const int b0 = __shfl(beg, src, WAVE), l0 = __shfl(len, src, WAVE);
         const u64 f0 = (u64)__shfl((long long)fv, src, WAVE);
         for (int k = lane; k < l0; k += WAVE) {
@@ -317,8 +298,8 @@ __global__ __launch_bounds__(BLOCK) void k_msbfs_step(msbfs_args_t a, unsigned l
           const u64 bits = f0 & ~seen[u];
           if (bits) atomicOr(nxt + u, bits);
         }
-      }
-      if (__ballot(body == 3)) msbfs_append_items(body == 3, v, len, a.seg, a.items, &next->n_items);
+      });
+      if (__ballot(body == ROW_LONG)) wave_append_segments_outlined(body == ROW_LONG, v, len, a.cuts.seg, a.items, &next->n_items);
     }
     return;
   }
@@ -332,8 +313,8 @@ __global__ __launch_bounds__(BLOCK) void k_msbfs_step(msbfs_args_t a, unsigned l
       const bool need = (~sn & full) != 0;
       const int beg = need ? a.io[u] : 0;
       const int len = need ? a.io[u + 1] - beg : 0;
-      const int body = msbfs_body_of(a, len);
-      if (body == 1) {
+      const int body = a.cuts.body_of(len);
+      if (body == ROW_LANE) {
         u64 acc = 0;
         for (int k = 0; k < len; ++k) {
           acc |= front[a.ia[beg + k]];
@@ -341,17 +322,14 @@ __global__ __launch_bounds__(BLOCK) void k_msbfs_step(msbfs_args_t a, unsigned l
         }
         if (acc & ~sn) nxt[u] = acc;
       }
-      u64 todo = __ballot(body == 2);
-      while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
+      for_each_wave_row(body == ROW_WAVE, [&](int src) {
         const int b0 = __shfl(beg, src, WAVE), l0 = __shfl(len, src, WAVE);
         u64 acc = 0;
         for (int k = lane; k < l0; k += WAVE) acc |= front[a.ia[b0 + k]];
-        acc = msbfs_wave_or(acc);
+        acc = wave_or(acc);
         if (lane == src && (acc & ~sn)) nxt[u] = acc;
-      }
-      if (__ballot(body == 3)) msbfs_append_items(body == 3, u, len, a.seg, a.items, &next->n_items);
+      });
+      if (__ballot(body == ROW_LONG)) wave_append_segments_outlined(body == ROW_LONG, u, len, a.cuts.seg, a.items, &next->n_items);
     }
     return;
   }
@@ -365,8 +343,8 @@ __global__ __launch_bounds__(BLOCK) void k_msbfs_step(msbfs_args_t a, unsigned l
       const int x = item.x;
       const int beg = off[x];
       const int len = off[x + 1] - beg;
-      const long long k0 = (long long)item.y * a.seg;
-      const int k1 = (int)min((long long)len, k0 + a.seg);
+      const long long k0 = (long long)item.y * a.cuts.seg;
+      const int k1 = (int)min((long long)len, k0 + a.cuts.seg);
       if (!pull) {
         const u64 fv = front[x];
         for (int k = (int)k0 + lane; k < k1; k += WAVE) {
@@ -377,7 +355,7 @@ __global__ __launch_bounds__(BLOCK) void k_msbfs_step(msbfs_args_t a, unsigned l
       } else {
         u64 acc = 0;
         for (int k = (int)k0 + lane; k < k1; k += WAVE) acc |= front[adj[beg + k]];
-        acc = msbfs_wave_or(acc);
+        acc = wave_or(acc);
         if (lane == 0 && (acc & ~seen[x])) atomicOr(nxt + x, acc);
       }
     }
@@ -417,7 +395,7 @@ __global__ __launch_bounds__(BLOCK) void k_msbfs_step(msbfs_args_t a, unsigned l
         a.far_in()[v] += pc * (u64)d;
         entries += a.ro[v + 1] - a.ro[v];
       }
-      u64 bits = msbfs_uniform(msbfs_wave_or(nw));
+      u64 bits = msbfs_uniform(wave_or(nw));
       while (bits) {
         const int b = __ffsll((long long)bits) - 1;
         bits &= bits - 1;
@@ -493,7 +471,7 @@ struct msbfs_fused_state_t {
     words = mem_t<u64>(5 * N, ctx);
     list = mem_t<int>(N, ctx);
     // rows of more than wave_max entries: an item per seg entries and one per row
-    item_cap = (int)std::min<long long>(std::min<long long>((long long)N, m / (opts.wave_max + 1) + 1) + m / opts.seg + 1, 0x7fffffff);
+    item_cap = (int)std::min<long long>(std::min<long long>((long long)N, m / (opts.cuts.wave_max + 1) + 1) + m / opts.cuts.seg + 1, 0x7fffffff);
     items = mem_t<int2>((size_t)item_cap, ctx);
     ctl = mem_t<msbfs_control_t>(1, ctx);
     h_totals = pinned_t<msbfs_totals_t>(1);
@@ -548,7 +526,7 @@ struct msbfs_fused_state_t {
     a.depth = want_depths ? depth.data() : nullptr;
     a.ctl = ctl.data();
     a.m = m; a.n = n; a.count = (int)cnt; a.batches = (int)batches; a.src_cap = src_cap; a.item_cap = item_cap;
-    a.short_max = opts.short_max; a.wave_max = opts.wave_max; a.seg = opts.seg; a.pull_div = opts.pull_div;
+    a.cuts = opts.cuts; a.pull_div = opts.pull_div;
     a.timing = timing ? 1 : 0;
     const int blocks = grid_for(n, BLOCK, std::max(ctx.num_cus, 1) * 8);
     long long waits = 0;

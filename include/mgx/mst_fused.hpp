@@ -388,8 +388,7 @@ __global__ __launch_bounds__(BLOCK) void k_mst_compress(mst_round_args_t a) {
 // ---- finish -------------------------------------------------------------------------------------------------------------------
 // tile_sum[t] = the weights of list entries [t * MST_SUM_TILE, ..) in double, summed in an order fixed by the count alone
 __device__ __forceinline__ double mst_block_sum(double x, double* sm) {
-#pragma unroll
-  for (int d = WAVE / 2; d > 0; d >>= 1) x += __shfl_xor(x, d, WAVE);
+  x = wave_sum(x);
   if (lane_id() == 0) sm[threadIdx.x / WAVE] = x;
   __syncthreads();
   double t = 0.0;

@@ -322,7 +322,7 @@ struct standard_context_t : context_t {
     num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     // MGX_GRID_CUS only ever lowers the count: the "chip-sized" grids (num_cus * 8 workgroups) then run their grid-stride loops
     // several times on a small test graph -- the carry-over of a wave's stage and every kernel's later iterations
-    if (const char* e = env("MGX_GRID_CUS")) num_cus = (int)std::min<long long>(std::max<long long>(std::atoll(e), 1), num_cus);
+    num_cus = env_int("MGX_GRID_CUS", 1, num_cus, num_cus);
     if (print_prop) std::printf("%s : %d CUs\n", prop.name, num_cus);
     mailbox = pinned_t<long long>(64);
     for (int i = 0; i < 64; ++i) mailbox[i] = 0;

@@ -46,6 +46,7 @@
 
 #include "color_hash.hpp"
 #include "env.hpp"
+#include "row_bodies.hpp"
 #include "runtime.hpp"
 #include "segsort.hpp"
 #include "wave.hpp"
@@ -68,19 +69,20 @@ enum : int { RW_BINS = 5 };                     // rows without entries, a lane'
 enum : unsigned { RW_FLAG_NEGATIVE = 1u, RW_FLAG_UNSORTED = 2u };
 
 struct rw_opts_t {
-  int tries = RW_TRIES_DEFAULT, tile = RW_TILE_DEFAULT, short_max = RW_SHORT_MAX_DEFAULT, wave_max = RW_WAVE_MAX_DEFAULT, seg = RW_SEG_DEFAULT;
+  int tries = RW_TRIES_DEFAULT, tile = RW_TILE_DEFAULT;
+  row_cuts_t cuts = {RW_SHORT_MAX_DEFAULT, RW_WAVE_MAX_DEFAULT, RW_SEG_DEFAULT};
   static rw_opts_t from_env() {
     rw_opts_t o;
-    if (const char* e = env("MGX_RW_TRIES")) o.tries = std::min(std::max(atoi(e), 1), RW_TRIES_MAX);
+    o.tries = env_int("MGX_RW_TRIES", 1, RW_TRIES_MAX, o.tries);
     if (const char* e = env("MGX_RW_TILE")) {
       const int want = std::min(std::max(atoi(e), 1), RW_TILE_MAX);
       o.tile = 1;
       while (o.tile * 2 <= want) o.tile *= 2;                // (the power of two at or below)
     }
-    if (const char* e = env("MGX_RW_SHORT_MAX")) o.short_max = std::min(std::max(atoi(e), 0), RW_CUT_MAX);
-    if (const char* e = env("MGX_RW_WAVE_MAX")) o.wave_max = std::min(std::max(atoi(e), 0), RW_CUT_MAX);
-    if (const char* e = env("MGX_RW_SEG")) o.seg = std::min(std::max(atoi(e), 1), RW_CUT_MAX);
-    o.wave_max = std::max(o.wave_max, o.short_max);
+    o.cuts.short_max = env_int("MGX_RW_SHORT_MAX", 0, RW_CUT_MAX, o.cuts.short_max);
+    o.cuts.wave_max = env_int("MGX_RW_WAVE_MAX", 0, RW_CUT_MAX, o.cuts.wave_max);
+    o.cuts.seg = env_int("MGX_RW_SEG", 1, RW_CUT_MAX, o.cuts.seg);
+    o.cuts.wave_max = std::max(o.cuts.wave_max, o.cuts.short_max);
     return o;
   }
 };
@@ -199,14 +201,10 @@ struct rw_setup_args_t {
   int* n_items;
   unsigned* flags;       // RW_FLAG_*
   long long* bins;       // RW_BINS
-  int n, item_cap, short_max, wave_max, seg;
+  int n, item_cap;
+  row_cuts_t cuts;
 };
 
-__device__ __forceinline__ u64 rw_wave_max(u64 x) {
-#pragma unroll
-  for (int d = WAVE / 2; d > 0; d >>= 1) x = max(x, (u64)__shfl_xor((long long)x, d, WAVE));
-  return x;
-}
 // entries [k0, k1) of a row of len entries at beg, k0 + first, k0 + first + stride ...: the maximum of (weight, first position)
 // and the flags (an entry greater than the one behind it; a negative or NaN weight)
 __device__ __forceinline__ u64 rw_scan_row(const rw_setup_args_t& a, int beg, int len, int k0, int k1, int first, int stride, unsigned& flags) {
@@ -222,10 +220,6 @@ __device__ __forceinline__ u64 rw_scan_row(const rw_setup_args_t& a, int beg, in
   }
   return best;
 }
-// 0 no entries, 1 a lane's, 2 a wave's, 3 segmented
-__device__ __forceinline__ int rw_body_of(const rw_setup_args_t& a, int len) {
-  return len == 0 ? 0 : (len <= a.short_max ? 1 : (len <= a.wave_max ? 2 : 3));
-}
 
 __global__ __launch_bounds__(BLOCK) void k_rw_setup(rw_setup_args_t a) {
   const unsigned gtid = blockIdx.x * (unsigned)BLOCK + threadIdx.x;
@@ -240,24 +234,24 @@ __global__ __launch_bounds__(BLOCK) void k_rw_setup(rw_setup_args_t a) {
     const int v = (int)(base + lane);
     const int beg = in ? a.ro[v] : 0;
     const int len = in ? a.ro[v + 1] - beg : 0;
-    const int body = in ? rw_body_of(a, len) : -1;
+    const int body = in ? a.cuts.body_of(len) : -1;
 #pragma unroll
     for (int c = 0; c < 4; ++c) b[c] += body == c ? 1 : 0;
-    if (body == 3) segs += (len + a.seg - 1) / a.seg;
-    if (body == 1) {
+    if (body == ROW_LONG) segs += a.cuts.segments_of(len);
+    if (body == ROW_LANE) {
       const u64 best = rw_scan_row(a, beg, len, 0, len, 0, 1, flags);
       if (a.wm) a.wm[v] = best;
     }
-    if ((body == 0 || body == 3) && a.wm) a.wm[v] = 0;          // (a segmented row's items meet here, in the launch behind)
-    u64 todo = __ballot(body == 2);
-    while (todo) {
+    if ((body == ROW_NONE || body == ROW_LONG) && a.wm) a.wm[v] = 0;          // (a segmented row's items meet here, in the launch behind)
+    u64 todo = __ballot(body == ROW_WAVE);                       // (for_each_wave_row and row_bins_t, written out: either cost this
+    while (todo) {                                               //  kernel two registers)
       const int src = __ffsll((long long)todo) - 1;
       todo &= todo - 1;
       const int b0 = __shfl(beg, src, WAVE), l0 = __shfl(len, src, WAVE);
-      const u64 best = rw_wave_max(rw_scan_row(a, b0, l0, 0, l0, lane, WAVE, flags));
+      const u64 best = wave_max(rw_scan_row(a, b0, l0, 0, l0, lane, WAVE, flags));
       if (lane == src && a.wm) a.wm[v] = best;
     }
-    if (__ballot(body == 3)) wave_append_segments(body == 3, v, len, a.seg, a.items, a.n_items);
+    if (__ballot(body == ROW_LONG)) wave_append_segments(body == ROW_LONG, v, len, a.cuts.seg, a.items, a.n_items);
   }
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
@@ -280,9 +274,9 @@ __global__ __launch_bounds__(BLOCK) void k_rw_setup_long(rw_setup_args_t a) {
     const int2 item = a.items[it];
     const int beg = a.ro[item.x];
     const int len = a.ro[item.x + 1] - beg;
-    const long long k0 = (long long)item.y * a.seg;
-    const int k1 = (int)min((long long)len, k0 + a.seg);
-    const u64 best = rw_wave_max(rw_scan_row(a, beg, len, (int)k0, k1, lane, WAVE, flags));
+    const long long k0 = (long long)item.y * a.cuts.seg;
+    const int k1 = (int)min((long long)len, k0 + a.cuts.seg);
+    const u64 best = wave_max(rw_scan_row(a, beg, len, (int)k0, k1, lane, WAVE, flags));
     if (lane == 0 && a.wm && best) atomicMax(a.wm + item.x, best);
   }
   if (flags) atomicOr(a.flags, flags);
@@ -395,7 +389,7 @@ struct rw_setup_state_t {
   long long bins[RW_BINS] = {0};
 
   rw_setup_state_t(int n_, long long m_, context_t& ctx) : n(n_), m(m_), opts(rw_opts_t::from_env()) {
-    item_cap = (int)std::min<long long>(std::min<long long>(std::max(n, 1), m / (opts.wave_max + 1) + 1) + m / opts.seg + 1, 0x7fffffff);
+    item_cap = (int)std::min<long long>(std::min<long long>(std::max(n, 1), m / (opts.cuts.wave_max + 1) + 1) + m / opts.cuts.seg + 1, 0x7fffffff);
     n_items = mem_t<int>(1, ctx);
     flags = mem_t<unsigned>(1, ctx);
     d_bins = mem_t<long long>(RW_BINS, ctx);
@@ -418,7 +412,7 @@ struct rw_setup_state_t {
     a.wm = need_w ? wm.data() : nullptr;
     a.check_order = need_o ? 1 : 0;
     a.items = items.data(); a.n_items = n_items.data(); a.flags = flags.data(); a.bins = d_bins.data();
-    a.n = n; a.item_cap = item_cap; a.short_max = opts.short_max; a.wave_max = opts.wave_max; a.seg = opts.seg;
+    a.n = n; a.item_cap = item_cap; a.cuts = opts.cuts;
     const int blocks = grid_for(n, BLOCK, std::max(ctx.num_cus, 1) * 8);
     hipLaunchKernelGGL(k_rw_setup, dim3(blocks), dim3(BLOCK), 0, st, a);
     hipLaunchKernelGGL(k_rw_setup_long, dim3(blocks), dim3(BLOCK), 0, st, a);

@@ -62,6 +62,7 @@
 // reaches through the fused BFS engine, trim-2, more than one device.
 #pragma once
 #include <algorithm>
+#include <climits>
 #include <vector>
 
 #include "cc_fused.hpp"
@@ -92,8 +93,8 @@ struct scc_opts_t {
   int long_min = SCC_LONG_MIN_DEFAULT, seg = SCC_SEG_DEFAULT;
   static scc_opts_t from_env() {
     scc_opts_t o;
-    if (const char* e = env("MGX_SCC_LONG_MIN")) o.long_min = std::max(atoi(e), 1);
-    if (const char* e = env("MGX_SCC_SEG")) o.seg = std::max(atoi(e), 1);
+    o.long_min = env_int("MGX_SCC_LONG_MIN", 1, INT_MAX, o.long_min);
+    o.seg = env_int("MGX_SCC_SEG", 1, INT_MAX, o.seg);
     return o;
   }
 };
@@ -209,8 +210,7 @@ __device__ __forceinline__ void scc_visit(const scc_step_args_t& a, scc_front_t&
     if (take) take = atomicExch(&a.vert[u].stamp, w.stamp) != w.stamp;
     if (w.pivot_phase && __ballot(take)) {
       int lowest = take ? u : SCC_NONE;
-#pragma unroll
-      for (int d = WAVE / 2; d > 0; d >>= 1) lowest = min(lowest, __shfl_xor(lowest, d, WAVE));
+      lowest = wave_min(lowest);
       if (lane_id() == 0) atomicMin(&a.ctl->totals.pivot_min, lowest);
     }
     scc_enlist(a, f, take, u, SCC_IN);
@@ -251,8 +251,7 @@ __device__ __forceinline__ void scc_sweep(const scc_step_args_t& a, scc_front_t&
       if (len >= a.long_min) len = 0;                        // (its items are walked above)
       const int c = (in && KIND != SCC_EXPAND) ? a.vert[v].col : 0;
       int longest = len;
-#pragma unroll
-      for (int d = WAVE / 2; d > 0; d >>= 1) longest = max(longest, __shfl_xor(longest, d, WAVE));
+      longest = wave_max(longest);
       for (int j = 0; j < longest; ++j) {
         const bool has = j < len;
         scc_visit<KIND>(a, f, w, out_side, has, v, c, has ? adj[beg + j] : 0);
@@ -386,8 +385,7 @@ __global__ __launch_bounds__(BLOCK) void k_scc_step(scc_step_args_t a, unsigned 
       if (kind == SCC_PMAX) best = max(best, prod);
       else if (prod == at_best) best = max(best, (u64)(0x7fffffff - v));
     }
-#pragma unroll
-    for (int d = WAVE / 2; d > 0; d >>= 1) best = max(best, (u64)__shfl_xor((long long)best, d, WAVE));
+    best = wave_max(best);
     if (lane == 0 && best > 0) {
       if (kind == SCC_PMAX) {
         if (__hip_atomic_load(&next->best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < best) atomicMax(&next->best, best);

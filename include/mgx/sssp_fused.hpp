@@ -711,8 +711,7 @@ __global__ __launch_bounds__(NT) void k_sssp_build(sssp_args_t a, int it) {
   if (a.delta > 0.f) {               // (grid-uniform) what stays behind: count and smallest distance, one atomic pair per wave
     const u32 wn = wave_sum(far_n);
     u32 wl = far_lo;
-#pragma unroll
-    for (int d = WAVE / 2; d > 0; d >>= 1) { const u32 o = (u32)__shfl_xor((int)wl, d, WAVE); wl = o < wl ? o : wl; }
+    wl = wave_min(wl);
     if ((threadIdx.x & (WAVE - 1)) == 0 && wn) {
       atomicAdd(&c->sssp_far_cnt[(it + 1) & 1], wn);
       atomicMin(&c->sssp_far_min[(it + 1) & 1], wl);
@@ -829,8 +828,7 @@ __global__ __launch_bounds__(NT, 4) void k_sssp_build2(sssp_args_t a, int it) {
   if (a.delta > 0.f) {               // (grid-uniform) what stays behind: count and smallest distance, one atomic pair per wave
     const u32 wn = wave_sum(far_n);
     u32 wl = far_lo;
-#pragma unroll
-    for (int d = WAVE / 2; d > 0; d >>= 1) { const u32 o = (u32)__shfl_xor((int)wl, d, WAVE); wl = o < wl ? o : wl; }
+    wl = wave_min(wl);
     if ((threadIdx.x & (WAVE - 1)) == 0 && wn) {
       atomicAdd(&c->sssp_far_cnt[(it + 1) & 1], wn);
       atomicMin(&c->sssp_far_min[(it + 1) & 1], wl);

@@ -39,6 +39,7 @@
 // is the k-truss's support of every entry (mgx/ktruss_fused.hpp): the same triangles, the adds sent to their three ENTRIES.
 #pragma once
 #include <algorithm>
+#include <climits>
 #include <vector>
 
 #include "env.hpp"
@@ -64,9 +65,9 @@ struct tc_opts_t {
   int short_max = TC_SHORT_MAX_DEFAULT, wave_max = TC_WAVE_MAX_DEFAULT, stage = TC_BLOCK_STAGE;
   static tc_opts_t from_env() {
     tc_opts_t o;
-    if (const char* e = env("MGX_TC_SHORT_MAX")) o.short_max = std::max(atoi(e), 0);
-    if (const char* e = env("MGX_TC_WAVE_MAX")) o.wave_max = std::max(atoi(e), 0);
-    if (const char* e = env("MGX_TC_STAGE")) o.stage = std::min(std::max(atoi(e), 1), TC_BLOCK_STAGE);
+    o.short_max = env_int("MGX_TC_SHORT_MAX", 0, INT_MAX, o.short_max);
+    o.wave_max = env_int("MGX_TC_WAVE_MAX", 0, INT_MAX, o.wave_max);
+    o.stage = env_int("MGX_TC_STAGE", 1, TC_BLOCK_STAGE, o.stage);
     return o;
   }
 };
@@ -233,8 +234,7 @@ __global__ __launch_bounds__(BLOCK) void k_tc_dagstats(tc_build_args_t a) {
   }
   (void)gmask;
   wedges = wave_sum(wedges);
-#pragma unroll
-  for (int d = WAVE / 2; d > 0; d >>= 1) longest = max(longest, __shfl_xor(longest, d, WAVE));
+  longest = wave_max(longest);
   if (lane_id() == 0) {
     if (wedges) tc_add(a.stat + TC_S_WEDGES, wedges);
     if (longest) atomicMax(a.stat + TC_S_MAXROW, (u64)longest);

@@ -36,10 +36,37 @@ __device__ __forceinline__ T wave_inclusive_sum(T x) {
   }
   return x;
 }
+// The reductions over a wave: an xor butterfly, d = 32 .. 1, after which every lane holds the result.  All 64 lanes call.  The
+// value is shuffled and compared as a T (__shfl_xor has an overload for every 32- and 64-bit integer type, unsigned ones
+// included, for float and for double): an unsigned key with its top bit set wins a wave_max, an unsigned minimum stays unsigned.
 template <typename T>
 __device__ __forceinline__ T wave_sum(T x) {
 #pragma unroll
   for (int d = WAVE / 2; d > 0; d >>= 1) x += __shfl_xor(x, d, WAVE);
+  return x;
+}
+template <typename T>
+__device__ __forceinline__ T wave_max(T x) {
+#pragma unroll
+  for (int d = WAVE / 2; d > 0; d >>= 1) {
+    const T o = __shfl_xor(x, d, WAVE);
+    x = o > x ? o : x;
+  }
+  return x;
+}
+template <typename T>
+__device__ __forceinline__ T wave_min(T x) {
+#pragma unroll
+  for (int d = WAVE / 2; d > 0; d >>= 1) {
+    const T o = __shfl_xor(x, d, WAVE);
+    x = o < x ? o : x;
+  }
+  return x;
+}
+template <typename T>
+__device__ __forceinline__ T wave_or(T x) {
+#pragma unroll
+  for (int d = WAVE / 2; d > 0; d >>= 1) x |= __shfl_xor(x, d, WAVE);
   return x;
 }
 

@@ -56,5 +56,10 @@ __device__ __forceinline__ void wave_append_segments(bool keep, int item, int le
   base = __shfl(base, WAVE - 1, WAVE);
   for (int s = 0; s < segs; ++s) out[base + incl - segs + s] = make_int2(item, s);
 }
+// the same for loops that count their scalar registers: rare there, and not inlined, since the scan inside it would cost the
+// caller's loop scalar registers it does not have
+__device__ __noinline__ void wave_append_segments_outlined(bool keep, int item, int len, int seg, int2* out, int* counter) {
+  wave_append_segments(keep, item, len, seg, out, counter);
+}
 
 }  // namespace mgx

@@ -3398,7 +3398,7 @@ int mgx_lpa_bins(mgx_lpa_t p, int64_t* out) {
   require_run(p->fused && p->fused->launches >= 0, "mgx_lpa_bins");
   const mgx::lpa_fused_state_t& f = *p->fused;
   for (int i = 0; i < 4; ++i) out[i] = f.bins[i];
-  out[4] = f.opts.short_max; out[5] = std::max(f.opts.wave_max, f.opts.short_max); out[6] = f.opts.table; out[7] = f.opts.list_div;
+  out[4] = f.opts.cuts.short_max; out[5] = std::max(f.opts.cuts.wave_max, f.opts.cuts.short_max); out[6] = f.opts.table; out[7] = f.opts.list_div;
   out[8] = f.overflowed;
   MGX_CATCH
 }
@@ -3569,7 +3569,7 @@ int mgx_msbfs_bins(mgx_msbfs_t p, int64_t* out) {
   require_run(p->fused && p->fused->launches >= 0, "mgx_msbfs_bins");
   const mgx::msbfs_fused_state_t& f = *p->fused;
   for (int i = 0; i < mgx::MSBFS_BINS; ++i) out[i] = f.bins[i];
-  out[10] = f.opts.short_max; out[11] = f.opts.wave_max; out[12] = f.opts.seg; out[13] = f.opts.pull_div;
+  out[10] = f.opts.cuts.short_max; out[11] = f.opts.cuts.wave_max; out[12] = f.opts.cuts.seg; out[13] = f.opts.pull_div;
   MGX_CATCH
 }
 int mgx_msbfs_set_timing(mgx_msbfs_t p, int on) { return chain_set_timing(p, &mgx_msbfs_s::fused, on); }
@@ -3721,7 +3721,7 @@ int mgx_rw_bins(mgx_rw_t p, int64_t* out) {
   require_run(p->last != 0 && p->setup, "mgx_rw_bins");
   const mgx::rw_setup_state_t& su = *p->setup;
   for (int i = 0; i < mgx::RW_BINS; ++i) out[i] = su.bins[i];
-  out[5] = su.opts.short_max; out[6] = su.opts.wave_max; out[7] = su.opts.seg; out[8] = su.opts.tries; out[9] = su.opts.tile;
+  out[5] = su.opts.cuts.short_max; out[6] = su.opts.cuts.wave_max; out[7] = su.opts.cuts.seg; out[8] = su.opts.tries; out[9] = su.opts.tile;
   MGX_CATCH
 }
 int mgx_rw_set_timing(mgx_rw_t p, int on) {
@@ -3863,7 +3863,7 @@ int mgx_louvain_bins(mgx_louvain_t p, int64_t* out) {
   require_run(p->last == 1, "mgx_louvain_bins");
   const mgx::louvain_fused_state_t& f = *p->fused;
   for (int i = 0; i < 4; ++i) out[i] = f.bins[i];
-  out[4] = f.opts.short_max; out[5] = f.opts.wave_max; out[6] = f.opts.seg; out[7] = f.long_items;
+  out[4] = f.opts.cuts.short_max; out[5] = f.opts.cuts.wave_max; out[6] = f.opts.cuts.seg; out[7] = f.long_items;
   MGX_CATCH
 }
 int mgx_louvain_set_timing(mgx_louvain_t p, int on) { return chain_set_timing(p, &mgx_louvain_s::fused, on); }

@@ -19,7 +19,7 @@ import math
 
 import numpy as np
 
-from tests import coloring_model, lpa_model
+from tests import coloring_model, lpa_model, row_bodies
 
 SEED = 0x9E3779B9
 STAT_KEYS = ("communities", "largest", "largest_id", "levels", "s_in", "s_sq", "w")
@@ -115,9 +115,7 @@ def aggregate(rcv, snd, wt, dense):
 
 
 def body_bins(lens, short_max, wave_max):
-    wave_max = max(wave_max, short_max)
-    return [int((lens == 0).sum()), int(((lens > 0) & (lens <= short_max)).sum()),
-            int(((lens > short_max) & (lens <= wave_max)).sum()), int((lens > wave_max).sum())]
+    return list(row_bodies.bodies(lens, short_max, wave_max).values())
 
 
 def louvain(ro, ci, symmetric=True, seed=SEED, max_iter=100, max_levels=32, tol=0.0, short_max=SHORT_MAX, wave_max=WAVE_MAX,
@@ -138,7 +136,7 @@ def louvain(ro, ci, symmetric=True, seed=SEED, max_iter=100, max_levels=32, tol=
         s = qnum(n, rcv, snd, wt, k, np.arange(n, dtype=np.int64))[1:] + (w,)
     while w > 0 and level < max_levels:
         lab, trace, accepted, q, ended = run_level(n_l, rcv, snd, wt, seed, max_iter, thr)
-        long_items = int(((lens[lens > max(wave_max, short_max)] + seg - 1) // seg).sum())
+        long_items = row_bodies.bodies(lens, short_max, wave_max, seg)["segments"]
         out["kinds"].append(SETUP)
         for _ in trace:
             out["kinds"] += [EVAL] + ([LONG_FILL, LONG_SCAN] if long_items else []) + [APPLY, QNUM]

@@ -12,7 +12,7 @@ from fractions import Fraction
 
 import numpy as np
 
-from tests import coloring_model
+from tests import coloring_model, row_bodies
 
 SYNC, LAZY = 0, 1
 SEED = coloring_model.SEED
@@ -107,7 +107,7 @@ def propagate(ro, ci, symmetric=False, mode=LAZY, seed=SEED, max_iter=100, activ
         dense = is_dense(n_act, n, list_div)
         seen = np.ones(n, dtype=bool) if dense else act
         evaluated.append(n if dense else n_act)
-        long_rows = seen & (ln > max(wave_max, short_max))
+        long_rows = seen & (row_bodies.classes(ln, short_max, wave_max) == row_bodies.LONG)
         overflowed += int((long_rows & (distinct > table)).sum())
         kinds.append(EVAL_DENSE if dense else EVAL_LIST)
         if long_rows.any():

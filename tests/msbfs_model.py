@@ -4,7 +4,7 @@ and predicts the kind and e_t of every level and the rows per body; it computes 
 transposed copy it builds itself, whatever kind the level is (the kind changes no result)."""
 import numpy as np
 
-from tests import cc_model
+from tests import cc_model, row_bodies
 
 SHORT_MAX, WAVE_MAX, SEG, PULL_DIV = 32, 1024, 1024, 8
 PUSH, PULL = 0, 1
@@ -15,12 +15,7 @@ U1 = np.uint64(1)
 
 def bodies(lengths, short_max=SHORT_MAX, wave_max=WAVE_MAX, seg=SEG):
     """rows without entries, a lane's, a wave's, segmented rows, the segments of the latter"""
-    ln = np.asarray(lengths, dtype=np.int64)
-    wave_max = max(wave_max, short_max)
-    big = ln > wave_max
-    return {"none": int((ln == 0).sum()), "short": int(((ln > 0) & (ln <= short_max)).sum()),
-            "wave": int(((ln > short_max) & (ln <= wave_max)).sum()), "long": int(big.sum()),
-            "segments": int(((ln[big] + seg - 1) // seg).sum())}
+    return row_bodies.bodies(lengths, short_max, wave_max, seg)
 
 
 def _bits_of(words):

@@ -3,6 +3,8 @@ inside a step, over the tries.  The fused path (include/mgx/rw_fused.hpp) and th
 paths, ends, lengths, visits, stats and bins, bit for bit: every float is a float32 and every product a single multiply."""
 import numpy as np
 
+from tests import row_bodies
+
 TRIES, TILE, SHORT_MAX, WAVE_MAX, SEG = 64, 16, 32, 1024, 1024
 STAT_KEYS = ("walkers", "length", "steps", "dead_ends", "restarts", "tries", "fallbacks", "sorted_copy")
 BIN_KEYS = ("none", "short", "wave", "long", "segments")
@@ -77,11 +79,7 @@ def rows_ascend(ro, ci):
 
 def row_bins(ro, short_max=SHORT_MAX, wave_max=WAVE_MAX, seg=SEG):
     """the rows per body of a setup launch"""
-    deg = np.diff(np.asarray(ro, dtype=np.int64))
-    wave_max = max(wave_max, short_max)
-    lng = deg[deg > wave_max]
-    return {"none": int((deg == 0).sum()), "short": int(((deg >= 1) & (deg <= short_max)).sum()),
-            "wave": int(((deg > short_max) & (deg <= wave_max)).sum()), "long": int(len(lng)), "segments": int((-(-lng // seg)).sum())}
+    return row_bodies.bodies(np.diff(np.asarray(ro, dtype=np.int64)), short_max, wave_max, seg)
 
 
 def fused_counts(walkers, n, starts_given, setup, sort):
