@@ -10,6 +10,8 @@ It restates what kcore_enactor_t::enact computes on ANY CSR (directed, duplicate
 """
 import numpy as np
 
+from tests import chain_model
+
 STAT_NAMES = ("levels", "passes", "expanded", "removed", "stranded")
 
 
@@ -63,8 +65,7 @@ def check_against_enactor(st, est):
 MINI_MAX = 2048          # KCORE_MINI_MAX: entries of a front one workgroup peels on its own
 LONG_MIN = 32            # KCORE_LONG_MIN: rows of at least this many entries are long
 SEG = 256                # KCORE_SEG: entries of a (vertex, segment) item
-BATCH_MIN = 64           # CHAIN_BATCH_MIN, CHAIN_BATCH_MAX (launch_chain.hpp): launches per host wait, doubling
-BATCH_MAX = 256
+BATCH_MIN, BATCH_MAX = chain_model.BATCH_MIN, chain_model.BATCH_MAX     # launches per host wait (launch_chain.hpp)
 # the codes of mini_amd.KcoreProblem.STEP_KINDS (kcore_kind_t)
 MIN, LIST, EXPAND, FILTER, IDLE, MINI = 1, 2, 3, 4, 5, 6
 _INIT = 0
@@ -186,15 +187,8 @@ def launch_plan(ro, ci):
 
 
 def host_waits_and_launches(n_kinds):
-    """(host waits, launches enqueued) of a run whose first idle launch is launch n_kinds - 1: batches of BATCH_MIN, doubling up to
-    BATCH_MAX, one wait behind each; the run ends at the first wait whose batches cover the idle launch"""
-    waits, launches, batch = 0, 0, BATCH_MIN
-    while True:
-        launches += batch
-        waits += 1
-        if launches >= n_kinds:
-            return waits, launches
-        batch = min(batch * 2, BATCH_MAX)
+    """(host waits, launches enqueued) of a run whose first idle launch is launch n_kinds - 1: tests/chain_model.py states the loop"""
+    return chain_model.waits_and_launches(n_kinds)
 
 
 # ---- the graphs both suites use ----

@@ -127,6 +127,29 @@ def decompose(row_offsets, col_indices, symmetric):
             "v": v[perm].astype(np.int32), "perm": perm}
 
 
+MIN, LIST, EXPAND, SEAL, IDLE = 1, 2, 3, 4, 5                      # ktruss_kind_t
+
+
+def peel_kinds(w):
+    """the kinds of the fused peel's launches up to and including the first idle one, from decompose's result: a level (the
+    fronts of one trussness) is MIN, LIST, SEAL, then EXPAND, SEAL per pass; behind the last level MIN finds nobody alive"""
+    kinds, level = [], None
+    for front in w["fronts"]:
+        k = int(w["truss"][front[0]])
+        if k != level:
+            kinds += [MIN, LIST, SEAL]
+            level = k
+        kinds += [EXPAND, SEAL]
+    return kinds + [MIN, IDLE]
+
+
+def peel_launches(stats):
+    """K of the fused peel's chain (tests/chain_model.py), by the kind rule of k_ktruss_step: every level is MIN, LIST and the SEAL
+    that makes the listed edges the front, every pass an EXPAND and the SEAL behind it (the level's last one finds no new front,
+    and MIN follows); then the MIN that finds nobody alive, and DONE"""
+    return 3 * stats["levels"] + 2 * stats["passes"] + 2
+
+
 def truss_edge_set(r, k):
     """the pairs (u, v), u < v, of the edges of trussness >= k"""
     keep = r["truss"][r["perm"]] >= k

@@ -167,6 +167,17 @@ def louvain(ro, ci, symmetric=True, seed=SEED, max_iter=100, max_levels=32, tol=
     return out
 
 
+def chains(kinds):
+    """K of every level's chain of launches (tests/chain_model.py), from the kinds of a run: a SETUP begins a chain; a run without
+    a level (max_levels == 0, W == 0) is one chain of SETUP and DONE"""
+    out = []
+    for k in kinds:
+        if k == SETUP:
+            out.append(0)
+        out[-1] += 1
+    return out or [2]
+
+
 def modularity(r):
     s = r["stats"]
     return 0.0 if s["w"] == 0 else s["s_in"] / s["w"] - s["s_sq"] / (s["w"] * s["w"])

@@ -112,6 +112,37 @@ def decompose(ro, ci):
     return {"labels": r.label.astype(np.int32), "stats": stats, "phases": phases}
 
 
+# ---- the fused path's launches where the graph determines them (the switch in k_scc_step, restated) ----
+# A general forward sweep's length depends on what a load sees, so its launches are not a function of the graph.  On a directed
+# path nothing sweeps, and on a directed ring every front is one vertex: there the kinds are.
+DEGINIT, LIST, EXPAND, PMAX, PPICK, RINIT, FWD, ROOTS, BWD, SEAL, DONE = range(1, 12)      # scc_kind_t
+
+
+def path_kinds(n):
+    """0 -> 1 -> ... -> n - 1, n >= 1: trim only.  LIST takes both ends (indeg 0, outdeg 0), every EXPAND of {j, n - 1 - j} empties
+    a counter of j + 1 and of n - 2 - j, which are the next front: ceil(n / 2) fronts, the last one's EXPAND appends nobody (what it
+    decrements has left already), and with nobody alive DONE follows"""
+    return [DEGINIT, LIST] + [EXPAND] * ((n + 1) // 2) + [DONE]
+
+
+def ring_kinds(n):
+    """v -> (v + 1) % n, n >= 2: nobody is trimmed, every product is 1 and the pivot is vertex 0.  FWD from {0} lowers one vertex
+    a launch; the launch whose front is {n - 1} meets vertex 0 and lowers nobody: n launches.  ROOTS claims 0, BWD claims one
+    source a launch, the one whose front is {1} meets 0 claimed: n launches.  SEAL removes all n, the EXPAND behind it appends
+    nobody, and with nobody alive DONE follows"""
+    return [DEGINIT, LIST, PMAX, PPICK, RINIT] + [FWD] * n + [ROOTS] + [BWD] * n + [SEAL, EXPAND, DONE]
+
+
+def path_launches(n):
+    """K of the chain (tests/chain_model.py) on the directed path of n vertices"""
+    return (n + 1) // 2 + 3
+
+
+def ring_launches(n):
+    """K of the chain on the directed ring of n >= 2 vertices"""
+    return 2 * n + 9
+
+
 def canonical(n, comp):
     """any component numbering -> the smallest vertex id of each component, int32"""
     comp = np.asarray(comp)

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+from tests import chain_model
 from tests import coloring_model as cm
 from tests import ktruss_cases as cases
 from tests import ktruss_model as model
@@ -19,8 +20,11 @@ pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 FIXTURES = ["bfs_test.mtx", "kcore_test.mtx", "pr_test.mtx", "sssp_test.mtx", "synthetic_dup.mtx"]
 KEYS = model.STAT_KEYS
-BUILD_WAITS = 4               # a first run's: the oriented graph's stats, the adjacency's size check, the sort's two
-MIN, LIST, EXPAND, SEAL, IDLE = 1, 2, 3, 4, 5
+# The waits beside the peel's (include/mgx/ktruss_fused.hpp: ensure_graph).  A first run's: the oriented graph's stats, the
+# adjacency's size check, the sort's two; without an edge only the first of them, the rest is not enqueued.  A repeat run builds
+# nothing and the supports wait for nothing.  Neither depends on the data beyond "is there an edge".
+BUILD_WAITS, BUILD_WAITS_NO_EDGES, REPEAT_WAITS = 4, 1, 0
+MIN, LIST, EXPAND, SEAL, IDLE = model.MIN, model.LIST, model.EXPAND, model.SEAL, model.IDLE
 
 
 def _graph(ctx, ro, ci, layout=False):
@@ -29,16 +33,6 @@ def _graph(ctx, ro, ci, layout=False):
     if layout:
         g.build_layout()
     return g
-
-
-def _batches(launches):
-    """host waits of a peel of that many launches: batches of 64, 128, 256, 256 ..."""
-    b, total, count = 64, 0, 0
-    while total < launches:
-        total += b
-        count += 1
-        b = min(2 * b, 256)
-    return count
 
 
 def _arrays(kp):
@@ -72,7 +66,11 @@ def _check(ctx, ro, ci, symmetric, layout=False, want=None, operator=True):
     a1 = _arrays(kp)
     _same(a1, wa, "fused")
     assert {k: s1[k] for k in KEYS} == w["stats"], (s1, w["stats"])
-    assert s1["built"] == 1 and 1 <= s1["host_waits"] <= _batches(s1["launches"]) + BUILD_WAITS, s1
+    # the peel's launches are the model's (3 levels + 2 passes + 2): the host enqueues whole batches up to the one that holds the
+    # DONE, and waits once behind each
+    waits, peel = chain_model.waits_and_launches(model.peel_launches(w["stats"]))
+    build_waits = BUILD_WAITS if s1["edges"] else BUILD_WAITS_NO_EDGES
+    assert s1["built"] == 1 and s1["host_waits"] == waits + build_waits, (s1, waits, peel)
     assert int(a1["hist"].sum()) == s1["edges"] and int(a1["sup0"].astype(np.int64).sum()) == 3 * s1["triangles"]
     order = kp.order()
     assert np.array_equal(np.sort(order), np.arange(s1["edges"]))
@@ -83,8 +81,10 @@ def _check(ctx, ro, ci, symmetric, layout=False, want=None, operator=True):
     kinds = kp.step_kinds()
     assert s1["edges"] == 0 or {MIN, LIST, EXPAND, SEAL, IDLE} <= set(kinds.tolist()), set(kinds.tolist())
     assert int((kinds == EXPAND).sum()) == s1["passes"] and int((kinds == LIST).sum()) == s1["levels"]
+    assert len(kinds) == peel and kinds.tolist() == chain_model.logged(model.peel_kinds(w), IDLE), "the log: the model's kinds, then IDLE"
     s2 = kp.run(symmetric)
-    assert s2["built"] == 0 and s2["launches"] < s1["launches"] and 1 <= s2["host_waits"] <= _batches(s2["launches"]), (s1, s2)
+    assert s2["built"] == 0 and s2["launches"] < s1["launches"] and s2["host_waits"] == waits + REPEAT_WAITS, (s1, s2)
+    assert np.array_equal(kp.step_kinds(), kinds)
     assert {k: s2[k] for k in KEYS} == w["stats"]
     _same(_arrays(kp), a1, "fused repeat")
     if operator:
@@ -370,7 +370,8 @@ def test_rmat18_identities_and_trusses(gpu_ctx):
     af = _arrays(kp)
     order = kp.order()
     print("fused", sf)
-    assert sf["host_waits"] <= _batches(sf["launches"]) + BUILD_WAITS and sf["passes"] > 1000
+    waits, peel = chain_model.waits_and_launches(model.peel_launches(sf))   # (no model at this size: the device's own counts)
+    assert sf["host_waits"] == waits + BUILD_WAITS and len(kp.step_kinds()) == min(peel, chain_model.LOG_CAP) and sf["passes"] > 1000
     assert np.array_equal(np.sort(order), np.arange(sf["edges"]))
     assert int(af["hist"].sum()) == sf["edges"] and int(af["sup0"].astype(np.int64).sum()) == 3 * sf["triangles"]
     for k in (sf["max_truss"], (sf["max_truss"] + 2) // 2):

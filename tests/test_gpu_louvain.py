@@ -9,7 +9,7 @@ nothing; mgx_modularity of the final labels gives back the stats' sums."""
 import numpy as np
 import pytest
 
-from tests import cc_model
+from tests import cc_model, chain_model
 from tests import louvain_cases as cases
 from tests import louvain_model as model
 from tests import lpa_cases
@@ -36,29 +36,19 @@ def _graph(ctx, ro, ci, csc=None, layout=False):
     return g
 
 
-def _batches(launches):
-    """host waits of a chain that needs that many launches: batches of 64, 128, 256, 256 ..."""
-    b, total, count = 64, 0, 0
-    while total < launches:
-        total += b
-        count += 1
-        b = min(2 * b, 256)
-    return count, total
-
-
 def _setenv(monkeypatch, opts):
     for k, v in opts.items():
         monkeypatch.setenv(ENV[k], str(v))
 
 
 def _check(ctx, ro, ci, symmetric=True, seed=model.SEED, max_iter=100, max_levels=32, tol=0.0, csc=None, layout=False, opts=None,
-           operator=True):
+           operator=True, want=None):
     """fused == operator path == model on the labels of every level, levels, trace and stats; the kinds, the rows per body and the long rows' items
     as the model predicts them; the host waits and launches; the repeat run; mgx_modularity of the final labels.
-    opts: the switches the handle reads, for the model."""
+    opts: the switches the handle reads, for the model; want: the model's result where the caller has it."""
     import mini_amd
     opts = opts or {}
-    w = model.louvain(ro, ci, symmetric, seed, max_iter, max_levels, tol, **opts)
+    w = model.louvain(ro, ci, symmetric, seed, max_iter, max_levels, tol, **opts) if want is None else want
     n = len(ro) - 1
     g = _graph(ctx, ro, ci, csc if csc else (None if symmetric else "build"), layout)
     lp = mini_amd.LouvainProblem(g)
@@ -88,17 +78,11 @@ def _check(ctx, ro, ci, symmetric=True, seed=model.SEED, max_iter=100, max_level
     # the chains: whole batches are enqueued per level (the run of max_levels == 0 and of W == 0 is one SETUP chain), one wait each;
     # the aggregation waits once per renumbering (the communities) and twice per contraction: the segmented sort's list sizes (its
     # lists are the handle's: no second wait before a release) and the coarse entries; one wait for the stats
-    chains = []
-    for k in kinds.tolist():
-        if k == model.SETUP:
-            chains.append(0)
-        chains[-1] += 1
-    if not chains:
-        chains = [2]
-    assert s1["launches"] == sum(_batches(c)[1] for c in chains)
+    chains = model.chains(w["kinds"])             # (K of every level's chain, from the model)
+    assert s1["launches"] == sum(chain_model.waits_and_launches(c)[1] for c in chains)
     # (a run that ended at max_levels does not contract its last level)
     contractions = s1["levels"] if len(w["levels"]) > s1["levels"] else max(s1["levels"] - 1, 0)
-    assert s1["host_waits"] == sum(_batches(c)[0] for c in chains) + s1["levels"] + 2 * contractions + 1, (s1, chains)
+    assert s1["host_waits"] == sum(chain_model.waits_and_launches(c)[0] for c in chains) + s1["levels"] + 2 * contractions + 1, (s1, chains)
     before = mini_amd.lib.mgx_device_allocations()
     s2 = lp.run(**args)
     assert mini_amd.lib.mgx_device_allocations() == before       # a repeat run allocates nothing

@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from tests import cc_model
+from tests import cc_model, chain_model
 from tests import lpa_cases as cases
 from tests import lpa_model as model
 from tests.grid_cus import one_cu_context
@@ -40,22 +40,14 @@ def _graph(ctx, ro, ci, csc=None, layout=False):
     return g
 
 
-def _batches(launches):
-    """host waits of a run of that many launches: batches of 64, 128, 256, 256 ..."""
-    b, total, count = 64, 0, 0
-    while total < launches:
-        total += b
-        count += 1
-        b = min(2 * b, 256)
-    return count
-
-
-def _check(ctx, ro, ci, symmetric=True, mode=LAZY, seed=model.SEED, max_iter=100, csc=None, layout=False, operator=True, opts=None):
+def _check(ctx, ro, ci, symmetric=True, mode=LAZY, seed=model.SEED, max_iter=100, csc=None, layout=False, operator=True, opts=None,
+           want=None):
     """fused == operator path == model on labels, stats [0] - [5] and the trace; the repeat run; the host waits; the kinds, the
-    rows evaluated and the overflowed rows as the model predicts them.  opts: the switches the handle reads, for the model."""
+    rows evaluated and the overflowed rows as the model predicts them.  opts: the switches the handle reads, for the model; want: the
+    model's result where the caller has it."""
     import mini_amd
     opts = opts or {}
-    w = model.propagate(ro, ci, symmetric, mode, seed, max_iter, **opts)
+    w = model.propagate(ro, ci, symmetric, mode, seed, max_iter, **opts) if want is None else want
     n = len(ro) - 1
     g = _graph(ctx, ro, ci, csc if csc else (None if symmetric else "build"), layout)
     lp = mini_amd.LpaProblem(g)
@@ -66,15 +58,17 @@ def _check(ctx, ro, ci, symmetric=True, mode=LAZY, seed=model.SEED, max_iter=100
     assert l1.dtype == np.int32
     assert np.array_equal(l1, w["labels"]), "fused: %d of %d labels differ" % (int((l1 != w["labels"]).sum()), len(l1))
     assert {k: s1[k] for k in KEYS} == w["stats"], (s1, w["stats"])
-    assert s1["host_waits"] == _batches(s1["launches"]) + STATS_WAITS, s1      # (whole batches are enqueued: exactly, not at most)
+    # the launches the model predicts end the run: the host enqueues whole batches up to the one that holds the IDLE, and no more
+    waits, launches = chain_model.waits_and_launches(len(w["kinds"]))
+    assert s1["launches"] == launches and s1["host_waits"] == waits + STATS_WAITS, (s1, len(w["kinds"]), launches, waits)
     tr = lp.trace()
     assert tr.shape == (w["stats"]["iterations"] + 1, 3)
     assert [tuple(x) for x in tr[:, :2].tolist()] == w["trace"]
     assert tr[:, 2].tolist() == w["evaluated"], (tr[:, 2].tolist(), w["evaluated"], w["active"])
     assert s1["evaluated"] == sum(w["evaluated"]) and s1["overflowed"] == w["overflowed"], (s1, w["overflowed"])
     kinds = lp.step_kinds()
-    assert len(kinds) == min(s1["launches"], 1 << 16)
-    assert kinds[:len(w["kinds"])].tolist() == w["kinds"] and (kinds[len(w["kinds"]):] == model.IDLE).all()
+    assert len(kinds) == min(launches, chain_model.LOG_CAP)
+    assert kinds.tolist() == chain_model.logged(w["kinds"], model.IDLE), "the log: the model's kinds, then IDLE, its first 2^16"
     b = lp.bins()
     ln = model.row_entries(ro, ci, symmetric)
     sm, wm = b["short_max"], b["wave_max"]

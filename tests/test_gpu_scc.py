@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from tests import cc_model
+from tests import cc_model, chain_model
 from tests import scc_cases as cases
 from tests import scc_model as model
 from tests.grid_cus import one_cu_context
@@ -35,18 +35,19 @@ def _graph(ctx, ro, ci, upload=False, layout=False):
     return g
 
 
-def _batches(launches):
-    """host waits of a run of that many launches: batches of 64, 128, 256, 256 ..."""
-    b, total, count = 64, 0, 0
-    while total < launches:
-        total += b
-        count += 1
-        b = min(2 * b, 256)
-    return count
+def launches_by_the_log(kinds):
+    """K of a run whose log holds its end: the number of the first idle launch, plus one.  Where no model predicts the launches (a
+    forward sweep's length depends on what a load sees), this is what ties the host's loop to the device's end: the launches
+    enqueued and the host's waits follow from it (tests/chain_model.py), not from what the host enqueued"""
+    idle = np.flatnonzero(kinds == IDLE)
+    assert len(idle) and (kinds[idle[0]:] == IDLE).all(), "nothing runs behind the first idle launch"
+    return int(idle[0]) + 1
 
 
-def _check(ctx, ro, ci, want=None, upload=False, layout=False, operator=True):
-    """fused == operator path == model on labels and stats [0] - [5]; the repeat run; the host waits; the launches' kinds"""
+def _check(ctx, ro, ci, want=None, upload=False, layout=False, operator=True, want_kinds=None):
+    """fused == operator path == model on labels and stats [0] - [5]; the repeat run; the launches' kinds; the launches and the host
+    waits from the run's end.  want_kinds: the kinds of every launch up to the first idle one, where the graph determines them
+    (scc_model.path_kinds, ring_kinds); else the end is read from the log"""
     import mini_amd
     w = model.decompose(ro, ci) if want is None else want
     g = _graph(ctx, ro, ci, upload, layout)
@@ -57,17 +58,29 @@ def _check(ctx, ro, ci, want=None, upload=False, layout=False, operator=True):
     assert l1.dtype == np.int32
     assert np.array_equal(l1, w["labels"]), "fused: %d of %d labels differ" % (int((l1 != w["labels"]).sum()), len(l1))
     assert {k: s1[k] for k in KEYS} == w["stats"], (s1, w["stats"])
-    assert s1["host_waits"] == _batches(s1["launches"]) + STATS_WAITS, s1     # (whole batches are enqueued: exactly, not at most)
     kinds = sp.step_kinds()
     st = w["stats"]
-    assert len(kinds) == min(s1["launches"], 1 << 16) and kinds[0] == DEGREES and kinds[1] == LIST and kinds[-1] == IDLE
-    if s1["launches"] <= 1 << 16:
-        count = {k: int((kinds == k).sum()) for k in range(1, 12)}
-        phases = st["rounds"] + (1 if st["pivot_size"] else 0)
-        assert count[DEGREES] == 1 and count[LIST] == 1 and count[PMAX] == count[PPICK] == (1 if st["pivot_size"] else 0)
+    if want_kinds is not None:
+        assert kinds.tolist() == chain_model.logged(want_kinds, IDLE), "the log: the predicted kinds, then IDLE, its first 2^16"
+        n_kinds = len(want_kinds)
+    else:
+        n_kinds = launches_by_the_log(kinds)
+    waits, launches = chain_model.waits_and_launches(n_kinds)
+    assert s1["launches"] == launches and s1["host_waits"] == waits + STATS_WAITS, (s1, n_kinds, launches, waits)
+    assert len(kinds) == min(launches, chain_model.LOG_CAP) and kinds[0] == DEGREES and kinds[1] == LIST
+    count = {k: int((kinds == k).sum()) for k in range(1, 12)}
+    phases = st["rounds"] + (1 if st["pivot_size"] else 0)
+    assert sum(count.values()) == len(kinds)                     # (every launch is one of the eleven kinds)
+    assert count[DEGREES] == 1 and count[LIST] == 1 and count[PMAX] == count[PPICK] == (1 if st["pivot_size"] else 0)
+    if launches <= chain_model.LOG_CAP:
+        assert kinds[-1] == IDLE and count[IDLE] == launches - n_kinds + 1
         assert count[RINIT] == count[ROOTS] == count[SEAL] == phases
         assert count[FWD] >= phases and count[BWD] >= phases and count[EXPAND] >= phases
-        assert sum(count.values()) == s1["launches"] and count[IDLE] >= 1          # (every launch is one of the eleven kinds)
+    else:
+        # the log ends before the run does: what it holds is the run's first 2^16 launches, and the run ended all the same
+        # (bit 1 of `done`, a fixpoint that did not end, would have thrown; the labels and stats above are the model's)
+        assert count[RINIT] <= phases and count[ROOTS] <= phases and count[SEAL] <= phases and count[RINIT] >= min(phases, 1)
+        assert count[IDLE] == max(chain_model.LOG_CAP - (n_kinds - 1), 0)
     s2 = sp.run()
     assert s2 == s1, (s1, s2)                                    # a repeat run: the same launches, the same waits
     assert np.array_equal(sp.labels(), l1)
@@ -126,14 +139,14 @@ def test_unsorted_rows(gpu_ctx):
 @pytest.mark.parametrize("n", [2, 3, 5000])
 def test_ring(gpu_ctx, n):
     """one component, the pivot's; 5000: as many forward and backward sweeps, across the first batches of launches"""
-    w, s = _check(gpu_ctx, *cases.ring(n))
+    w, s = _check(gpu_ctx, *cases.ring(n), want_kinds=model.ring_kinds(n))           # (one hop a launch: the kinds are the graph's)
     assert s["components"] == 1 and s["pivot_size"] == n and s["trimmed"] == 0 and s["launches"] >= 2 * n
 
 
 @pytest.mark.parametrize("n", [3, 5000])
 def test_path(gpu_ctx, n):
     """3: the middle vertex loses both counters in one pass and is removed once; 5000: 2500 trim passes"""
-    w, s = _check(gpu_ctx, *cases.path(n))
+    w, s = _check(gpu_ctx, *cases.path(n), want_kinds=model.path_kinds(n))           # (trim only: the kinds are the graph's)
     assert s["components"] == n and s["trimmed"] == n and s["pivot_size"] == 0
     assert s["launches"] >= n // 2
 
@@ -221,7 +234,8 @@ def test_rmat18_against_scipy(gpu_ctx, oracle):
     want = model.scipy_labels(ro, ci)
     assert np.array_equal(sp.labels(), want)
     assert (s["components"], s["largest"], s["largest_label"]) == model.label_stats(want)
-    assert s["host_waits"] == _batches(s["launches"]) + STATS_WAITS
+    waits, launches = chain_model.waits_and_launches(launches_by_the_log(sp.step_kinds()))
+    assert s["launches"] == launches and s["host_waits"] == waits + STATS_WAITS, (s, launches, waits)
     sp.close()
     g.close()
 
