@@ -155,6 +155,7 @@ struct bfs_run_stats_t {
   int lazy_slots = 0;                // slots that ran without queues (bfs_build_is_lazy)
   int cold_slots = 0;                // slots that ran the cold-edge pass (bfs_fused_cold.hpp)
   int mini_slots = 0;                // levels expanded by M launches (bfs_fused_mini.hpp)
+  int level_byte_slot = 0;           // 1 + the last slot whose queue build stored level bytes (mgx/bfs_fused.hpp: lvl8); 0: none did
   long long claims_level[64] = {0};
 };
 
@@ -206,6 +207,7 @@ struct bfs_fused_enactor_t {
     last.lazy_slots = hc->lazy_slots;
     last.cold_slots = hc->cold_slots;
     last.mini_slots = hc->mini_slots;
+    last.level_byte_slot = hc->lvl8_slot;
     for (int i = 0; i < last.push_levels && i < (int)last.trace.size(); ++i) last.push_edges += last.trace[i].second;
     if (hc->levels > (int)last.trace.size() && !direction_optimizing) last.push_edges = last.m_t;   // (a deep traversal whose trace tail stayed on the device)
     long long push_vertices = 0;

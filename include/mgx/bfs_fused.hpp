@@ -116,6 +116,8 @@ struct bfs_ctrl_t {
   // bitmap exchange.  d2_level_kind[L]: 1 merged from id lists, 2 its lists overflowed, 0 bitmaps without asking (or not run);
   // d2_level_new[L]: vertices all ranks discovered in level L (what the next plan is made from).
   int d2_frozen_level;           // -1: not frozen
+  int lvl8_slot;     // level bytes (bfs_fused_args_t::lvl8): 1 + the last slot whose queue build stored any (0: none since the init) -- what
+                     // the translation role compares with the first slot of its batch of launches (bfs_translate_body)
   unsigned char d2_level_kind[64];
   u32 d2_level_new[64];
   u64 stamp[64];     // s_memrealtime (100 MHz) when each level was opened: per-level times without host syncs
@@ -140,6 +142,9 @@ struct bfs_fused_args_t {
   const int* in_indices;
   const int* old_of_new;   // hub-first layout: original id of layout vertex v (NULL = identity)
   const int* new_of_old;   // and its inverse
+  unsigned char* lvl8 = nullptr;   // n bytes (padded like mark), LAYOUT order: the level k_bfs_build2 found the vertex in, 0xFF: none stored.  Set on
+                           // the single-GPU path under a hub-first layout (MGX_BFS_LEVEL_BYTES): the build stores these contiguous bytes instead of
+                           // scattering labels[old_of_new[v]], and bfs_translate_body writes the labels in one coalesced pass; NULL: labels directly
   int long_min;            // rows of at least this many edges go to the long-row queue (0: no such queue)
   u32 hot_min_edges;       // a push kernel copies the hot prefix of the bitmap into LDS when its queue holds at least this many edges
   int mode;                // MGX_BFS_PUSH / MGX_BFS_DIRECTION_OPT
@@ -304,6 +309,7 @@ __device__ __forceinline__ void bfs_ctrl_reset(bfs_ctrl_t* c) {
   for (int i = 0; i < 4; ++i) c->mini_blocks[i] = 0u;
   c->reached_mini = 0;
   c->d2_frozen_level = -1;
+  c->lvl8_slot = 0;
   for (int i = 0; i < 16; ++i) ((u32*)c->d2_level_kind)[i] = 0u;
   for (int i = 0; i < 64; ++i) c->d2_level_new[i] = 0u;
   c->sssp_thr = 0x7f7fffffu;
@@ -365,8 +371,12 @@ __device__ __forceinline__ void bfs_init_body(const bfs_fused_args_t& a, int src
                                src_old == j + 3 ? 0 : -1);
       *(int4*)(a.labels + j) = l;
       *(u32*)(a.mark + i * 4) = 0u;
+      if (a.lvl8) *(u32*)(a.lvl8 + i * 4) = 0xFFFFFFFFu;
     } else {
-      for (long long j = i * 4; j < n; ++j) { a.labels[j] = (j == src_old) ? 0 : -1; a.mark[j] = 0; }
+      for (long long j = i * 4; j < n; ++j) {
+        a.labels[j] = (j == src_old) ? 0 : -1; a.mark[j] = 0;
+        if (a.lvl8) a.lvl8[j] = 0xFF;
+      }
     }
   }
   const u32 src_bit = 1u << (src & 31);
@@ -992,6 +1002,13 @@ __global__ __launch_bounds__(NT, 4) void k_bfs_build2(bfs_fused_args_t a, int ar
   const int mine = __popc(new16);
 
   // ---- my discoveries' row extents and label targets: contiguous, no gathers ----------------------------------------
+  // LEVEL BYTES (a.lvl8; levels up to 254: grid-uniform).  Nothing inside a traversal reads labels[] -- pushes, builds, chains and M
+  // launches read bitmaps, marks and queues -- so under a hub-first layout the build does not scatter labels[old_of_new[v]] (a 4-byte
+  // store per discovery at a random original id: one 32-byte sector each, 77 MB per RMAT-22 traversal, behind 64 bytes of old_of_new per
+  // thread): it stores the level into the thread's own 16 contiguous bytes of lvl8 -- one 16-byte read-modify-write, the read asked for
+  // beside the row extents --, and bfs_translate_body writes the labels from them, coalesced, beside a tail launch.  From level 255 on
+  // (a grid, a path): the int stores as ever.
+  const bool lvl_bytes = !DIST && a.lvl8 != nullptr && new_label <= 254;
   u32 ro[17];
   int target[16];
   u64 sum_s = 0, sum_l = 0;
@@ -1003,6 +1020,8 @@ __global__ __launch_bounds__(NT, 4) void k_bfs_build2(bfs_fused_args_t a, int ar
 #pragma unroll
     for (int q = 0; q < 16; ++q) target[q] = (int)(i0 + q);
   } else if (new16) {
+    uint4 lb = make_uint4(0u, 0u, 0u, 0u);
+    if (lvl_bytes) lb = *(const uint4*)(a.lvl8 + i0);                        // (i0 is a multiple of 16; padded like mark: always readable)
     if (i0 + 16 < (long long)n) {                                            // (row_offsets has n + 1 entries)
       const u32* const p = a.row_offsets + i0;                               // i0 is a multiple of 16: 64-byte aligned
       const uint4 r0 = *(const uint4*)p, r1 = *(const uint4*)(p + 4), r2 = *(const uint4*)(p + 8), r3 = *(const uint4*)(p + 12);
@@ -1013,7 +1032,19 @@ __global__ __launch_bounds__(NT, 4) void k_bfs_build2(bfs_fused_args_t a, int ar
 #pragma unroll
       for (int q = 0; q < 17; ++q) ro[q] = a.row_offsets[(i0 + q <= (long long)n) ? i0 + q : (long long)n];
     }
-    if (a.old_of_new) {
+    if (lvl_bytes) {
+      // the thread is the only writer of its 16 bytes (as of its half-word of the bitmap); new16 has no bit at or behind n
+      if (!(MGX_LAB_GET(a, build_diag, 0) & 1)) {
+        const u32 lab4 = (u32)new_label * 0x01010101u;
+        u32 w[4] = {lb.x, lb.y, lb.z, lb.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const u32 bm = ((((new16 >> (4 * q)) & 15u) * 0x00204081u) & 0x01010101u) * 0xFFu;      // 4 bits -> 4 byte masks
+          w[q] = (w[q] & ~bm) | (lab4 & bm);
+        }
+        *(uint4*)(a.lvl8 + i0) = make_uint4(w[0], w[1], w[2], w[3]);
+      }
+    } else if (a.old_of_new) {
       if (i0 + 16 <= (long long)n) {
         const int* const p = a.old_of_new + i0;
         const int4 t0 = *(const int4*)p, t1 = *(const int4*)(p + 4), t2 = *(const int4*)(p + 8), t3 = *(const int4*)(p + 12);
@@ -1030,7 +1061,7 @@ __global__ __launch_bounds__(NT, 4) void k_bfs_build2(bfs_fused_args_t a, int ar
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       if ((new16 >> q) & 1u) {
-        if (!(MGX_LAB_GET(a, build_diag, 0) & 1)) labels[target[q]] = new_label;
+        if (!lvl_bytes && !(MGX_LAB_GET(a, build_diag, 0) & 1)) labels[target[q]] = new_label;
         const u32 deg = ro[q + 1] - ro[q];
         if (deg >= long_min) { sum_l += CNT1 | (u64)bfs_lq_pad(deg); long_true += deg; }
         else if (deg) sum_s += CNT1 | (u64)deg;
@@ -1051,6 +1082,7 @@ __global__ __launch_bounds__(NT, 4) void k_bfs_build2(bfs_fused_args_t a, int ar
     __syncthreads();
     if (threadIdx.x == 0 && s_scan[3]) {
       const u64 tot_s = s_scan[0], tot_l = s_scan[1];
+      if (lvl_bytes) c->lvl8_slot = slot + 1;          // (every workgroup that found anything stores the same value)
       atomicAdd(&c->reached, s_scan[3]);
       if (tot_s >> 40) atomicAdd(&c->cursor[(slot + 1) % 3], ((tot_s >> 40) << BFS_VSHIFT) | (tot_s & DEGMASK));
       if (tot_l >> 40) {
@@ -1072,6 +1104,7 @@ __global__ __launch_bounds__(NT, 4) void k_bfs_build2(bfs_fused_args_t a, int ar
   u64 ex_l = block_exclusive_sum_lean<NW>(sum_l, s_scan, &tot_l);
   // the two returning atomics from two different waves: one thread would wait for the first before it issues the second
   if (threadIdx.x == 0) {
+    if (lvl_bytes) c->lvl8_slot = slot + 1;            // (every workgroup that found anything stores the same value)
     atomicAdd(&c->reached, tot_n);
     if (MGX_LAB_GET(a, build_diag, 0) & 4) s_base[0] = ((u64)blockIdx.x * 8192) << BFS_VSHIFT;
     else s_base[0] = (tot_s >> 40) ? atomicAdd(&c->cursor[(slot + 1) % 3], ((tot_s >> 40) << BFS_VSHIFT) | (tot_s & DEGMASK)) : 0ull;
@@ -1107,6 +1140,47 @@ __global__ __launch_bounds__(NT, 4) void k_bfs_build2(bfs_fused_args_t a, int ar
       }
     }
   }
+}
+
+// The TRANSLATION of the level bytes (a.lvl8, see k_bfs_build2), block `blk` of `nblk` blocks of NT threads: for every original id o,
+// b = lvl8[new_of_old[o]]; labels[o] = b where a byte is stored.  new_of_old is read and labels are written coalesced (a wave
+// instruction covers 64 consecutive ids), the byte gathers hit a table of n bytes that lives in the L2s; a thread has K gathers in
+// flight, its loads unconditional (index clamped, store masked).  A gather by original id and not a scatter from layout order: the
+// scatter is the very store pattern the bytes were introduced to remove (a 32-byte sector per label).
+// It writes ONLY where a byte is stored -- the vertices the byte builds discovered, which no chain, M launch or int-path build ever
+// writes (a vertex is discovered once) -- so it may run beside or behind any of them, once the last queue build of the batch of
+// launches is over: a role of the launch behind it (bfs_fused_run.hpp), never a launch in between.  Idempotent: a traversal that
+// needs another batch of slots translates again at that batch's tail.  No byte stored since `first_slot` (the first slot of the
+// batch of launches; ctrl->lvl8_slot is written by builds only, none runs beside this): nothing to sweep, returns at once.
+template <int NT>
+__device__ __forceinline__ void bfs_translate_body(const bfs_fused_args_t& a, int first_slot, u32 blk, u32 nblk) {
+  constexpr int K = 8;
+  if (!a.lvl8 || a.ctrl->lvl8_slot <= first_slot) return;                    // (grid-uniform)
+  const long long n = a.n;
+  const long long T = (long long)nblk * NT;
+  const int* __restrict__ const new_of_old = a.new_of_old;
+  const unsigned char* __restrict__ const lvl8 = a.lvl8;
+  int* __restrict__ const labels = a.labels;
+  for (long long base = (long long)blk * NT + threadIdx.x; base < n; base += T * K) {
+    int at[K];
+    unsigned char b[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const long long o = base + (long long)k * T;
+      at[k] = new_of_old[o < n ? o : n - 1];
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) b[k] = lvl8[at[k]];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const long long o = base + (long long)k * T;
+      if (o < n && b[k] != 0xFF) labels[o] = (int)b[k];
+    }
+  }
+}
+// ... as a launch of its own: only where a batch of launches ends WITHOUT an in-place chain launch to ride in (chains switched off)
+__global__ __launch_bounds__(1024) void k_bfs_translate(bfs_fused_args_t a, int first_slot) {
+  bfs_translate_body<1024>(a, first_slot, blockIdx.x, gridDim.x);
 }
 
 // End of a batch of launches: the control block's head goes to the host's pinned copy, then a sequence number the host
@@ -1166,6 +1240,8 @@ struct bfs_run_opts_t {
   long long defer = -1;    // MGX_BFS_DEFER: 0 never defer hot marks, N: flush a bitmap above N deferred marks per workgroup
   int spin = -1;           // (no switch since round 6) 0 read the control block back with a copy + hipStreamSynchronize, 1 publish kernel + spin, -1 the handle's default
   int build_list = 0;      // MGX_BFS_BUILD_LIST=1: the list-based queue build (k_bfs_build) instead of k_bfs_build2
+  int level_bytes = 1;     // MGX_BFS_LEVEL_BYTES=0: k_bfs_build2 scatters its discoveries' labels itself under a hub-first layout (default: level
+                           // bytes in layout order + one translation pass beside a tail launch, bfs_fused_args_t::lvl8)
   int mini = 1;            // MGX_BFS_MINI=0: no M launches (mid-size levels take device-wide slots; bfs_fused_mini.hpp); 1: on graphs of at
                            // least 2^22 vertices; 2: always
   int batch_overlap = 1;   // MGX_BFS_BATCH_OVERLAP=0: a batch (mgx_bfs_run_many) runs every traversal in the handle's one state, its launches strictly
@@ -1188,6 +1264,7 @@ struct bfs_run_opts_t {
     geti("MGX_BFS_VSHORT", o.vshort);
     getll("MGX_BFS_CHAIN_MAX_EDGES", o.chain);
     geti("MGX_BFS_BUILD_LIST", o.build_list);
+    geti("MGX_BFS_LEVEL_BYTES", o.level_bytes);
     getll("MGX_BFS_DEFER", o.defer);
     geti("MGX_BFS_DEFER_WORDS", o.defer_words);
     geti("MGX_BFS_SRC_PLAN", o.src_plan);
@@ -1231,18 +1308,19 @@ struct bfs_alt_state_t {
   mem_t<char> pool;                  // ONE allocation (a batch makes it while the device works: every call counts), carved into:
   u32 *visited = nullptr, *frontier_bits = nullptr;
   unsigned char* mark = nullptr;
+  unsigned char* lvl8 = nullptr;     // level bytes (bfs_fused_args_t::lvl8)
   u32 *fr_row[2] = {}, *fr_off[2] = {}, *lq_row[2] = {}, *lq_off[2] = {};
   bfs_ctrl_t* ctrl = nullptr;
   u32* slot_marks = nullptr;
   int* labels = nullptr;
-  // NULL when the device has no room for it (37 bytes per vertex): the caller goes on with the one state it has
+  // NULL when the device has no room for it (38 bytes per vertex): the caller goes on with the one state it has
   static std::unique_ptr<bfs_alt_state_t> make(int num_nodes, size_t words, standard_context_t& ctx) {
     std::unique_ptr<bfs_alt_state_t> t(new bfs_alt_state_t());
     const size_t n = (size_t)num_nodes;
     size_t at = 0;
     auto take = [&](size_t bytes) { const size_t off = at; at += (bytes + 255) & ~(size_t)255; return off; };
     const size_t o_vis = take(words * 4), o_fb = take(words * 4), o_mark = take(n + 64), o_ctrl = take(sizeof(bfs_ctrl_t)),
-                 o_sm = take((size_t)2 * BFS_MARK_CTRS * BFS_MARK_STRIDE * 4), o_lab = take((n + 4) * 4);
+                 o_sm = take((size_t)2 * BFS_MARK_CTRS * BFS_MARK_STRIDE * 4), o_lab = take((n + 4) * 4), o_lvl = take(n + 64);
     size_t o_q[8];
     for (int i = 0; i < 8; ++i) o_q[i] = take((n + 1) * 4);
     char* b = nullptr;
@@ -1250,6 +1328,7 @@ struct bfs_alt_state_t {
     t->pool = mem_t<char>::adopt(b, at);
     t->visited = (u32*)(b + o_vis); t->frontier_bits = (u32*)(b + o_fb); t->mark = (unsigned char*)(b + o_mark);
     t->ctrl = (bfs_ctrl_t*)(b + o_ctrl); t->slot_marks = (u32*)(b + o_sm); t->labels = (int*)(b + o_lab);
+    t->lvl8 = (unsigned char*)(b + o_lvl);
     for (int i = 0; i < 2; ++i) {
       t->fr_row[i] = (u32*)(b + o_q[i]); t->fr_off[i] = (u32*)(b + o_q[2 + i]);
       t->lq_row[i] = (u32*)(b + o_q[4 + i]); t->lq_off[i] = (u32*)(b + o_q[6 + i]);
@@ -1265,6 +1344,7 @@ struct bfs_fused_state_t {
   bfs_run_opts_t opts = bfs_run_opts_t::from_env();
   mem_t<u32> visited;
   mem_t<unsigned char> mark;
+  mem_t<unsigned char> lvl8;         // level bytes (bfs_fused_args_t::lvl8): n + 64, allocated by the first plan that uses them
   mem_t<u32> frontier_bits;
   mem_t<u32> fr_row[2];
   mem_t<u32> fr_off[2];

@@ -206,8 +206,12 @@ __device__ __forceinline__ void bfs_chain_inplace_body(const bfs_fused_args_t& a
   if (!bfs_level_is_chained(a, cur, lcur, c->ledges[slot % 3], a.chain_big_edges, BFS_CHAIN_CAP_BIG)) return;
   bfs_chain_body<1024, true, BFS_CHAIN_CAP_BIG>(a, slot, level);
 }
-__global__ __launch_bounds__(1024) void k_bfs_chain_inplace(bfs_fused_args_t a, int arg) {
-  bfs_chain_inplace_body(a, arg);
+// Behind a batch of launches (the tail of a call, of the last traversal of a batch of sources, of every later batch of slots) the grid
+// may be 1 + E workgroups: the others translate the level bytes the batch's queue builds stored (bfs_translate_body; first_slot: the
+// batch's first slot) beside the chain -- the two write disjoint labels and share nothing else.
+__global__ __launch_bounds__(1024) void k_bfs_chain_inplace(bfs_fused_args_t a, int arg, int first_slot) {
+  if (blockIdx.x == 0) bfs_chain_inplace_body(a, arg);
+  else bfs_translate_body<1024>(a, first_slot, blockIdx.x - 1u, gridDim.x - 1u);
 }
 
 // The SEAM between two traversals of a batch (bfs_fused_run_many): traversal A ends with [M][chain], traversal B begins with
@@ -218,8 +222,10 @@ __global__ __launch_bounds__(1024) void k_bfs_chain_inplace(bfs_fused_args_t a, 
 // fences between them, so a seam launch can hang no more than the launches it replaces.  The launch boundaries in front of and behind
 // it order each role against its own traversal's neighbours exactly as before.
 //   k_bfs_seam_mini_init    [A: the M launch behind the slots, BFS_MINI_WGS workgroups][B: init, the rest of the grid]
-//   k_bfs_seam_chain_chain  [A: the chain behind that, one workgroup][B: the chain at the start, one workgroup]
-//   k_bfs_seam_chain_init   (plans without M launches) [A: the chain behind the slots][B: init]; B's chain is a launch of its own
+//   k_bfs_seam_chain_chain  [A: the chain behind that, one workgroup][B: the chain at the start, one workgroup][A: translation, the rest]
+//   k_bfs_seam_chain_init   (plans without M launches) [A: the chain behind the slots][B: init][A: translation]; B's chain is a launch of its own
+// (A's translation of its level bytes, bfs_translate_body: A's queue builds are all over, and it writes only labels that neither A's
+//  chain nor anybody else writes.  The first two workgroups of k_bfs_seam_chain_chain used to be alone on the device.)
 // B's init resets the state that the traversal BEFORE A used and copies that one's head out first (init.prev_ctrl == B's own control
 // block): a launch boundary lies between that traversal's last write and this read.  A's head is NOT copied here -- the launch is
 // still working on it.
@@ -228,6 +234,7 @@ struct bfs_seam_init_t {
   const bfs_ctrl_t* prev_ctrl;
   bfs_ctrl_t* prev_head;
   int src, head_words;
+  int ninit;           // k_bfs_seam_chain_init: workgroups of the init role (behind them: the translation role's)
 };
 static_assert(2 * sizeof(bfs_fused_args_t) + sizeof(bfs_seam_init_t) + 64 <= 4096, "a seam launch's two argument structs fit the 4 KB of kernel arguments");
 __global__ __launch_bounds__(1024) void k_bfs_seam_mini_init(bfs_fused_args_t a, int arg_a, bfs_fused_args_t b, bfs_seam_init_t init) {
@@ -237,11 +244,14 @@ __global__ __launch_bounds__(1024) void k_bfs_seam_mini_init(bfs_fused_args_t a,
 }
 __global__ __launch_bounds__(1024) void k_bfs_seam_chain_chain(bfs_fused_args_t a, int arg_a, bfs_fused_args_t b, int arg_b) {
   if (blockIdx.x == 0) bfs_chain_inplace_body(a, arg_a);
-  else bfs_chain_inplace_body(b, arg_b);
+  else if (blockIdx.x == 1) bfs_chain_inplace_body(b, arg_b);
+  else bfs_translate_body<1024>(a, 0, blockIdx.x - 2u, gridDim.x - 2u);
 }
 __global__ __launch_bounds__(1024) void k_bfs_seam_chain_init(bfs_fused_args_t a, int arg_a, bfs_fused_args_t b, bfs_seam_init_t init) {
+  const u32 ninit = (u32)init.ninit;
   if (blockIdx.x == 0) bfs_chain_inplace_body(a, arg_a);
-  else bfs_init_body<1024>(b, init.src, init.nwords, init.prev_ctrl, init.prev_head, init.head_words, blockIdx.x - 1u, gridDim.x - 1u);
+  else if (blockIdx.x <= ninit) bfs_init_body<1024>(b, init.src, init.nwords, init.prev_ctrl, init.prev_head, init.head_words, blockIdx.x - 1u, ninit);
+  else bfs_translate_body<1024>(a, 0, blockIdx.x - 1u - ninit, gridDim.x - 1u - ninit);
 }
 
 #ifdef MGX_LAB
@@ -437,6 +447,11 @@ inline bfs_launch_plan_t bfs_fused_plan(bfs_fused_state_t& st, const int* row_of
   //  -- RMAT-22, per call: 1/2 0.3282, 1/4 0.3262, 1/8 0.3215, 1/16 0.3250 ms; with 32-bit entries 1/2 was best)
   // k_bfs_build2 reads a thread's 17 row offsets and 16 layout ids with 16-byte loads: borrowed arrays must be aligned
   const bool build2_ok = ((uintptr_t)a.row_offsets % 16 == 0) && ((uintptr_t)a.old_of_new % 16 == 0);
+  // level bytes (bfs_fused_args_t::lvl8): under a hub-first layout, where k_bfs_build2 is the queue build (without a layout its label
+  // stores are contiguous already)
+  const bool level_bytes = relabelled && a.old_of_new && a.new_of_old && build2_ok && !opt.build_list && opt.level_bytes != 0;
+  if (level_bytes && !st.lvl8.size()) st.lvl8 = mem_t<unsigned char>((size_t)st.n + 64, ctx);
+  a.lvl8 = level_bytes ? st.lvl8.data() : nullptr;
   // cold-edge lists (bfs_fused_cold.hpp): with the unit blocks they were cut from, the prefix they were cut behind, and a
   // queue build that knows their bitmaps
   // (the pairs at 8 bytes -- round 6: gone when every slice is packed -- or every slice packed at 4 and a run that may read those)
@@ -584,7 +599,27 @@ inline int bfs_class_slots(const bfs_fused_state_t& st, int cls) {
 // the launches of a traversal on the product path (no events, merged push): init + the chain of the small levels at the
 // start; one slot; the chain behind the last slot of a batch.  prev_head: see k_bfs_fused_init.
 inline void bfs_enqueue_chain_inplace(const bfs_launch_plan_t& plan, int slot, hipStream_t s) {
-  hipLaunchKernelGGL(k_bfs_chain_inplace, dim3(1), dim3(1024), bfs_chain_lds_bytes(BFS_CHAIN_CAP_BIG), s, plan.a, bfs_slot_arg(slot));
+  hipLaunchKernelGGL(k_bfs_chain_inplace, dim3(1), dim3(1024), bfs_chain_lds_bytes(BFS_CHAIN_CAP_BIG), s, plan.a, bfs_slot_arg(slot), 0);
+}
+// workgroups of a translation role (bfs_translate_body) that has `room` compute units beside the other roles of its launch -- the
+// chain's LDS gives one workgroup per CU --: no more than the ids need at eight a thread; 0: the plan stores no level bytes
+inline int bfs_translate_wgs(const bfs_launch_plan_t& plan, int room) {
+  if (!plan.a.lvl8) return 0;
+  const long long want = ((long long)plan.a.n + 8191) / 8192;
+  long long e = room < 1 ? 1 : room;
+  if (e > want) e = want;
+  return e < 1 ? 1 : (int)e;
+}
+// the END of a batch of launches: the chain behind its last slot (`chain`: the caller's rule says there is one) with the translation
+// of the level bytes that the builds from `first_slot` on stored riding in the same launch; without a chain launch to ride in (chains
+// switched off) the translation is a launch of its own.  may_store == false: the caller knows that no build of the batch stored a byte
+inline void bfs_enqueue_tail(const bfs_launch_plan_t& plan, int slot, int first_slot, bool chain, bool may_store, standard_context_t& ctx) {
+  hipStream_t s = ctx.stream();
+  const int e = may_store ? bfs_translate_wgs(plan, ctx.num_cus - 1) : 0;
+  if (chain)
+    hipLaunchKernelGGL(k_bfs_chain_inplace, dim3(1 + e), dim3(1024), bfs_chain_lds_bytes(BFS_CHAIN_CAP_BIG), s, plan.a, bfs_slot_arg(slot), first_slot);
+  else if (e)
+    hipLaunchKernelGGL(k_bfs_translate, dim3(e), dim3(1024), 0, s, plan.a, first_slot);
 }
 inline void bfs_enqueue_mini(const bfs_launch_plan_t& plan, int slot, hipStream_t s) {
   hipLaunchKernelGGL(k_bfs_mini<1024>, dim3(BFS_MINI_WGS), dim3(1024), bfs_mini_lds_bytes(), s, plan.a, bfs_slot_arg(slot));
@@ -622,6 +657,7 @@ inline bool bfs_fused_plan_alt(bfs_fused_state_t& st, const bfs_launch_plan_t& p
   }
   a.ctrl = t.ctrl;
   a.slot_marks = t.slot_marks;
+  if (a.lvl8) a.lvl8 = t.lvl8;
   return true;
 }
 // The seam launches of a batch (see k_bfs_seam_mini_init): traversal A's tail -- its M launch in slot `sl_a` (plans with M launches)
@@ -636,6 +672,7 @@ inline void bfs_enqueue_seam(const bfs_fused_state_t& st, const bfs_launch_plan_
   init.prev_head = prev_head;
   init.src = src;
   init.head_words = head_words;
+  init.ninit = 0;
   const int want = grid_for(((long long)st.n + 3) / 4, 1024, 1 << 20);       // init workgroups of 1024 threads, four labels a thread
   if (plan_a.minis) {
     // one workgroup of this launch per CU (the M body's registers): the init role gets the CUs the M role leaves, so that the whole
@@ -645,13 +682,17 @@ inline void bfs_enqueue_seam(const bfs_fused_state_t& st, const bfs_launch_plan_
     if (ninit > want) ninit = want;
     hipLaunchKernelGGL(k_bfs_seam_mini_init, dim3(BFS_MINI_WGS + ninit), dim3(1024), bfs_mini_lds_bytes(), s, plan_a.a, bfs_slot_arg(sl_a),
                        plan_b.a, init);
-    hipLaunchKernelGGL(k_bfs_seam_chain_chain, dim3(2), dim3(1024), bfs_chain_lds_bytes(BFS_CHAIN_CAP_BIG), s, tail_a.a, bfs_slot_arg(sl_a + 1),
-                       plan_b.a, bfs_slot_arg(0));
+    // (A's translation role: the compute units the two chains leave)
+    hipLaunchKernelGGL(k_bfs_seam_chain_chain, dim3(2 + bfs_translate_wgs(tail_a, ctx.num_cus - 2)), dim3(1024), bfs_chain_lds_bytes(BFS_CHAIN_CAP_BIG), s,
+                       tail_a.a, bfs_slot_arg(sl_a + 1), plan_b.a, bfs_slot_arg(0));
   } else {
-    int ninit = ctx.num_cus - 1;                                              // (the chain's LDS: one workgroup per CU)
+    // (the chain's LDS: one workgroup per CU.  A's translation role and B's init move about the same bytes: half of the CUs each)
+    const int e = bfs_translate_wgs(tail_a, (ctx.num_cus - 1) / 2);
+    int ninit = ctx.num_cus - 1 - e;
     if (ninit < 16) ninit = 16;
     if (ninit > want) ninit = want;
-    hipLaunchKernelGGL(k_bfs_seam_chain_init, dim3(1 + ninit), dim3(1024), bfs_chain_lds_bytes(BFS_CHAIN_CAP_BIG), s, tail_a.a, bfs_slot_arg(sl_a),
+    init.ninit = ninit;
+    hipLaunchKernelGGL(k_bfs_seam_chain_init, dim3(1 + ninit + e), dim3(1024), bfs_chain_lds_bytes(BFS_CHAIN_CAP_BIG), s, tail_a.a, bfs_slot_arg(sl_a),
                        plan_b.a, init);
     bfs_enqueue_chain_inplace(plan_b, 0, s);
   }
@@ -810,7 +851,10 @@ inline void bfs_fused_run(bfs_fused_state_t& st, const int* row_offsets, const i
       if (timed_merged) MGX_HIP(hipEventRecord(st.wev[3 * i + 2], s));    // (timing mode 2: the slot's queue build too)
     }
     if (plan.minis && batch == 0) { bfs_enqueue_mini(plan, slot, s); ++slot; }                // (the mid-size level behind the peak)
-    if (a.chain_big_edges && (slot >= st.tail_from || plan.minis) && opt.tail_chain) chain_inplace(slot);    // (the stragglers: may end the traversal here)
+    // (the stragglers: may end the traversal here; beside them the translation of the level bytes this batch's builds stored -- none
+    //  when the batch began at level 254 or deeper, which the host knows from the last read-back: slot levels only grow)
+    bfs_enqueue_tail(plan, slot, first_slot, a.chain_big_edges && (slot >= st.tail_from || plan.minis) && opt.tail_chain,
+                     batch == 0 || st.host_ctrl->slot_level[first_slot & 3] < 254, ctx);
     if (batch_events) MGX_HIP(hipEventRecord(st.ev1, s));
     // one read-back per batch: the counters and the first 64 trace slots (the flag alone would cost the same trip)
     constexpr size_t head_bytes = offsetof(bfs_ctrl_t, trace) + 64 * sizeof(u64);
@@ -1020,7 +1064,7 @@ inline int bfs_fused_run_many(bfs_fused_state_t& st, const int* row_offsets, con
     if (overlap && i + 1 == lead && !st.alt) second_state();
     const bool seam_behind = i + 1 < count && state_of(i + 1) != me;          // (the next traversal's seam runs this one's tail)
     if (plan.minis) { if (!seam_behind) bfs_enqueue_mini(P, sl, s); ++sl; }
-    if (tail && !seam_behind) bfs_enqueue_chain_inplace(tails[me], sl, s);
+    if (!seam_behind) bfs_enqueue_tail(tails[me], sl, 0, tail, true, ctx);      // (with the translation of the traversal's level bytes)
     last_slots[(size_t)i] = sl;
     classes[(size_t)i] = cls;
   }

@@ -45,6 +45,7 @@ inline const env_switch_t* env_switches(int* count) {
     {"MGX_BFS_DEFER_REACH", "\"mul/div\": a level defers its hot marks while reached * mul < range * div"},
     {"MGX_BFS_DEFER_WORDS", "words of the bitmap prefix whose marks are deferred (default: all)"},
     {"MGX_BFS_BUILD_LIST", "1: the list-based queue build of round 1"},
+    {"MGX_BFS_LEVEL_BYTES", "0: under a layout the queue build scatters labels itself (no level bytes, no translation pass)"},
     {"MGX_BFS_SRC_PLAN", "0: no per-source launch plan"},
     {"MGX_BFS_LONG_MIN", "long-row threshold of the layout (entries)"},
     {"MGX_BFS_HOT_MIN_EDGES", "smallest level that copies the bitmap prefix to LDS (edges)"},
