@@ -54,6 +54,7 @@ typedef struct mgx_scc_s* mgx_scc_t;
 typedef struct mgx_lpa_s* mgx_lpa_t;
 typedef struct mgx_msbfs_s* mgx_msbfs_t;
 typedef struct mgx_rw_s* mgx_rw_t;
+typedef struct mgx_nsample_s* mgx_nsample_t;
 typedef struct mgx_louvain_s* mgx_louvain_t;
 typedef struct mgx_dbfs_s* mgx_dbfs_t;
 typedef struct mgx_dbfs2_s* mgx_dbfs2_t;
@@ -1061,6 +1062,65 @@ MGX_API int mgx_louvain_bins(mgx_louvain_t p, int64_t* out);
  * rows, applies, Qnum launches (device clock) and aggregation (host clock, waits included) */
 MGX_API int mgx_louvain_set_timing(mgx_louvain_t p, int on);
 MGX_API int mgx_louvain_phase_ms(mgx_louvain_t p, double* out);
+
+/* ---- neighbour sampling for GNN mini-batches (include/mgx/nsample_fused.hpp, include/gunrock/nsample/) ----
+ * Fan-out sampling in the GraphSAGE / NeighborLoader shape along out-entries, in original ids; an attached layout is ignored.  seeds
+ * is a host int32[count], duplicates allowed, NULL means every vertex (count is ignored); fanouts is a host int32[hops], every
+ * entry -1 (all of a row's entries) or 1 .. 64.
+ *   frontiers   V_0 is the ascending set of distinct seeds.  For h = 0 .. hops - 1 every v of V_h is sampled once; V_{h+1} is the
+ *               ascending set of the sampled destinations that are in none of V_0 .. V_h: a vertex is sampled at most once in a
+ *               run.  A vertex's local id is its place in V_0 | V_1 | ... | V_hops.
+ *   a row       v at hop h, d entries, k = fanouts[h], key = step_key(walker_key(seed, v), h) of the random walks' draws (above),
+ *               from the GLOBAL id: a vertex's sample depends on the graph, seed, h and v, never on who else is in the batch.
+ *               d == 0: nothing.  k == -1, or replace == 0 and d <= k: positions 0 .. d - 1 in the row's STORED order (a whole row).
+ *               replace != 0: k positions hi(draw(key, j) x d), j = 0 .. k - 1.  Otherwise Floyd's algorithm, exactly k draws, no
+ *               retries: for j = 0 .. k - 1, i = d - k + j, t = hi(draw(key, j) x (i + 1)), p_j = i when t is among p_0 .. p_{j-1}
+ *               (a collision), else t.  Slot j of the row holds p_j: insertion order, no sort.  Self-loops and duplicate entries
+ *               are entries like any other.
+ * Results: vertices int32[N] (local -> global), hop_offsets int32[hops + 2] (V_h = vertices[hop_offsets[h], hop_offsets[h + 1])),
+ * row_offsets int32[R + 1], R = hop_offsets[hops] (the sampled subgraph as a CSR over the local rows; {0} when hops == 0), cols
+ * int32[E] (local ids), entry_pos int32[E] (the index into the graph's col_indices / weights of every sampled entry), seed_local
+ * int32[count].
+ * hops outside [0, 16], a fan-out that is neither -1 nor in 1 .. 64, count < 0, a seed outside [0, n): MGX_E_INVALID before any
+ * device work, the message names the parameter.  The arrays are sized before the first launch by bounds: F_0 = min(n, count), E_h =
+ * F_h x k_h (clamped to m unless replace; k = -1: m), F_{h+1} = min(n, E_h); a bound of 2^31 or more is MGX_E_FRONTIER_OVERFLOW,
+ * before any device work as well.  They live on the handle and only grow: a repeat run of the same or a smaller shape allocates
+ * nothing.
+ * stats (may be NULL), int64[14]: [0] seeds, [1] distinct seeds, [2] hops, [3] vertices N, [4] rows R, [5] entries E, [6] rows
+ * without entries, [7] whole rows, [8] sampled rows, [9] draws, [10] collisions, [11] revisits (sampled entries whose destination
+ * had a local id before its hop's new vertices were numbered), [12] launches (fused: 5 hops + 4; operator path: operator calls),
+ * [13] host waits (fused: one for the seeds' upload when given, one for the totals).  Without vertices or without seeds a run
+ * does no device work: launches and waits are 0.  Every run starts afresh, on the context's stream.  A run that fails leaves no
+ * result: the getters return MGX_E_INVALID until a run succeeds. */
+MGX_API int mgx_nsample_create(mgx_graph_t g, mgx_nsample_t* out);
+MGX_API int mgx_nsample_free(mgx_nsample_t p);
+/* the fused path: per hop a launch that counts, one that samples (a group of lanes per row, membership by one ballot), one for
+ * the segments of long copied rows and two that rank the new vertices' bits; nothing is read back between the hops */
+MGX_API int mgx_nsample_run(mgx_nsample_t p, const int* seeds, int count, const int* fanouts, int hops, int replace, uint32_t seed,
+                            int64_t* stats);
+/* the operator path: a filter over the frontier, a lane per row, and a filter over all vertices for the next frontier; the same
+ * results, bit for bit */
+MGX_API int mgx_nsample_enact(mgx_nsample_t p, const int* seeds, int count, const int* fanouts, int hops, int replace, uint32_t seed,
+                              int64_t* stats);
+/* the last run's arrays to the host (sizes: stats [3], hops + 2, [4] + 1, [5], [5], [0]); the device pointers stay valid until the
+ * next run or free (NULL where the array is empty) */
+MGX_API int mgx_nsample_vertices(mgx_nsample_t p, int* host);
+MGX_API int mgx_nsample_hop_offsets(mgx_nsample_t p, int* host);
+MGX_API int mgx_nsample_row_offsets(mgx_nsample_t p, int* host);
+MGX_API int mgx_nsample_cols(mgx_nsample_t p, int* host);
+MGX_API int mgx_nsample_entry_pos(mgx_nsample_t p, int* host);
+MGX_API int mgx_nsample_seed_local(mgx_nsample_t p, int* host);
+MGX_API int mgx_nsample_vertices_device(mgx_nsample_t p, const int** d_vertices);
+MGX_API int mgx_nsample_row_offsets_device(mgx_nsample_t p, const int** d_row_offsets);
+MGX_API int mgx_nsample_cols_device(mgx_nsample_t p, const int** d_cols);
+MGX_API int mgx_nsample_entry_pos_device(mgx_nsample_t p, const int** d_entry_pos);
+/* int64[8]: [0] - [3] the rows without entries / a lane's / a wave's / segmented among the rows the last fused run copied in its
+ * hops with fan-out -1, [4] the segments of the latter, [5] - [7] MGX_NSAMPLE_SHORT_MAX, _WAVE_MAX and _SEG as read */
+MGX_API int mgx_nsample_bins(mgx_nsample_t p, int64_t* out);
+/* timing (measurement tools; off by default): mgx_nsample_phase_ms gives out[2] = ms of the last fused run's sampling launches
+ * and of its deduplication (marks, ranks, renumbering) */
+MGX_API int mgx_nsample_set_timing(mgx_nsample_t p, int on);
+MGX_API int mgx_nsample_phase_ms(mgx_nsample_t p, double* out);
 
 /* ---- segmented sort (mgpu::segmented_sort, lspar_enactor.hxx:85; mgx/segsort.hpp) ----
  * Sorts d_keys[0, count) (and d_vals with them; NULL: keys only) in place, stably, ascending or descending, within segments:

@@ -81,6 +81,10 @@ inline const env_switch_t* env_switches(int* count) {
     {"MGX_RW_SHORT_MAX", "the setup finds the maximum weight of rows of at most N entries a lane each (default 32)"},
     {"MGX_RW_WAVE_MAX", "longer rows of at most N entries take a wave each, the rest go out as (vertex, segment) items (default 1024)"},
     {"MGX_RW_SEG", "entries of a segmented row one wave takes (default 1024)"},
+    // ---- neighbour sampling (ns_opts_t::from_env: read once per handle; all three defaults are unmeasured guesses)
+    {"MGX_NSAMPLE_SHORT_MAX", "a hop that takes whole rows (fan-out -1) copies rows of at most N entries a lane each (default 32)"},
+    {"MGX_NSAMPLE_WAVE_MAX", "longer rows of at most N entries take a wave each, the rest go out as (row, segment) items (default 1024)"},
+    {"MGX_NSAMPLE_SEG", "entries of a segmented row one wave copies (default 1024)"},
     {"MGX_LOUVAIN_SHORT_MAX", "Louvain: vertices whose rows have at most N entries score their candidates a lane each, labels and weights in registers (default and at most 16)"},
     {"MGX_LOUVAIN_WAVE_MAX", "Louvain: longer rows of at most N entries take a wave each and a wave-private LDS table; the rest go out as (vertex, segment) items into a table in device memory (default 256, at most 512)"},
     {"MGX_LOUVAIN_SEG", "Louvain: entries of a long row one wave takes, a power of two in [64, 1024] (default 256)"},

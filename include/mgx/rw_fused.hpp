@@ -38,7 +38,7 @@
 //              (and its weight), then -- second order -- a branch-light binary search over prev's row.  Nothing overlaps inside
 //              a walker; the lever is waves in flight, so the kernels keep out of scratch (DESIGN 3.17 has their registers).
 // Not built: alias tables or an exact inverse-CDF fallback, more than one device, walkers re-sorted by vertex per
-// step, metapaths, sampling without replacement / k-hop fan-out.
+// step, metapaths.  (Sampling without replacement / k-hop fan-out: nsample_fused.hpp)
 #pragma once
 #include <algorithm>
 #include <cmath>

@@ -9,7 +9,9 @@ vertex id of v's strongly connected component, on the directed graph with its ge
 propagation (LpaProblem) with the modularity of any labelling (modularity) and bit-parallel multi-source BFS (MsBfsProblem: depths
 from 64 sources per pass over the graph; closeness, harmonic centrality and eccentricity of the sources) and random walks (RandomWalkProblem: uniform, weighted and node2vec
 walks with restarts, counter-based draws; paths, visit counts, Monte-Carlo personalised PageRank) and Louvain community detection
-(LouvainProblem: levels of modularity-raising moves and graph contraction in integer arithmetic; labels, dendrogram, modularity).
+(LouvainProblem: levels of modularity-raising moves and graph contraction in integer arithmetic; labels, dendrogram, modularity) and
+fan-out neighbour sampling for GNN mini-batches (NeighborSampleProblem: up to k_h out-neighbours per newly reached vertex and hop,
+without replacement, one renumbered subgraph).
 
 Layout: csrc/ (HIP sources of libmgx.so), _lib.py (ctypes binding of include/mgx.h),
 api.py (host mirror of the reference's data model), rmat.py (synthetic inputs, device-side).
@@ -17,7 +19,7 @@ Importing the package loads libmgx.so and raises ImportError if it has not been 
 """
 from ._lib import (LIB_PATH, MGX_BFS_DIRECTION_OPT, MGX_BFS_PUSH, MGX_E_FRONTIER_OVERFLOW, MGX_E_INVALID, MGX_LPA_LAZY, MGX_LPA_SYNC,
                    MGX_E_NEGATIVE_WEIGHT, MgxError, lib)
-from .api import (BcProblem, BfsProblem, CcProblem, ColorProblem, Context, Frontier, Graph, KcoreProblem, KtrussProblem, LouvainProblem, LpaProblem, LsparProblem, MsBfsProblem, MstProblem, PageRankProblem, PrProblem, RandomWalkProblem, SccProblem, SsspProblem, TcProblem, compact_i32,
+from .api import (BcProblem, BfsProblem, CcProblem, ColorProblem, Context, Frontier, Graph, KcoreProblem, KtrussProblem, LouvainProblem, LpaProblem, LsparProblem, MsBfsProblem, MstProblem, NeighborSampleProblem, PageRankProblem, PrProblem, RandomWalkProblem, SccProblem, SsspProblem, TcProblem, compact_i32,
                   lbs_expand_debug, load_csr_cache, load_mtx, rmat_edges, save_csr_cache, scan_exclusive_i32, scan_frontier_degrees,
                   modularity, segmented_sort, segreduce)
 

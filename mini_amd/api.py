@@ -1529,6 +1529,126 @@ class RandomWalkProblem(_Timed):
             self._h = None
 
 
+class NeighborSampleProblem(_Timed):
+    """Fan-out neighbour sampling for GNN mini-batches, the GraphSAGE / NeighborLoader shape: from a batch of seeds up
+    to fanouts[h] out-neighbours of every newly reached vertex at hop h, the result one renumbered subgraph.  run() is the fused
+    path (5 H + 4 launches, nothing read back between the hops), enact() the operator path; the getters describe the last run of
+    either, and both give the same results bit for bit.  The fine print of the definition:
+      * V_0 is the ascending set of distinct seeds, V_{h+1} the ascending set of hop h's sampled destinations that are in none of
+        V_0 .. V_h; a vertex's local id is its place in V_0 | V_1 | ... | V_H.  A vertex is sampled at most once in a run, at the
+        hop that reached it first;
+      * a pick is a position in the row's STORED order: two uploads of one graph with differently ordered rows sample differently;
+      * a row's key comes from (seed, the vertex's GLOBAL id, the hop): its sample does not depend on who else is in the batch;
+      * a row of d entries at fan-out k: all of them, in stored order, when k == -1 or d <= k (replace=False); with replace=True k
+        positions drawn independently; otherwise Floyd's algorithm, exactly k draws and no retries: t uniform in [0, d - k + j] for
+        j = 0 .. k - 1, and d - k + j instead when t was picked before (a collision).  The picks stay in insertion order;
+      * self-loops and duplicate entries are entries like any other; weights do not bias the sample (gather them with entry_pos())."""
+
+    _C = "mgx_nsample"
+    KEYS = ("seeds", "unique_seeds", "hops", "vertices", "rows", "edges", "empty_rows", "whole_rows", "sampled_rows", "draws", "collisions",
+            "revisits", "launches", "host_waits")
+    PHASES = ("sample", "dedup")
+    BINS = ("none", "short", "wave", "long", "segments", "short_max", "wave_max", "seg")
+
+    def __init__(self, graph):
+        h = C.c_void_p()
+        check(lib.mgx_nsample_create(graph._h, C.byref(h)))
+        self.graph, self._h = graph, h
+        self._last = None
+
+    def _go(self, fn, seeds, fanouts, replace, seed):
+        st = (C.c_int64 * 14)()
+        if seeds is None:
+            src, ptr, count = None, None, 0
+        else:
+            src = _np_i32(np.asarray(seeds))
+            ptr, count = _ptr(src), len(src)
+            if count == 0:
+                src = np.zeros(1, dtype=np.int32)                # (NULL would mean every vertex)
+                ptr = _ptr(src)
+        fo = _np_i32(np.asarray(list(fanouts) + [0]))            # (never an empty array)
+        self._last = None
+        check(fn(self._h, ptr, count, _ptr(fo), len(fo) - 1, int(bool(replace)), int(seed) & 0xFFFFFFFF, st))
+        self._last = dict(zip(self.KEYS, (int(x) for x in st)))
+        return dict(self._last)
+
+    def run(self, seeds=None, fanouts=(15, 10, 5), replace=False, seed=1):
+        """fused path from `seeds` (None: every vertex) -> the stats dict of KEYS"""
+        return self._go(lib.mgx_nsample_run, seeds, fanouts, replace, seed)
+
+    def enact(self, seeds=None, fanouts=(15, 10, 5), replace=False, seed=1):
+        """operator path (a filter over the frontier per hop, a filter over all vertices for the next one); the same results"""
+        return self._go(lib.mgx_nsample_enact, seeds, fanouts, replace, seed)
+
+    def _get(self, fn, count):
+        out = np.zeros(max(count, 1), dtype=np.int32)
+        check(fn(self._h, _ptr(out)))
+        return out[:count]
+
+    def _size(self, key, extra=0):
+        return (self._last[key] + extra) if self._last else 1
+
+    def vertices(self):
+        """int32[N]: local id -> global id"""
+        return self._get(lib.mgx_nsample_vertices, self._size("vertices"))
+
+    def hop_offsets(self):
+        """int32[H + 2]: V_h = vertices()[hop_offsets[h]:hop_offsets[h + 1]]"""
+        return self._get(lib.mgx_nsample_hop_offsets, self._size("hops", 2))
+
+    def row_offsets(self):
+        """int32[R + 1]: the sampled subgraph as a CSR over the local rows 0 .. R - 1, R = hop_offsets[H]"""
+        return self._get(lib.mgx_nsample_row_offsets, self._size("rows", 1))
+
+    def cols(self):
+        """int32[E]: the sampled entries' destinations, local ids"""
+        return self._get(lib.mgx_nsample_cols, self._size("edges"))
+
+    def entry_pos(self):
+        """int32[E]: the index into the graph's col_indices / weights of every sampled entry"""
+        return self._get(lib.mgx_nsample_entry_pos, self._size("edges"))
+
+    def seed_local(self):
+        """int32[len(seeds)]: the local id of every seed, duplicates included"""
+        return self._get(lib.mgx_nsample_seed_local, self._size("seeds"))
+
+    def block(self, h):
+        """(row_offsets, cols) of hop h's rows: row_offsets starts at 0, cols are local ids"""
+        off, ro = self.hop_offsets(), self.row_offsets()
+        if not 0 <= h < len(off) - 2:
+            raise IndexError("hop %d of %d" % (h, len(off) - 2))
+        part = ro[off[h]:off[h + 1] + 1]
+        return part - part[0], self.cols()[part[0]:part[-1]]
+
+    def _device(self, fn):
+        d = C.c_void_p()
+        check(fn(self._h, C.byref(d)))
+        return d.value
+
+    def vertices_device_ptr(self):
+        return self._device(lib.mgx_nsample_vertices_device)
+
+    def row_offsets_device_ptr(self):
+        return self._device(lib.mgx_nsample_row_offsets_device)
+
+    def cols_device_ptr(self):
+        return self._device(lib.mgx_nsample_cols_device)
+
+    def entry_pos_device_ptr(self):
+        return self._device(lib.mgx_nsample_entry_pos_device)
+
+    def bins(self):
+        """rows per copy body of the last fused run's hops with fan-out -1, their segments, the switches as read"""
+        out = (C.c_int64 * 8)()
+        check(lib.mgx_nsample_bins(self._h, out))
+        return dict(zip(self.BINS, (int(x) for x in out)))
+
+    def close(self):
+        if self._h:
+            lib.mgx_nsample_free(self._h)
+            self._h = None
+
+
 def modularity(graph, labels, symmetric=False):
     """Modularity of any labelling (labels in [0, n): a numpy array, a torch tensor on the device or a device address) ->
     (Q, S_in, S_sq, W); Q = S_in / W - S_sq / W^2 in double from the three integers the library returns (0.0 when W == 0)."""

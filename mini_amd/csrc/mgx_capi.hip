@@ -24,6 +24,7 @@
 #include "gunrock/mst/mst_enactor.hxx"
 #include "gunrock/pagerank/pagerank_enactor.hxx"
 #include "gunrock/pr/pr_enactor.hxx"
+#include "gunrock/nsample/nsample_enactor.hxx"
 #include "gunrock/rw/rw_enactor.hxx"
 #include "gunrock/kcore/kcore_enactor.hxx"
 #include "gunrock/sssp/sssp_enactor.hxx"
@@ -45,6 +46,7 @@
 #include "mgx/env.hpp"
 #include "mgx/sssp_dist.hpp"
 #include "mgx/rmat.hpp"
+#include "mgx/nsample_fused.hpp"
 #include "mgx/rw_fused.hpp"
 #include "mgx/sssp_fused.hpp"
 #include "mgx/sssp_preds.hpp"
@@ -217,6 +219,15 @@ struct mgx_rw_s : mgx_problem_s {
   int last = 0;                                                   // 0: no run yet; 1: the fused path's results; 2: the operator path's
   long long walkers = 0, length = 0;                              // of the last run
   bool kept_paths = false, kept_visits = false;
+  bool timing = false;
+};
+
+struct mgx_nsample_s : mgx_problem_s {
+  std::unique_ptr<mgx::ns_fused_state_t> fused;                   // lazily: the fused path's bitmaps, map and results
+  std::unique_ptr<nsample::nsample_state_t> op_state;             // lazily: the operator path's arrays
+  std::shared_ptr<nsample::nsample_problem_t> p;
+  std::unique_ptr<nsample::nsample_enactor_t> e;
+  int last = 0;                                                   // 0: no run yet; 1: the fused path's results; 2: the operator path's
   bool timing = false;
 };
 
@@ -3739,6 +3750,136 @@ int mgx_rw_phase_ms(mgx_rw_t p, double* out) {
   MGX_CATCH
 }
 
+
+// ---- neighbour sampling for GNN mini-batches ---------------------------------------
+// a run's arguments, checked before any device work (the parameters first: their messages do not need a handle)
+static mgx::ns_request_t nsample_check(mgx_nsample_t p, const int* seeds, int count, const int* fanouts, int hops, int replace, uint32_t seed,
+                                       mgx::ns_bounds_t* bounds, const char* who) {
+  const std::string w(who);
+  MGX_REQUIRE(hops >= 0 && hops <= mgx::NS_MAX_HOPS, w + ": hops must be in [0, 16]");
+  MGX_REQUIRE(fanouts || hops == 0, w + ": fanouts is NULL");
+  for (int h = 0; h < hops; ++h)
+    MGX_REQUIRE(fanouts[h] == -1 || (fanouts[h] >= 1 && fanouts[h] <= mgx::NS_MAX_FANOUT), w + ": every one of fanouts must be -1 or in 1 .. 64");
+  MGX_REQUIRE(count >= 0 || !seeds, w + ": count must not be negative");
+  MGX_REQUIRE(p, "NULL argument");
+  const int n = p->graph().num_nodes;
+  mgx::ns_request_t r;
+  r.h_seeds = seeds;
+  r.count = seeds ? count : n;
+  if (seeds) for (int i = 0; i < count; ++i) MGX_REQUIRE(seeds[i] >= 0 && seeds[i] < n, w + ": seed out of range");
+  r.hops = hops;
+  for (int h = 0; h < hops; ++h) r.fanouts[h] = fanouts[h];
+  r.replace = replace != 0; r.seed = seed;
+  *bounds = mgx::ns_bounds(n, (long long)p->graph().num_edges, r, mgx::ns_opts_t::from_env().cuts);
+  if (bounds->overflow()) throw mgx::mgx_error(MGX_E_FRONTIER_OVERFLOW, w + ": a capacity bound of 2^31 or more (seeds x fanouts)");
+  return r;
+}
+static const mgx::ns_results_t& nsample_results(mgx_nsample_t p, const char* who) {
+  MGX_REQUIRE(p, "NULL argument");
+  require_run(p->last != 0, who);
+  return p->last == 1 ? p->fused->res : p->op_state->res;
+}
+int mgx_nsample_create(mgx_graph_t g, mgx_nsample_t* out) { return create_handle(g, out); }
+int mgx_nsample_free(mgx_nsample_t p) { return free_handle(p); }
+int mgx_nsample_run(mgx_nsample_t p, const int* seeds, int count, const int* fanouts, int hops, int replace, uint32_t seed, int64_t* stats) {
+  MGX_TRY
+  if (p) p->last = 0;                                        // (a run that is refused leaves nothing to the getters)
+  mgx::ns_bounds_t b;
+  const mgx::ns_request_t r = nsample_check(p, seeds, count, fanouts, hops, replace, seed, &b, "mgx_nsample_run");
+  auto [ctx, g] = enter(p);
+  if (!p->fused) p->fused.reset(new mgx::ns_fused_state_t(g.num_nodes, g.num_edges, ctx));
+  p->fused->timing = p->timing;
+  const std::vector<long long> st = p->fused->run(g.d_row_offsets.data(), g.d_col_indices.data(), r, b, ctx);
+  p->last = 1;
+  put_stats(stats, mgx::NS_STATS, st);
+  MGX_CATCH
+}
+int mgx_nsample_enact(mgx_nsample_t p, const int* seeds, int count, const int* fanouts, int hops, int replace, uint32_t seed, int64_t* stats) {
+  MGX_TRY
+  if (p) p->last = 0;
+  mgx::ns_bounds_t b;
+  const mgx::ns_request_t r = nsample_check(p, seeds, count, fanouts, hops, replace, seed, &b, "mgx_nsample_enact");
+  auto [ctx, g] = enter(p);
+  const int n = g.num_nodes;
+  if (!p->op_state) p->op_state.reset(new nsample::nsample_state_t());
+  nsample::nsample_state_t& os = *p->op_state;
+  std::vector<long long> st = {r.count, 0, r.hops, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (n > 0 && r.count > 0) {
+    const hipStream_t s = ctx.stream();
+    long long waits = 0;
+    os.ensure(r, b, n, ctx);
+    if (seeds) { MGX_HIP(mgx::htod(os.res.d_seeds.data(), seeds, (size_t)r.count, s)); ++waits; }
+    const nsample::nsample_problem_t::data_slice_t slice = os.slice(g.d_row_offsets.data(), g.d_col_indices.data(), r);
+    if (!p->p) p->p = std::make_shared<nsample::nsample_problem_t>(p->g->g, slice, ctx);
+    else MGX_HIP(mgx::htod(p->p->d_data_slice.data(), &slice, 1, s));
+    ++waits;
+    if (!p->e) p->e.reset(new nsample::nsample_enactor_t(ctx, n));
+    p->e->enact(p->p, os, slice, r, n, ctx);
+    const unsigned long long* c = p->e->counters;
+    st = {r.count, os.res.hop_offsets[1], r.hops, os.res.count_vertices(), os.res.count_rows(), os.res.edges, (long long)c[mgx::NS_C_EMPTY],
+          (long long)c[mgx::NS_C_WHOLE], (long long)c[mgx::NS_C_SAMPLED], (long long)c[mgx::NS_C_DRAWS], (long long)c[mgx::NS_C_COLLISIONS],
+          (long long)c[mgx::NS_C_REVISITS], p->e->calls, waits + p->e->waits};
+  } else {
+    os.res.nothing(r);
+  }
+  p->last = 2;
+  put_stats(stats, mgx::NS_STATS, st);
+  MGX_CATCH
+}
+// an array of the last run to the host; NULL skips it.  A run without device work has no array but row_offsets = {0}.
+static int nsample_get(mgx_nsample_t p, int* host, const char* who, mem_t<int> mgx::ns_results_t::*arr, int which) {
+  MGX_TRY
+  const mgx::ns_results_t& res = nsample_results(p, who);
+  if (!host) return MGX_OK;
+  const size_t count = which == 0 ? (size_t)res.count_vertices() : which == 1 ? (size_t)res.count_rows() + 1 : which == 2 ? (size_t)res.edges : (size_t)res.seeds;
+  if (!res.device) { if (which == 1) host[0] = 0; return MGX_OK; }
+  read_back(p, host, (const int*)(res.*arr).data(), count);
+  MGX_CATCH
+}
+static int nsample_get_device(mgx_nsample_t p, const int** out, const char* who, mem_t<int> mgx::ns_results_t::*arr) {
+  MGX_TRY
+  const mgx::ns_results_t& res = nsample_results(p, who);
+  MGX_REQUIRE(out, "NULL argument");
+  *out = res.device ? (res.*arr).data() : nullptr;
+  MGX_CATCH
+}
+int mgx_nsample_vertices(mgx_nsample_t p, int* host) { return nsample_get(p, host, "mgx_nsample_vertices", &mgx::ns_results_t::vertices, 0); }
+int mgx_nsample_row_offsets(mgx_nsample_t p, int* host) { return nsample_get(p, host, "mgx_nsample_row_offsets", &mgx::ns_results_t::row_offsets, 1); }
+int mgx_nsample_cols(mgx_nsample_t p, int* host) { return nsample_get(p, host, "mgx_nsample_cols", &mgx::ns_results_t::cols, 2); }
+int mgx_nsample_entry_pos(mgx_nsample_t p, int* host) { return nsample_get(p, host, "mgx_nsample_entry_pos", &mgx::ns_results_t::entry_pos, 2); }
+int mgx_nsample_seed_local(mgx_nsample_t p, int* host) { return nsample_get(p, host, "mgx_nsample_seed_local", &mgx::ns_results_t::seed_local, 3); }
+int mgx_nsample_hop_offsets(mgx_nsample_t p, int* host) {
+  MGX_TRY
+  const mgx::ns_results_t& res = nsample_results(p, "mgx_nsample_hop_offsets");
+  if (host) std::copy(res.hop_offsets.begin(), res.hop_offsets.end(), host);
+  MGX_CATCH
+}
+int mgx_nsample_vertices_device(mgx_nsample_t p, const int** out) { return nsample_get_device(p, out, "mgx_nsample_vertices_device", &mgx::ns_results_t::vertices); }
+int mgx_nsample_row_offsets_device(mgx_nsample_t p, const int** out) { return nsample_get_device(p, out, "mgx_nsample_row_offsets_device", &mgx::ns_results_t::row_offsets); }
+int mgx_nsample_cols_device(mgx_nsample_t p, const int** out) { return nsample_get_device(p, out, "mgx_nsample_cols_device", &mgx::ns_results_t::cols); }
+int mgx_nsample_entry_pos_device(mgx_nsample_t p, const int** out) { return nsample_get_device(p, out, "mgx_nsample_entry_pos_device", &mgx::ns_results_t::entry_pos); }
+int mgx_nsample_bins(mgx_nsample_t p, int64_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->last == 1, "mgx_nsample_bins");
+  const mgx::ns_fused_state_t& f = *p->fused;
+  for (int i = 0; i < mgx::NS_BINS; ++i) out[i] = f.bins[i];
+  out[5] = f.opts.cuts.short_max; out[6] = f.opts.cuts.wave_max; out[7] = f.opts.cuts.seg;
+  MGX_CATCH
+}
+int mgx_nsample_set_timing(mgx_nsample_t p, int on) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  p->timing = on != 0;
+  MGX_CATCH
+}
+int mgx_nsample_phase_ms(mgx_nsample_t p, double* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->last == 1, "mgx_nsample_phase_ms");
+  out[0] = p->fused->phase_ms[0]; out[1] = p->fused->phase_ms[1];
+  MGX_CATCH
+}
 
 // ---- Louvain community detection ---------------------------------------------------
 static void louvain_check_args(const graph_device_t& g, int symmetric, int max_iter, int max_levels, double tol, const char* who) {
