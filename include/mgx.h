@@ -1122,6 +1122,61 @@ MGX_API int mgx_nsample_bins(mgx_nsample_t p, int64_t* out);
 MGX_API int mgx_nsample_set_timing(mgx_nsample_t p, int on);
 MGX_API int mgx_nsample_phase_ms(mgx_nsample_t p, double* out);
 
+/* ---- vertex similarity for link prediction (include/mgx/sim_fused.hpp, include/gunrock/sim/) ----
+ * How alike are two vertices' neighbourhoods, exactly, for arbitrary pairs.  The graph is the underlying simple undirected graph of
+ * the triangle count: N(v) = the distinct neighbours of v other than v, original ids, d(v) = |N(v)|; symmetric as in mgx_tc_run.
+ * A run takes `pairs` pairs (h_u[p], h_v[p]), host int32; both NULL selects EDGES MODE: the pairs are the simple graph's m_dag edges
+ * in the order of mgx_ktruss_edges (`pairs` is ignored).  With c = |N(u) & N(v)|, common[p] = c (int32) always, and score[p]
+ * (double) by `measure`:
+ *   MGX_SIM_COMMON    c
+ *   MGX_SIM_JACCARD   c / (d(u) + d(v) - c)        MGX_SIM_OVERLAP   c / min(d(u), d(v))
+ *   MGX_SIM_SORENSEN  2 c / (d(u) + d(v))         MGX_SIM_COSINE    c / sqrt(d(u) d(v))          (each 0 where its denominator is 0)
+ *   MGX_SIM_WEIGHTED  the sum of h_x[w] over the common neighbours w; h_x is a host double[n], required for this measure and read
+ *                     by no other (Adamic-Adar: x = 1 / ln d, resource allocation: x = 1 / d; the caller builds x from
+ *                     mgx_sim_degrees, no logarithm runs on the device)
+ * u == v is legal (c = d(u)), duplicate pairs are legal, pairs == 0 is a valid run.  An id outside [0, n) is found on the device by
+ * the classifying launch: the run returns MGX_E_INVALID and leaves no result.  The four ratios are one round-to-nearest division
+ * of exact integers; the weighted sum uses no float atomics and a fixed reduction order: two runs are bit-equal, and (u, v) and
+ * (v, u) score bit-equal (of two equally long rows the smaller id's plays the shorter).
+ * stats (may be NULL), int64[8]: [0] pairs, [1] the sum of c, [2] pairs with c > 0, [3] adjacency entries (2 m_dag), [4] the longest
+ * simple row, [5] 1 if this run built the adjacency, [6] host waits, [7] launches (mgx_sim_enact: two per operator call).  The
+ * adjacency is built once per `symmetric` value and kept on the handle; a repeat run waits once, for its stats, and allocates
+ * nothing while pairs does not exceed the largest seen. */
+#define MGX_SIM_COMMON 0
+#define MGX_SIM_JACCARD 1
+#define MGX_SIM_OVERLAP 2
+#define MGX_SIM_SORENSEN 3
+#define MGX_SIM_COSINE 4
+#define MGX_SIM_WEIGHTED 5
+typedef struct mgx_sim_s* mgx_sim_t;
+MGX_API int mgx_sim_create(mgx_graph_t g, mgx_sim_t* out);
+MGX_API int mgx_sim_free(mgx_sim_t p);
+/* builds the adjacency of `symmetric` unless the handle has it, so that mgx_sim_degrees can be read before a run */
+MGX_API int mgx_sim_prepare(mgx_sim_t p, int symmetric);
+/* the fused path: one classifying launch, four pair kernels by row lengths (a lane, a group of 16 lanes, a wave's LDS stage, a
+ * workgroup's), one scoring launch; nothing is read back between them */
+MGX_API int mgx_sim_run(mgx_sim_t p, int symmetric, const int* h_u, const int* h_v, int pairs, int measure, const double* h_x, int64_t* stats);
+/* the operator path: one filter over the pair indices, a two-pointer merge per thread; the same results (WEIGHTED: within the
+ * summation bound, its order is the merge's) */
+MGX_API int mgx_sim_enact(mgx_sim_t p, int symmetric, const int* h_u, const int* h_v, int pairs, int measure, const double* h_x, int64_t* stats);
+/* the last run's results to the host (stats [0] entries each); the device pointers stay valid until the next run or free */
+MGX_API int mgx_sim_common(mgx_sim_t p, int* host);
+MGX_API int mgx_sim_scores(mgx_sim_t p, double* host);
+MGX_API int mgx_sim_common_device(mgx_sim_t p, const int** d_common);
+MGX_API int mgx_sim_scores_device(mgx_sim_t p, const double** d_scores);
+/* the last run's pairs (edges mode: the edges it generated); either may be NULL */
+MGX_API int mgx_sim_pairs(mgx_sim_t p, int* h_u, int* h_v);
+/* d(v) of the n vertices, of the adjacency the handle prepared or ran on last */
+MGX_API int mgx_sim_degrees(mgx_sim_t p, int* host);
+/* int64[10] of the last fused run: [0] - [4] pairs without a possible common neighbour (a row is empty) / a lane's / a group's / a
+ * wave's / a workgroup's, [5] - [8] MGX_SIM_SHORT_MAX, _PROBE_RATIO, _WAVE_MAX and _STAGE as read, [9] the adjacency entries the
+ * pair kernels loaded */
+MGX_API int mgx_sim_bins(mgx_sim_t p, int64_t* out);
+/* timing (measurement tools; off by default): mgx_sim_phase_ms gives out[3] = ms of the last fused run's build, classifying
+ * launch and pair kernels (the scoring launch with them) */
+MGX_API int mgx_sim_set_timing(mgx_sim_t p, int on);
+MGX_API int mgx_sim_phase_ms(mgx_sim_t p, double* out);
+
 /* ---- segmented sort (mgpu::segmented_sort, lspar_enactor.hxx:85; mgx/segsort.hpp) ----
  * Sorts d_keys[0, count) (and d_vals with them; NULL: keys only) in place, stably, ascending or descending, within segments:
  * d_segments holds num_segments heads, ascending, duplicates allowed; whatever lies before the first head is a segment too,

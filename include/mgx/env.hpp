@@ -85,6 +85,11 @@ inline const env_switch_t* env_switches(int* count) {
     {"MGX_NSAMPLE_SHORT_MAX", "a hop that takes whole rows (fan-out -1) copies rows of at most N entries a lane each (default 32)"},
     {"MGX_NSAMPLE_WAVE_MAX", "longer rows of at most N entries take a wave each, the rest go out as (row, segment) items (default 1024)"},
     {"MGX_NSAMPLE_SEG", "entries of a segmented row one wave copies (default 1024)"},
+    // ---- vertex similarity (sim_opts_t::from_env: read once per handle; short_max and wave_max are unmeasured guesses)
+    {"MGX_SIM_SHORT_MAX", "pairs whose shorter adjacency row has at most N entries take a lane each: every entry searched in the longer row (default 16)"},
+    {"MGX_SIM_PROBE_RATIO", "longer short rows against rows of at least N times their length take a group of 16 lanes searching the long row in global memory; the rest are staged (default 8: measured at rows of 256)"},
+    {"MGX_SIM_WAVE_MAX", "staged pairs whose shorter row has at most N entries take a wave and its LDS stage, the rest a workgroup (default 512)"},
+    {"MGX_SIM_STAGE", "entries of an LDS stage of the shorter row; a longer one is staged in chunks against slices of the long row (default and at most 4096; a wave's: 512)"},
     {"MGX_LOUVAIN_SHORT_MAX", "Louvain: vertices whose rows have at most N entries score their candidates a lane each, labels and weights in registers (default and at most 16)"},
     {"MGX_LOUVAIN_WAVE_MAX", "Louvain: longer rows of at most N entries take a wave each and a wave-private LDS table; the rest go out as (vertex, segment) items into a table in device memory (default 256, at most 512)"},
     {"MGX_LOUVAIN_SEG", "Louvain: entries of a long row one wave takes, a power of two in [64, 1024] (default 256)"},

@@ -11,15 +11,17 @@ from 64 sources per pass over the graph; closeness, harmonic centrality and ecce
 walks with restarts, counter-based draws; paths, visit counts, Monte-Carlo personalised PageRank) and Louvain community detection
 (LouvainProblem: levels of modularity-raising moves and graph contraction in integer arithmetic; labels, dendrogram, modularity) and
 fan-out neighbour sampling for GNN mini-batches (NeighborSampleProblem: up to k_h out-neighbours per newly reached vertex and hop,
-without replacement, one renumbered subgraph).
+without replacement, one renumbered subgraph) and vertex similarity for link prediction (SimilarityProblem: the common neighbours of
+arbitrary vertex pairs or of every edge, exactly; Jaccard, overlap, Sorensen, cosine, Adamic-Adar, resource allocation).
 
 Layout: csrc/ (HIP sources of libmgx.so), _lib.py (ctypes binding of include/mgx.h),
 api.py (host mirror of the reference's data model), rmat.py (synthetic inputs, device-side).
 Importing the package loads libmgx.so and raises ImportError if it has not been built.
 """
 from ._lib import (LIB_PATH, MGX_BFS_DIRECTION_OPT, MGX_BFS_PUSH, MGX_E_FRONTIER_OVERFLOW, MGX_E_INVALID, MGX_LPA_LAZY, MGX_LPA_SYNC,
+                   MGX_SIM_COMMON, MGX_SIM_COSINE, MGX_SIM_JACCARD, MGX_SIM_OVERLAP, MGX_SIM_SORENSEN, MGX_SIM_WEIGHTED,
                    MGX_E_NEGATIVE_WEIGHT, MgxError, lib)
-from .api import (BcProblem, BfsProblem, CcProblem, ColorProblem, Context, Frontier, Graph, KcoreProblem, KtrussProblem, LouvainProblem, LpaProblem, LsparProblem, MsBfsProblem, MstProblem, NeighborSampleProblem, PageRankProblem, PrProblem, RandomWalkProblem, SccProblem, SsspProblem, TcProblem, compact_i32,
+from .api import (BcProblem, BfsProblem, CcProblem, ColorProblem, Context, Frontier, Graph, KcoreProblem, KtrussProblem, LouvainProblem, LpaProblem, LsparProblem, MsBfsProblem, MstProblem, NeighborSampleProblem, PageRankProblem, PrProblem, RandomWalkProblem, SccProblem, SimilarityProblem, SsspProblem, TcProblem, compact_i32,
                   lbs_expand_debug, load_csr_cache, load_mtx, rmat_edges, save_csr_cache, scan_exclusive_i32, scan_frontier_degrees,
                   modularity, segmented_sort, segreduce)
 

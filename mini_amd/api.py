@@ -1649,6 +1649,142 @@ class NeighborSampleProblem(_Timed):
             self._h = None
 
 
+class SimilarityProblem(_Timed):
+    """Vertex similarity for link prediction: how alike are two vertices' neighbourhoods, exactly, for arbitrary pairs
+    or for every edge.  The graph is the underlying simple undirected graph of the triangle count: N(v) = the distinct neighbours of
+    v other than v, d(v) = |N(v)|, original ids; symmetric as in TcProblem.run.  run() is the fused path (one classifying launch,
+    pair kernels by row lengths, one scoring launch), enact() the operator path (one filter, a merge per thread); the getters
+    describe the last run of either.  With c = |N(u) & N(v)|:
+      common   c                          jaccard  c / (d(u) + d(v) - c)       overlap  c / min(d(u), d(v))
+      sorensen 2 c / (d(u) + d(v))        cosine   c / sqrt(d(u) d(v))         (each 0 where its denominator is 0)
+      weighted the sum of weights[w] over the common neighbours w: weights="adamic_adar" is 1 / ln d (0 where d < 2),
+               "resource_allocation" 1 / d (0 where d == 0), built here with numpy from degrees(); or any float64[n]
+    pairs=None is edges mode: the pairs are the simple graph's edges in the order of KtrussProblem.edges().  u == v and duplicate
+    pairs are legal; an id outside [0, n) raises MgxError(MGX_E_INVALID).  The ratios are bit-equal to numpy's division; the weighted
+    sum uses a fixed order (two runs are bit-equal) and score(u, v) == score(v, u) bit for bit."""
+
+    _C = "mgx_sim"
+    KEYS = ("pairs", "common", "positive", "entries", "longest_row", "built", "host_waits", "launches")
+    MEASURES = {"common": _lib.MGX_SIM_COMMON, "jaccard": _lib.MGX_SIM_JACCARD, "overlap": _lib.MGX_SIM_OVERLAP,
+                "sorensen": _lib.MGX_SIM_SORENSEN, "cosine": _lib.MGX_SIM_COSINE, "weighted": _lib.MGX_SIM_WEIGHTED}
+    PHASES = ("build", "classify", "pairs")
+    BINS = ("none", "lane", "probe", "wave", "block", "short_max", "probe_ratio", "wave_max", "stage", "entries_read")
+
+    def __init__(self, graph):
+        h = C.c_void_p()
+        check(lib.mgx_sim_create(graph._h, C.byref(h)))
+        self.graph, self._h = graph, h
+        self._pairs = None
+
+    def degrees(self, symmetric=True):
+        """int32[n]: d(v) of the simple graph (builds the adjacency of `symmetric` when the handle does not have it)"""
+        check(lib.mgx_sim_prepare(self._h, int(bool(symmetric))))
+        n = self.graph.num_nodes
+        out = np.zeros(max(n, 1), dtype=np.int32)
+        check(lib.mgx_sim_degrees(self._h, _ptr(out)))
+        return out[:n]
+
+    def weights(self, kind, symmetric=True):
+        """float64[n] for measure="weighted": "adamic_adar" 1 / ln d (0 where d < 2), "resource_allocation" 1 / d (0 where d == 0)"""
+        d = self.degrees(symmetric).astype(np.float64)
+        x = np.zeros(len(d), dtype=np.float64)
+        if kind == "adamic_adar":
+            ok = d >= 2
+            x[ok] = 1.0 / np.log(d[ok])
+        elif kind == "resource_allocation":
+            ok = d > 0
+            x[ok] = 1.0 / d[ok]
+        else:
+            raise ValueError("weights: 'adamic_adar', 'resource_allocation' or an array of n doubles")
+        return x
+
+    def _go(self, fn, pairs, measure, weights, symmetric):
+        st = (C.c_int64 * 8)()
+        if weights is not None:
+            measure = "weighted"                                 # (weights given: the measure is their sum over the common neighbours)
+        code = self.MEASURES[measure] if isinstance(measure, str) else int(measure)
+        x = None
+        if code == _lib.MGX_SIM_WEIGHTED:
+            if weights is None:
+                raise ValueError("measure 'weighted' needs weights")
+            x = self.weights(weights, symmetric) if isinstance(weights, str) else np.ascontiguousarray(weights, dtype=np.float64)
+            if len(x) != self.graph.num_nodes:
+                raise ValueError("weights: %d values for %d vertices" % (len(x), self.graph.num_nodes))
+            if len(x) == 0:
+                x = np.zeros(1, dtype=np.float64)
+        if pairs is None:
+            u = v = None
+            pu = pv = None
+            count = 0
+        else:
+            pr = np.asarray(pairs).reshape(-1, 2)
+            u, v = _np_i32(pr[:, 0]), _np_i32(pr[:, 1])
+            count = len(u)
+            if count == 0:
+                u = v = np.zeros(1, dtype=np.int32)              # (NULL would mean edges mode)
+            pu, pv = _ptr(u), _ptr(v)
+        self._pairs = None
+        check(fn(self._h, int(bool(symmetric)), pu, pv, count, code, None if x is None else _ptr(x), st))
+        out = dict(zip(self.KEYS, (int(s) for s in st)))
+        self._pairs = out["pairs"]
+        return out
+
+    def run(self, pairs=None, measure="jaccard", weights=None, symmetric=True):
+        """fused path over `pairs` (anything that reshapes to (P, 2); None: every edge) -> the stats dict of KEYS"""
+        return self._go(lib.mgx_sim_run, pairs, measure, weights, symmetric)
+
+    def enact(self, pairs=None, measure="jaccard", weights=None, symmetric=True):
+        """operator path (one filter over the pair indices, a two-pointer merge per thread); the same results and stats"""
+        return self._go(lib.mgx_sim_enact, pairs, measure, weights, symmetric)
+
+    def _count(self):
+        if self._pairs is None:
+            check(lib.mgx_sim_common(self._h, None))             # raises: no run yet
+        return self._pairs or 0
+
+    def common(self):
+        """int32[P]: the common neighbours of every pair"""
+        p = self._count()
+        out = np.zeros(max(p, 1), dtype=np.int32)
+        check(lib.mgx_sim_common(self._h, _ptr(out)))
+        return out[:p]
+
+    def scores(self):
+        """float64[P]: the chosen measure of every pair"""
+        p = self._count()
+        out = np.zeros(max(p, 1), dtype=np.float64)
+        check(lib.mgx_sim_scores(self._h, _ptr(out)))
+        return out[:p]
+
+    def pairs(self):
+        """int32[P, 2]: the last run's pairs (edges mode: the edges it generated, (src, dst) of KtrussProblem.edges())"""
+        p = self._count()
+        u, v = np.zeros(max(p, 1), dtype=np.int32), np.zeros(max(p, 1), dtype=np.int32)
+        check(lib.mgx_sim_pairs(self._h, _ptr(u), _ptr(v)))
+        return np.stack([u[:p], v[:p]], axis=1)
+
+    def common_device_ptr(self):
+        d = C.c_void_p()
+        check(lib.mgx_sim_common_device(self._h, C.byref(d)))
+        return d.value
+
+    def scores_device_ptr(self):
+        d = C.c_void_p()
+        check(lib.mgx_sim_scores_device(self._h, C.byref(d)))
+        return d.value
+
+    def bins(self):
+        """the last run(): pairs per class, the cuts as read, the adjacency entries the pair kernels loaded"""
+        out = (C.c_int64 * 10)()
+        check(lib.mgx_sim_bins(self._h, out))
+        return dict(zip(self.BINS, (int(x) for x in out)))
+
+    def close(self):
+        if self._h:
+            lib.mgx_sim_free(self._h)
+            self._h = None
+
+
 def modularity(graph, labels, symmetric=False):
     """Modularity of any labelling (labels in [0, n): a numpy array, a torch tensor on the device or a device address) ->
     (Q, S_in, S_sq, W); Q = S_in / W - S_sq / W^2 in double from the three integers the library returns (0.0 when W == 0)."""

@@ -25,6 +25,7 @@
 #include "gunrock/pagerank/pagerank_enactor.hxx"
 #include "gunrock/pr/pr_enactor.hxx"
 #include "gunrock/nsample/nsample_enactor.hxx"
+#include "gunrock/sim/sim_enactor.hxx"
 #include "gunrock/rw/rw_enactor.hxx"
 #include "gunrock/kcore/kcore_enactor.hxx"
 #include "gunrock/sssp/sssp_enactor.hxx"
@@ -47,6 +48,7 @@
 #include "mgx/sssp_dist.hpp"
 #include "mgx/rmat.hpp"
 #include "mgx/nsample_fused.hpp"
+#include "mgx/sim_fused.hpp"
 #include "mgx/rw_fused.hpp"
 #include "mgx/sssp_fused.hpp"
 #include "mgx/sssp_preds.hpp"
@@ -228,6 +230,17 @@ struct mgx_nsample_s : mgx_problem_s {
   std::shared_ptr<nsample::nsample_problem_t> p;
   std::unique_ptr<nsample::nsample_enactor_t> e;
   int last = 0;                                                   // 0: no run yet; 1: the fused path's results; 2: the operator path's
+  bool timing = false;
+};
+
+struct mgx_sim_s : mgx_problem_s {
+  std::unique_ptr<mgx::sim_state_t> st;                           // lazily: the adjacencies (per `symmetric`), the fused path's lists and results
+  mgx::sim_results_t op_res;                                      // the operator path's pairs and results
+  mem_t<unsigned long long> op_sums;
+  std::shared_ptr<sim::sim_problem_t> p;
+  std::unique_ptr<sim::sim_enactor_t> e;
+  int last = 0;                                                   // 0: no run yet; 1: the fused path's results; 2: the operator path's
+  int sym = -1;                                                   // the adjacency prepared or run on last (-1: none yet)
   bool timing = false;
 };
 
@@ -3878,6 +3891,163 @@ int mgx_nsample_phase_ms(mgx_nsample_t p, double* out) {
   MGX_REQUIRE(p && out, "NULL argument");
   require_run(p->last == 1, "mgx_nsample_phase_ms");
   out[0] = p->fused->phase_ms[0]; out[1] = p->fused->phase_ms[1];
+  MGX_CATCH
+}
+
+// ---- vertex similarity for link prediction -----------------------------------------
+static mgx::sim_state_t& sim_state(mgx_sim_t p) {
+  if (!p->st) p->st.reset(new mgx::sim_state_t(p->graph().num_nodes, p->graph().num_edges, p->ctx()));
+  return *p->st;
+}
+// a run's arguments, checked before any device work (the ids are checked on the device)
+static void sim_check(mgx_sim_t p, const int* h_u, const int* h_v, int pairs, int measure, const double* h_x, const char* who) {
+  const std::string w(who);
+  MGX_REQUIRE(p, "NULL argument");
+  MGX_REQUIRE(measure >= 0 && measure < mgx::SIM_MEASURES, w + ": measure must be one of MGX_SIM_*");
+  MGX_REQUIRE((h_u == nullptr) == (h_v == nullptr), w + ": of the two pair arrays one is NULL");
+  MGX_REQUIRE(!h_u || pairs >= 0, w + ": pairs must not be negative");
+  MGX_REQUIRE(measure != mgx::SIM_WEIGHTED || h_x, w + ": MGX_SIM_WEIGHTED needs the weights h_x");
+}
+static const mgx::sim_results_t& sim_results(mgx_sim_t p, const char* who) {
+  MGX_REQUIRE(p, "NULL argument");
+  require_run(p->last != 0, who);
+  return p->last == 1 ? p->st->res : p->op_res;
+}
+int mgx_sim_create(mgx_graph_t g, mgx_sim_t* out) { return create_handle(g, out); }
+int mgx_sim_free(mgx_sim_t p) { return free_handle(p); }
+int mgx_sim_prepare(mgx_sim_t p, int symmetric) {
+  MGX_TRY
+  auto [ctx, g] = enter(p);
+  sim_state(p).prepare(symmetric != 0, g.d_row_offsets.data(), g.d_col_indices.data(), ctx);
+  p->sym = symmetric != 0 ? 1 : 0;
+  MGX_CATCH
+}
+int mgx_sim_run(mgx_sim_t p, int symmetric, const int* h_u, const int* h_v, int pairs, int measure, const double* h_x, int64_t* stats) {
+  MGX_TRY
+  if (p) p->last = 0;                                          // (a run that is refused leaves nothing to the getters)
+  sim_check(p, h_u, h_v, pairs, measure, h_x, "mgx_sim_run");
+  auto [ctx, g] = enter(p);
+  mgx::sim_state_t& st = sim_state(p);
+  st.timing = p->timing;
+  const std::vector<long long> out = st.run(g.d_row_offsets.data(), g.d_col_indices.data(), symmetric != 0, h_u, h_v, pairs, measure, h_x, ctx);
+  p->sym = symmetric != 0 ? 1 : 0;
+  p->last = 1;
+  put_stats(stats, mgx::SIM_STATS, out);
+  MGX_CATCH
+}
+int mgx_sim_enact(mgx_sim_t p, int symmetric, const int* h_u, const int* h_v, int pairs, int measure, const double* h_x, int64_t* stats) {
+  MGX_TRY
+  if (p) p->last = 0;
+  sim_check(p, h_u, h_v, pairs, measure, h_x, "mgx_sim_enact");
+  auto [ctx, g] = enter(p);
+  mgx::sim_state_t& st = sim_state(p);
+  const int sym = symmetric != 0 ? 1 : 0;
+  const bool timing = st.timing;
+  st.timing = false;                                           // (the phases describe fused runs)
+  const bool built_now = st.begin(sym != 0, g.d_row_offsets.data(), g.d_col_indices.data(), ctx);
+  st.timing = timing;
+  p->op_res.pairs = 0;
+  std::vector<long long> out = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (st.n > 0) {
+    const hipStream_t s = ctx.stream();
+    mgx::ktruss_graph_t& kg = st.kt.gr[sym];
+    const long long P = h_u ? pairs : kg.m;
+    const bool weighted = measure == mgx::SIM_WEIGHTED;
+    mgx::sim_results_t& res = p->op_res;
+    res.ensure((size_t)P, weighted, st.n, ctx);
+    if (p->op_sums.size() == 0) p->op_sums = mem_t<unsigned long long>(2, ctx);
+    res.upload(h_u, h_v, P, kg.src.data(), st.kt.tc.dag[sym].ci.data(), weighted ? h_x : nullptr, st.n, s);
+    MGX_HIP(hipMemsetAsync(p->op_sums.data(), 0, 2 * sizeof(unsigned long long), s));
+    const sim::sim_problem_t::data_slice_t slice = {kg.adj_ro.data(), kg.adj_ci.data(), res.u, res.v, weighted ? res.x.data() : nullptr,
+                                                    res.common.data(), res.score.data(), p->op_sums.data(), st.n, measure};
+    if (!p->p) p->p = std::make_shared<sim::sim_problem_t>(p->g->g, slice, ctx);
+    else MGX_HIP(mgx::htod(p->p->d_data_slice.data(), &slice, 1, s));
+    long long waits = 1, positive = 0, calls = 0;              // (the data slice goes up with a blocking copy)
+    if (P > 0) {
+      if (!p->e || (size_t)P > p->e->cap) {
+        p->e.reset();
+        p->e.reset(new sim::sim_enactor_t(ctx, (size_t)P));
+      }
+      positive = p->e->enact(p->p, P, ctx);
+      waits += p->e->waits;
+      calls = p->e->calls;
+    }
+    unsigned long long sums[2] = {0, 0};
+    MGX_HIP(mgx::dtoh(sums, (const unsigned long long*)p->op_sums.data(), 2, s));
+    ++waits;
+    MGX_REQUIRE(!sums[1], "mgx_sim_enact: a pair names a vertex outside [0, n)");
+    const long long longest = st.longest_row(sym, ctx);
+    out = {P, (long long)sums[0], positive, 2ll * kg.m, longest, built_now ? 1 : 0, st.kt.tc.waits + waits, st.kt.tc.launches + 1 + 2 * calls};
+  }
+  p->sym = sym;
+  p->last = 2;
+  put_stats(stats, mgx::SIM_STATS, out);
+  MGX_CATCH
+}
+int mgx_sim_common(mgx_sim_t p, int* host) {
+  MGX_TRY
+  const mgx::sim_results_t& res = sim_results(p, "mgx_sim_common");
+  if (host) read_back(p, host, (const int*)res.common.data(), (size_t)res.pairs);
+  MGX_CATCH
+}
+int mgx_sim_scores(mgx_sim_t p, double* host) {
+  MGX_TRY
+  const mgx::sim_results_t& res = sim_results(p, "mgx_sim_scores");
+  if (host) read_back(p, host, (const double*)res.score.data(), (size_t)res.pairs);
+  MGX_CATCH
+}
+int mgx_sim_common_device(mgx_sim_t p, const int** out) {
+  MGX_TRY
+  const mgx::sim_results_t& res = sim_results(p, "mgx_sim_common_device");
+  MGX_REQUIRE(out, "NULL argument");
+  *out = res.pairs ? res.common.data() : nullptr;
+  MGX_CATCH
+}
+int mgx_sim_scores_device(mgx_sim_t p, const double** out) {
+  MGX_TRY
+  const mgx::sim_results_t& res = sim_results(p, "mgx_sim_scores_device");
+  MGX_REQUIRE(out, "NULL argument");
+  *out = res.pairs ? res.score.data() : nullptr;
+  MGX_CATCH
+}
+int mgx_sim_pairs(mgx_sim_t p, int* h_u, int* h_v) {
+  MGX_TRY
+  const mgx::sim_results_t& res = sim_results(p, "mgx_sim_pairs");
+  if (h_u) read_back(p, h_u, res.u, (size_t)res.pairs);
+  if (h_v) read_back(p, h_v, res.v, (size_t)res.pairs);
+  MGX_CATCH
+}
+int mgx_sim_degrees(mgx_sim_t p, int* host) {
+  MGX_TRY
+  MGX_REQUIRE(p && host, "NULL argument");
+  MGX_REQUIRE(p->sym >= 0, "mgx_sim_degrees: no adjacency yet (mgx_sim_prepare)");
+  const size_t n = p->n();
+  if (n == 0) return MGX_OK;
+  std::vector<int> ro(n + 1);
+  read_back(p, ro.data(), (const int*)p->st->kt.gr[p->sym].adj_ro.data(), n + 1);
+  for (size_t v = 0; v < n; ++v) host[v] = ro[v + 1] - ro[v];
+  MGX_CATCH
+}
+int mgx_sim_bins(mgx_sim_t p, int64_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->last == 1, "mgx_sim_bins");
+  const mgx::sim_state_t& st = *p->st;
+  for (int i = 0; i < mgx::SIM_CLASSES; ++i) out[i] = st.bins[i];
+  out[5] = st.opts.short_max; out[6] = st.opts.probe_ratio; out[7] = st.opts.wave_max; out[8] = st.opts.stage; out[9] = st.entries_read;
+  MGX_CATCH
+}
+int mgx_sim_set_timing(mgx_sim_t p, int on) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  p->timing = on != 0;
+  MGX_CATCH
+}
+int mgx_sim_phase_ms(mgx_sim_t p, double* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->last == 1, "mgx_sim_phase_ms");
+  for (int i = 0; i < 3; ++i) out[i] = p->st->phase_ms[i];
   MGX_CATCH
 }
 
