@@ -20,8 +20,10 @@
 //     (the value for delta = 0) on the deepest level ONLY -- the one level no backward launch visits.  Deeper levels of the same
 //     parity hold stale values; nothing on level d has an out-entry to them.
 //   The host knows the depth only to one level (the traversal reports the levels that expanded an entry: D or D - 1): it plans for
-//   D' = levels + 1, the forward pass seeds Q on the levels D' - 2 and D' - 1, the backward pass starts at D' - 2 (a level whose
-//   sum comes out 0 rewrites the same 1 / sigma).
+//   D' = levels + 1, the forward pass seeds Q on the levels D' - 2 and D' - 1, the backward pass starts at D' - 2 and the device
+//   leaves that level alone when the list of D' - 1 is empty (bc_deepest): it is the deepest then, delta = 0 and Q is seeded.
+//   (Folding it all the same rewrites the same 1 / sigma for a finite sigma -- but an overflowed sigma gives inf * 0 = NaN, which
+//   the next levels spread over the whole traversal: tests/bc_cases.py, sigma_limits at 2^1024.)
 //
 // Level lists: key[v] = (label + 1) * 4 + row class, (key, id) sorted with rocPRIM's radix sort over the bits D' needs, the
 // list bounds found from the sorted keys -- one contiguous list per level and class, unreached vertices in front.  A directed
@@ -142,6 +144,11 @@ __device__ __forceinline__ double bc_seg_block(const int* __restrict__ idx, int 
   return t;
 }
 
+// backward: is level d the deepest, i.e. is the list of level d + 1 empty?  Asked for the one level the host cannot tell.
+__device__ __forceinline__ bool bc_deepest(const int* __restrict__ bound, int d) {
+  const int k = (d + 2) * BC_KEY_STRIDE;
+  return bound[k] == bound[k + BC_KEY_STRIDE];
+}
 // what the owner of v does with the row's sum S
 template <bool BACK>
 __device__ __forceinline__ void bc_finish(int v, double S, const bc_arrays_t& A, int d, int seed_q) {
@@ -201,9 +208,11 @@ __global__ __launch_bounds__(BLOCK) void k_bc_finish(const int* __restrict__ lab
 }
 
 // ---- one level, chip-sized grid: the lane rows and the wave rows ------------------------------------
+// seed_q: forward, seed Q on this level; backward, this level may be the deepest (nothing to do then)
 template <bool BACK>
 __global__ __launch_bounds__(BLOCK) void k_bc_level(bc_dir_t G, const int* __restrict__ list, const int* __restrict__ bound, int d, int seed_q,
                                                     bc_arrays_t A) {
+  if (BACK && seed_q && bc_deepest(bound, d)) return;
   const int k0 = (d + 1) * BC_KEY_STRIDE;
   const int l0 = bound[k0], l1 = bound[k0 + 1], l2 = bound[k0 + 2];
   const double* const vals = BACK ? A.Q[(d + 1) & 1] : A.P[(d - 1) & 1];
@@ -241,6 +250,7 @@ __global__ __launch_bounds__(BLOCK) void k_bc_huge_seg(bc_dir_t G, const int* __
 template <bool BACK>
 __global__ __launch_bounds__(BLOCK) void k_bc_huge_fold(bc_dir_t G, const int* __restrict__ list, const int* __restrict__ bound, int d, int seed_q,
                                                         bc_arrays_t A, const double* __restrict__ partial) {
+  if (BACK && seed_q && bc_deepest(bound, d)) return;
   const int k0 = (d + 1) * BC_KEY_STRIDE;
   const int l2 = bound[k0 + 2], l3 = bound[k0 + 3];
   for (long long i = l2 + (long long)blockIdx.x * BLOCK + threadIdx.x; i < l3; i += (long long)gridDim.x * BLOCK) {
@@ -254,12 +264,14 @@ __global__ __launch_bounds__(BLOCK) void k_bc_huge_fold(bc_dir_t G, const int* _
 }
 
 // ---- the chain: ONE workgroup, the levels [lo, hi] one after the other (backward: hi down to lo) -----
+// seed_from: forward, the levels from here on seed Q; backward, the levels from here on may be the deepest
 template <bool BACK>
 __global__ __launch_bounds__(BLOCK) void k_bc_chain(bc_dir_t G, const int* __restrict__ list, const int* __restrict__ bound, int lo, int hi,
                                                     int seed_from, bc_arrays_t A) {
   __shared__ double s_w[WAVES_PER_BLOCK];
   const int lane = lane_id(), wave = (int)threadIdx.x / WAVE;
   for (int d = BACK ? hi : lo; BACK ? d >= lo : d <= hi; BACK ? --d : ++d) {   // (workgroup-uniform)
+    if (BACK && d >= seed_from && bc_deepest(bound, d)) continue;               // (workgroup-uniform; nothing written, no fence)
     const int k0 = (d + 1) * BC_KEY_STRIDE;
     const int l0 = bound[k0], l1 = bound[k0 + 1], l2 = bound[k0 + 2], l3 = bound[k0 + 3];
     const double* const vals = BACK ? A.Q[(d + 1) & 1] : A.P[(d - 1) & 1];
@@ -491,22 +503,23 @@ struct bc_state_t {
       ++d;
     }
     mark(3, st);
-    // backward: d = D - 2 .. 1
+    // backward: d = D - 2 .. 1; D - 2 is the deepest level when the traversal's last level expanded an entry: the device looks
     for (int d = D - 2; d >= 1;) {
       int e = d;
       while (e >= 1 && small(e)) --e;
       if (d - e >= 2) {
-        hipLaunchKernelGGL(k_bc_chain<true>, dim3(1), dim3(BLOCK), 0, st, Gout, list_b, bound_b, e + 1, d, 0, A);
+        hipLaunchKernelGGL(k_bc_chain<true>, dim3(1), dim3(BLOCK), 0, st, Gout, list_b, bound_b, e + 1, d, D - 2, A);
         ++launches; ++chain_launches; ++last_chain_launches;
         d = e;
         continue;
       }
-      hipLaunchKernelGGL(k_bc_level<true>, dim3(level_grid(d)), dim3(BLOCK), 0, st, Gout, list_b, bound_b, d, 0, A);
+      const int maybe_deepest = d == D - 2 ? 1 : 0;
+      hipLaunchKernelGGL(k_bc_level<true>, dim3(level_grid(d)), dim3(BLOCK), 0, st, Gout, list_b, bound_b, d, maybe_deepest, A);
       ++launches;
       if (rout.count[BC_HUGE] > 0) {
         hipLaunchKernelGGL(k_bc_huge_seg<true>, dim3((int)std::min<long long>(max_blocks, rout.segments)), dim3(BLOCK), 0, st, Gout, labels, d, A,
                            partial.data());
-        hipLaunchKernelGGL(k_bc_huge_fold<true>, dim3(1), dim3(BLOCK), 0, st, Gout, list_b, bound_b, d, 0, A, (const double*)partial.data());
+        hipLaunchKernelGGL(k_bc_huge_fold<true>, dim3(1), dim3(BLOCK), 0, st, Gout, list_b, bound_b, d, maybe_deepest, A, (const double*)partial.data());
         launches += 2;
       }
       --d;
