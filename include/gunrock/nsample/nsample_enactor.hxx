@@ -86,6 +86,8 @@ struct nsample_enactor_t {
     MGX_HIP(mgx::dtoh(counters, (const unsigned long long*)s.d_counters.data(), mgx::NS_COUNTERS, st));
     ++waits;
     s.res.seeds = r.count; s.res.edges = edge_off[r.hops]; s.res.device = true;
+    s.res.edge_offsets.assign(edge_off, edge_off + r.hops + 1);
+    s.res.any_whole = std::any_of(r.fanouts, r.fanouts + r.hops, [](int k) { return k < 0; });
     int* const seed_local = s.res.seed_local.data();
     transform([=] __device__(int e) { d.d_cols[e] = d.d_local[d.d_cols[e]]; }, s.res.edges, ctx);
     transform([=] __device__(int i) { seed_local[i] = d.d_local[seeds ? seeds[i] : i]; }, r.count, ctx);

@@ -55,6 +55,7 @@ typedef struct mgx_lpa_s* mgx_lpa_t;
 typedef struct mgx_msbfs_s* mgx_msbfs_t;
 typedef struct mgx_rw_s* mgx_rw_t;
 typedef struct mgx_nsample_s* mgx_nsample_t;
+typedef struct mgx_agg_s* mgx_agg_t;
 typedef struct mgx_louvain_s* mgx_louvain_t;
 typedef struct mgx_dbfs_s* mgx_dbfs_t;
 typedef struct mgx_dbfs2_s* mgx_dbfs2_t;
@@ -1121,6 +1122,67 @@ MGX_API int mgx_nsample_bins(mgx_nsample_t p, int64_t* out);
  * and of its deduplication (marks, ranks, renumbering) */
 MGX_API int mgx_nsample_set_timing(mgx_nsample_t p, int on);
 MGX_API int mgx_nsample_phase_ms(mgx_nsample_t p, double* out);
+
+/* ---- neighbour feature aggregation for GNN layers (include/mgx/agg_fused.hpp, include/gunrock/agg/) ----
+ * For every row r of a CSR the reduction of its neighbours' feature rows, Y[r, f] = (+) over the entries e of row r of t_e, the
+ * memory-bound step of a GraphSAGE / GCN layer, in a FIXED order of arithmetic: both paths and tests/agg_model.py give the same
+ * float32 bits, on every run.
+ *   the CSR   source 0: the graph's out-rows; 1: its in-rows (needs the genuine CSC, mgx_graph_build_csc); 2: the rows of `block`'s
+ *             last successful sampling run, read on the device without a copy: hop h's rows, or all R sampled rows with hop = -1.
+ *             A block's columns are local ids: X is then indexed by local id and needs the run's `vertices` rows.  Original ids; an
+ *             attached layout is ignored.
+ *   X, Y      float32 device arrays, row-major: X is x_rows x feats with leading dimension ldx >= feats, Y is R x feats with ldy >=
+ *             feats.  Their ranges must not overlap.  Every element of Y[:R, :feats] is written on every run, the padding columns
+ *             feats .. ldy - 1 never.
+ *   a term    t_e = X[col_e, f], or with weighted != 0 w_e * X[col_e, f] rounded once to float32: the multiply and the add are never
+ *             fused.  w_e is the graph's weight of the entry (out-rows; a block's through entry_pos) or the CSC's row value (in-rows).
+ *   the order a row's entries are cut into segments of seg entries in STORED order (MGX_AGG_SEG, a power of two in 64 .. 4096,
+ *             default 256).  Within a segment acc = t_0, then acc = acc (+) t_j, j = 1, 2, ..; the row's value is the segments' values
+ *             combined the same way, in segment order: a row of at most seg entries is one plain left-to-right fold.  (+) is float32 +
+ *             for MGX_AGG_SUM and MGX_AGG_MEAN, t > acc ? t : acc for MGX_AGG_MAX, t < acc ? t : acc for MGX_AGG_MIN, which fixes +-0
+ *             and NaN by the order.  MEAN divides the sum by float(d), one correctly rounded division.  A row without entries gives
+ *             0.0 for every op.
+ * MGX_E_INVALID before any device work, the message names the parameter: feats outside [1, 65536], ldx or ldy below feats, an unknown
+ * op or source, weighted without weights, in-rows without a CSC, a block of another graph or without a successful run, hop outside
+ * [-1, the run's hops), x_rows below n (the graph's rows) or below the run's vertices (a block), NULL d_x or d_y with R > 0,
+ * overlapping X and Y.
+ * stats (may be NULL), int64[9]: [0] rows R, [1] entries, [2] feats, [3] team width G (lanes a row takes), [4] column tiles, [5] 1
+ * on the vector path (feats, ldx, ldy multiples of 4 and both bases 16-byte aligned: a lane owns 4 columns), [6] seg, [7] launches
+ * (mgx_agg_enact: operator calls), [8] host waits.  mgx_agg_run only enqueues on the context's stream: 1 launch (3 with rows longer
+ * than seg) and no wait; the run that builds a plan of the long rows has 2 launches and 1 wait more: the first run on the out-rows
+ * and on the in-rows (kept for the handle's life), and every run on a block whose sampling run had a fan-out of -1.  R == 0: nothing.
+ * Partials and plans live on the handle and only grow: a repeat run of the same or a smaller shape allocates nothing.  A call that
+ * is refused leaves no result: the getters return MGX_E_INVALID until a call succeeds. */
+#define MGX_AGG_SUM 0
+#define MGX_AGG_MEAN 1
+#define MGX_AGG_MAX 2
+#define MGX_AGG_MIN 3
+#define MGX_AGG_OUT_ROWS 0
+#define MGX_AGG_IN_ROWS 1
+#define MGX_AGG_BLOCK 2
+MGX_API int mgx_agg_create(mgx_graph_t g, mgx_agg_t* out);
+MGX_API int mgx_agg_free(mgx_agg_t p);
+/* the fused path: a team of lanes per row, the loads of 8 entries in flight, one launch; rows longer than seg as (row, segment)
+ * items and a fold of their partials in segment order */
+MGX_API int mgx_agg_run(mgx_agg_t p, int source, mgx_nsample_t block, int hop, const float* d_x, int64_t x_rows, int64_t ldx, int feats, int op,
+                        int weighted, float* d_y, int64_t ldy, int64_t* stats);
+/* the operator path: one filter over the rows, a lane per row, column by column; the same bits */
+MGX_API int mgx_agg_enact(mgx_agg_t p, int source, mgx_nsample_t block, int hop, const float* d_x, int64_t x_rows, int64_t ldx, int feats, int op,
+                          int weighted, float* d_y, int64_t ldy, int64_t* stats);
+/* for callers with host arrays: mgx_agg_upload copies host_x (rows x feats, contiguous) into an array the handle owns and gives its
+ * device address (leading dimension feats); mgx_agg_output gives a handle-owned device array of rows x ld floats to pass as d_y.
+ * Both grow only and stay valid until a larger request or free. */
+MGX_API int mgx_agg_upload(mgx_agg_t p, const float* host_x, int64_t rows, int feats, float** d_x);
+MGX_API int mgx_agg_output(mgx_agg_t p, int64_t rows, int64_t ld, float** d_y);
+/* the last call's Y[:R, :feats] to the host, contiguous (R x feats), from wherever the call wrote it; waits */
+MGX_API int mgx_agg_result(mgx_agg_t p, float* host_y);
+/* int64[5] of the last fused run, counted by its own launches (waits): [0] rows without entries, [1] rows of at most seg entries (a
+ * team's), [2] longer rows, [3] the segments of the latter, [4] seg */
+MGX_API int mgx_agg_bins(mgx_agg_t p, int64_t* out);
+/* timing (measurement tools; off by default): mgx_agg_phase_ms gives out[3] = ms of the last fused run's rows, items and fold
+ * launches (waits for them) */
+MGX_API int mgx_agg_set_timing(mgx_agg_t p, int on);
+MGX_API int mgx_agg_phase_ms(mgx_agg_t p, double* out);
 
 /* ---- vertex similarity for link prediction (include/mgx/sim_fused.hpp, include/gunrock/sim/) ----
  * How alike are two vertices' neighbourhoods, exactly, for arbitrary pairs.  The graph is the underlying simple undirected graph of

@@ -85,6 +85,8 @@ inline const env_switch_t* env_switches(int* count) {
     {"MGX_NSAMPLE_SHORT_MAX", "a hop that takes whole rows (fan-out -1) copies rows of at most N entries a lane each (default 32)"},
     {"MGX_NSAMPLE_WAVE_MAX", "longer rows of at most N entries take a wave each, the rest go out as (row, segment) items (default 1024)"},
     {"MGX_NSAMPLE_SEG", "entries of a segmented row one wave copies (default 1024)"},
+    // ---- neighbour feature aggregation (agg_seg_from_env: read once per handle, at its first call; 256 against 64 and 1024: DESIGN 3.23)
+    {"MGX_AGG_SEG", "entries of a row's segment, a power of two in [64, 4096]: a row of at most N entries is one left-to-right fold by a team of lanes, a longer one goes out as (row, segment) items whose values are combined in segment order (default 256); part of the result's definition"},
     // ---- vertex similarity (sim_opts_t::from_env: read once per handle; short_max and wave_max are unmeasured guesses)
     {"MGX_SIM_SHORT_MAX", "pairs whose shorter adjacency row has at most N entries take a lane each: every entry searched in the longer row (default 16)"},
     {"MGX_SIM_PROBE_RATIO", "longer short rows against rows of at least N times their length take a group of 16 lanes searching the long row in global memory; the rest are staged (default 8: measured at rows of 256)"},

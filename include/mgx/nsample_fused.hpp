@@ -399,6 +399,8 @@ struct ns_results_t {
   mem_t<int> d_seeds, vertices, row_offsets, cols, entry_pos, seed_local;
   size_t seeds_cap = 0, vertices_cap = 0, rows_cap = 0, entries_cap = 0;
   std::vector<int> hop_offsets;      // H + 2
+  std::vector<int> edge_offsets;     // H + 1: the entries before hop h (what a reader of one hop's rows needs without a wait)
+  bool any_whole = false;            // a fan-out of the run was -1: rows may be longer than NS_MAX_FANOUT
   long long seeds = 0, edges = 0;
   bool device = false;               // the last run did device work (else every array is empty and row_offsets is {0})
   static void grow(mem_t<int>& m, size_t& cap, size_t want, context_t& ctx) {
@@ -426,6 +428,8 @@ struct ns_results_t {
   }
   void nothing(const ns_request_t& r) {
     hop_offsets.assign((size_t)r.hops + 2, 0);
+    edge_offsets.assign((size_t)r.hops + 1, 0);
+    any_whole = false;
     seeds = r.count; edges = 0; device = false;
   }
   long long count_vertices() const { return hop_offsets.empty() ? 0 : hop_offsets.back(); }
@@ -540,6 +544,8 @@ struct ns_fused_state_t {
     for (int s = 0; s < NS_SLOTS; ++s)
       for (int i = 0; i < NS_COUNTERS; ++i) sum[i] += (long long)c.counters[s][i];
     res.hop_offsets.assign(c.hop_off, c.hop_off + r.hops + 2);
+    res.edge_offsets.assign(c.edge_off, c.edge_off + r.hops + 1);
+    res.any_whole = std::any_of(r.fanouts, r.fanouts + r.hops, [](int k) { return k < 0; });
     res.seeds = r.count; res.edges = c.edge_off[r.hops]; res.device = true;
     std::copy(c.bins, c.bins + NS_BINS, bins);
     if (timing) {

@@ -1649,6 +1649,111 @@ class NeighborSampleProblem(_Timed):
             self._h = None
 
 
+class AggregateProblem(_Timed):
+    """Neighbour feature aggregation for GNN layers: Y[r, :] = the reduction over row r's entries of the neighbours'
+    feature rows X[col_e, :], optionally times the entry's weight -- the memory-bound step of a GraphSAGE / GCN layer.  run() is the
+    fused path (a team of lanes per row, one launch; three with rows longer than seg), enact() the operator path (a lane per row);
+    both give the same float32 bits as tests/agg_model.py, on every run.  The fine print of the definition:
+      * the rows are the graph's out-rows (rows="out"), its in-rows (rows="in", after graph.build_csc()) or, with block=a
+        NeighborSampleProblem, the rows of its last sampling run: hop h's, or all sampled rows with hop=None.  A block's columns are
+        local ids: x is then indexed by local id (x[i] belongs to block.vertices()[i]);
+      * a term is x[col, f], or weight * x[col, f] rounded once to float32 (weighted=True: the graph's weights, a block's through
+        entry_pos, the CSC's row values for in-rows); the multiply and the add are never fused;
+      * a row's entries are folded in STORED order, left to right, from its first term (not from zero); a row of more than seg
+        entries (MGX_AGG_SEG, default 256) in segments of seg whose values are combined in segment order.  max and min are
+        t > acc ? t : acc and t < acc ? t : acc, which fixes +-0 and NaN by the order;
+      * mean is the sum divided by float32(d), correctly rounded; a row without entries gives 0.0 for every op;
+      * every element of the result is written on every run, padding columns (ldy > feats) never.
+    x and out may be numpy arrays (x is uploaded into the handle's buffer, the result stays in the handle's: result()), torch
+    tensors, or device addresses (then with x_rows= and feats=)."""
+
+    _C = "mgx_agg"
+    KEYS = ("rows", "entries", "feats", "team_width", "col_tiles", "vector", "seg", "launches", "host_waits")
+    PHASES = ("rows", "items", "fold")
+    BINS = ("none", "team", "long", "segments", "seg")
+    OPS = ("sum", "mean", "max", "min")
+    ROWS = ("out", "in")
+
+    def __init__(self, graph):
+        h = C.c_void_p()
+        check(lib.mgx_agg_create(graph._h, C.byref(h)))
+        self.graph, self._h = graph, h
+        self._last = None
+
+    def _rows_of(self, block, hop):
+        if block is None:
+            return self.graph.num_nodes
+        if not block._last:
+            return 0                                             # (the library refuses the block)
+        if hop is None:
+            return block._last["rows"]
+        off = block.hop_offsets()
+        return int(off[hop + 1] - off[hop]) if 0 <= hop < len(off) - 2 else 0
+
+    def _go(self, fn, x, op, weighted, rows, block, hop, out, ldx, ldy, x_rows, feats):
+        if op not in self.OPS or rows not in self.ROWS:
+            raise ValueError("op must be one of %s and rows one of %s" % (self.OPS, self.ROWS))
+        self._last = None
+        if isinstance(x, np.ndarray):
+            hx = np.ascontiguousarray(x, dtype=np.float32)
+            if hx.ndim != 2:
+                raise ValueError("x must be two-dimensional (x_rows, feats)")
+            x_rows, feats = hx.shape
+            d = C.c_void_p()
+            check(lib.mgx_agg_upload(self._h, _ptr(hx), x_rows, max(feats, 1), C.byref(d)))
+            d_x, ldx = d, feats
+        else:
+            if (x_rows is None or feats is None) and hasattr(x, "shape"):
+                x_rows, feats = (int(s) for s in x.shape)          # a two-dimensional tensor
+                if ldx is None and x_rows > 1:
+                    ldx = int(x.stride(0))
+            if x_rows is None or feats is None:
+                raise ValueError("a device address needs x_rows= and feats=")
+            d_x, ldx = _dev_ptr(x), feats if ldx is None else ldx
+        R = self._rows_of(block, hop)
+        if out is None:
+            ldy = feats if ldy is None else ldy
+            d = C.c_void_p()
+            check(lib.mgx_agg_output(self._h, R, max(ldy, 1), C.byref(d)))
+            d_y = d
+        else:
+            if ldy is None:
+                ldy = int(out.stride(0)) if hasattr(out, "stride") and len(out.shape) == 2 and out.shape[0] > 1 else feats
+            d_y = _dev_ptr(out)
+        st = (C.c_int64 * 9)()
+        source = 2 if block is not None else self.ROWS.index(rows)
+        check(fn(self._h, source, None if block is None else block._h, -1 if hop is None else int(hop), d_x, int(x_rows), int(ldx), int(feats),
+                 self.OPS.index(op), int(bool(weighted)), d_y, int(ldy), st))
+        self._last = dict(zip(self.KEYS, (int(v) for v in st)))
+        return dict(self._last)
+
+    def run(self, x, op="sum", weighted=False, rows="out", block=None, hop=None, out=None, ldx=None, ldy=None, x_rows=None, feats=None):
+        """fused path -> the stats dict of KEYS; only enqueues on the context's stream (a run that builds a plan waits once)"""
+        return self._go(lib.mgx_agg_run, x, op, weighted, rows, block, hop, out, ldx, ldy, x_rows, feats)
+
+    def enact(self, x, op="sum", weighted=False, rows="out", block=None, hop=None, out=None, ldx=None, ldy=None, x_rows=None, feats=None):
+        """operator path (one filter over the rows, a lane per row); the same bits"""
+        return self._go(lib.mgx_agg_enact, x, op, weighted, rows, block, hop, out, ldx, ldy, x_rows, feats)
+
+    def result(self):
+        """float32[R, feats]: the last call's result, from wherever it was written (waits)"""
+        R, F = (self._last["rows"], self._last["feats"]) if self._last else (0, 1)
+        y = np.zeros((max(R, 1), F), dtype=np.float32)
+        check(lib.mgx_agg_result(self._h, _ptr(y)))
+        return y[:R]
+
+    def bins(self):
+        """the last fused run's rows without entries, of at most seg entries (a team's), longer ones, their segments, and seg (waits)"""
+        out = (C.c_int64 * 5)()
+        check(lib.mgx_agg_bins(self._h, out))
+        return dict(zip(self.BINS, (int(v) for v in out)))
+
+    def close(self):
+        if self._h:
+            lib.mgx_agg_free(self._h)
+            self._h = None
+
+
 class SimilarityProblem(_Timed):
     """Vertex similarity for link prediction: how alike are two vertices' neighbourhoods, exactly, for arbitrary pairs
     or for every edge.  The graph is the underlying simple undirected graph of the triangle count: N(v) = the distinct neighbours of

@@ -25,6 +25,7 @@
 #include "gunrock/pagerank/pagerank_enactor.hxx"
 #include "gunrock/pr/pr_enactor.hxx"
 #include "gunrock/nsample/nsample_enactor.hxx"
+#include "gunrock/agg/agg_enactor.hxx"
 #include "gunrock/sim/sim_enactor.hxx"
 #include "gunrock/rw/rw_enactor.hxx"
 #include "gunrock/kcore/kcore_enactor.hxx"
@@ -48,6 +49,7 @@
 #include "mgx/sssp_dist.hpp"
 #include "mgx/rmat.hpp"
 #include "mgx/nsample_fused.hpp"
+#include "mgx/agg_fused.hpp"
 #include "mgx/sim_fused.hpp"
 #include "mgx/rw_fused.hpp"
 #include "mgx/sssp_fused.hpp"
@@ -242,6 +244,20 @@ struct mgx_sim_s : mgx_problem_s {
   int last = 0;                                                   // 0: no run yet; 1: the fused path's results; 2: the operator path's
   int sym = -1;                                                   // the adjacency prepared or run on last (-1: none yet)
   bool timing = false;
+};
+
+struct mgx_agg_s : mgx_problem_s {
+  std::unique_ptr<mgx::agg_fused_state_t> fused;                  // lazily: the fused path's plans, partials and control words
+  std::shared_ptr<agg::agg_problem_t> p;                          // lazily: the operator path's slice
+  std::unique_ptr<agg::agg_enactor_t> e;
+  mem_t<float> xbuf, ybuf;                                        // mgx_agg_upload's and mgx_agg_output's arrays, growing only
+  size_t xcap = 0, ycap = 0;
+  int last = 0;                                                   // 0: no run yet; 1: the fused path's result; 2: the operator path's
+  const float* last_y = nullptr;                                  // where the last run wrote: rows x feats, leading dimension ldy
+  long long last_ldy = 0;
+  int last_rows = 0, last_feats = 0;
+  bool timing = false;
+  int seg = 0;                                                    // MGX_AGG_SEG as read at the handle's first call, for both paths (0: not yet)
 };
 
 struct mgx_louvain_s : mgx_problem_s {
@@ -3891,6 +3907,173 @@ int mgx_nsample_phase_ms(mgx_nsample_t p, double* out) {
   MGX_REQUIRE(p && out, "NULL argument");
   require_run(p->last == 1, "mgx_nsample_phase_ms");
   out[0] = p->fused->phase_ms[0]; out[1] = p->fused->phase_ms[1];
+  MGX_CATCH
+}
+
+// ---- neighbour feature aggregation for GNN layers ----------------------------------
+// a call's arguments, checked before any device work (the parameters first: their messages do not need a handle)
+static mgx::agg_request_t agg_check(mgx_agg_t p, int source, mgx_nsample_t block, int hop, const float* d_x, int64_t x_rows, int64_t ldx, int feats,
+                                    int op, int weighted, float* d_y, int64_t ldy, const char* who) {
+  const std::string w(who);
+  MGX_REQUIRE(feats >= 1 && feats <= mgx::AGG_MAX_FEATS, w + ": feats must be in [1, 65536]");
+  MGX_REQUIRE(ldx >= feats && ldy >= feats, w + ": ldx and ldy must be at least feats");
+  MGX_REQUIRE(op >= 0 && op < mgx::AGG_OPS, w + ": op must be 0 (sum), 1 (mean), 2 (max) or 3 (min)");
+  MGX_REQUIRE(source >= 0 && source < mgx::AGG_SOURCES, w + ": source must be 0 (out-rows), 1 (in-rows) or 2 (block)");
+  MGX_REQUIRE(x_rows >= 0, w + ": x_rows must not be negative");
+  MGX_REQUIRE(p, "NULL argument");
+  const graph_device_t& g = p->graph();
+  const size_t m = (size_t)g.num_edges;
+  mgx::agg_request_t r;
+  r.x = d_x; r.y = d_y; r.ldx = ldx; r.ldy = ldy; r.feats = feats; r.op = op; r.source = source;
+  long long need_rows = g.num_nodes;
+  if (source == mgx::AGG_SRC_OUT) {
+    r.ro = g.d_row_offsets.data(); r.ci = g.d_col_indices.data();
+    MGX_REQUIRE(!weighted || g.d_col_values.size() >= m, w + ": weighted, and the graph has no weights");
+    if (weighted) r.w = g.d_col_values.data();
+    r.R = g.num_nodes; r.entries = g.num_edges;
+  } else if (source == mgx::AGG_SRC_IN) {
+    MGX_REQUIRE(!g.csc_is_csr, w + ": the in-rows need the graph's genuine CSC (mgx_graph_build_csc)");
+    r.ro = g.d_col_offsets.data(); r.ci = g.d_row_indices.data();
+    MGX_REQUIRE(!weighted || g.d_row_values.size() >= m, w + ": weighted, and the CSC has no weights");
+    if (weighted) r.w = g.d_row_values.data();
+    r.R = g.num_nodes; r.entries = g.num_edges;
+  } else {
+    MGX_REQUIRE(block, w + ": source 2 needs a block (an mgx_nsample_t)");
+    MGX_REQUIRE(block->g == p->g, w + ": the block was sampled from another graph");
+    MGX_REQUIRE(block->last != 0, w + ": the block has no successful sampling run");
+    const mgx::ns_results_t& res = block->last == 1 ? block->fused->res : block->op_state->res;
+    const int hops = (int)res.hop_offsets.size() - 2;
+    MGX_REQUIRE(hop >= -1 && hop < hops, w + ": hop must be -1 (all sampled rows) or in [0, the run's hops)");
+    MGX_REQUIRE(!weighted || g.d_col_values.size() >= m, w + ": weighted, and the graph has no weights");
+    need_rows = res.count_vertices();
+    if (res.device) {
+      const int h0 = hop < 0 ? 0 : hop, h1 = hop < 0 ? hops : hop + 1;
+      r.ro = res.row_offsets.data() + res.hop_offsets[h0]; r.ci = res.cols.data();
+      r.R = res.hop_offsets[h1] - res.hop_offsets[h0];
+      r.entries = res.edge_offsets[h1] - res.edge_offsets[h0];
+      if (weighted) { r.w = g.d_col_values.data(); r.entry_pos = res.entry_pos.data(); }
+      r.needs_plan = res.any_whole;
+    }
+  }
+  MGX_REQUIRE(x_rows >= need_rows, w + ": x_rows is below the number of vertices the columns name");
+  MGX_REQUIRE(r.R == 0 || (d_x && d_y), w + ": d_x or d_y is NULL");
+  if (r.R > 0 && x_rows > 0) {
+    const char* const x0 = (const char*)d_x;
+    const char* const x1 = x0 + ((size_t)(x_rows - 1) * (size_t)ldx + (size_t)feats) * sizeof(float);
+    const char* const y0 = (const char*)d_y;
+    const char* const y1 = y0 + ((size_t)(r.R - 1) * (size_t)ldy + (size_t)feats) * sizeof(float);
+    MGX_REQUIRE(x1 <= y0 || y1 <= x0, w + ": the ranges of X and Y overlap");
+  }
+  return r;
+}
+// MGX_AGG_SEG is read once per handle: seg is part of the result's definition, and both paths of a handle use the same
+static int agg_seg(mgx_agg_t p) {
+  if (!p->seg) p->seg = mgx::agg_seg_from_env();
+  return p->seg;
+}
+static void agg_ran(mgx_agg_t p, const mgx::agg_request_t& r, int which) {
+  p->last_y = r.y; p->last_ldy = r.ldy; p->last_rows = r.R; p->last_feats = r.feats;
+  p->last = which;
+}
+int mgx_agg_create(mgx_graph_t g, mgx_agg_t* out) { return create_handle(g, out); }
+int mgx_agg_free(mgx_agg_t p) { return free_handle(p); }
+int mgx_agg_run(mgx_agg_t p, int source, mgx_nsample_t block, int hop, const float* d_x, int64_t x_rows, int64_t ldx, int feats, int op, int weighted,
+                float* d_y, int64_t ldy, int64_t* stats) {
+  MGX_TRY
+  if (p) p->last = 0;                                        // (a run that is refused leaves nothing to the getters)
+  const mgx::agg_request_t r = agg_check(p, source, block, hop, d_x, x_rows, ldx, feats, op, weighted, d_y, ldy, "mgx_agg_run");
+  auto [ctx, g] = enter(p);
+  if (!p->fused) p->fused.reset(new mgx::agg_fused_state_t(agg_seg(p)));
+  p->fused->timing = p->timing;
+  const std::vector<long long> st = p->fused->run(r, ctx);
+  agg_ran(p, r, 1);
+  put_stats(stats, mgx::AGG_STATS, st);
+  MGX_CATCH
+}
+int mgx_agg_enact(mgx_agg_t p, int source, mgx_nsample_t block, int hop, const float* d_x, int64_t x_rows, int64_t ldx, int feats, int op, int weighted,
+                  float* d_y, int64_t ldy, int64_t* stats) {
+  MGX_TRY
+  if (p) p->last = 0;
+  const mgx::agg_request_t r = agg_check(p, source, block, hop, d_x, x_rows, ldx, feats, op, weighted, d_y, ldy, "mgx_agg_enact");
+  auto [ctx, g] = enter(p);
+  const mgx::agg_shape_t sh = mgx::agg_shape(feats, mgx::agg_vector_ok(d_x, ldx, d_y, ldy, feats));
+  const int seg = agg_seg(p);
+  long long calls = 0, waits = 0;
+  if (r.R > 0) {
+    const agg::agg_problem_t::data_slice_t slice = {r.ro, r.ci, r.w ? r.entry_pos : nullptr, r.w, r.x, r.y, r.ldx, r.ldy, r.feats, r.op, seg};
+    if (!p->p) p->p = std::make_shared<agg::agg_problem_t>(p->g->g, slice, ctx);
+    else MGX_HIP(mgx::htod(p->p->d_data_slice.data(), &slice, 1, ctx.stream()));
+    ++waits;
+    if (!p->e) p->e.reset(new agg::agg_enactor_t());
+    p->e->enact(p->p, r.R, ctx);
+    calls = p->e->calls; waits += p->e->waits;
+  }
+  agg_ran(p, r, 2);
+  put_stats(stats, mgx::AGG_STATS, {r.R, r.entries, r.feats, sh.G, sh.tiles, sh.vector, seg, calls, waits});
+  MGX_CATCH
+}
+// a handle-owned array grown to `want` floats (growing only)
+static float* agg_buffer(mgx_agg_t p, mem_t<float> mgx_agg_s::*buf, size_t mgx_agg_s::*cap, size_t want) {
+  if (want > p->*cap) {
+    p->ctx().synchronize();                                  // (a queued run may still read the old one)
+    p->*buf = mem_t<float>();
+    p->*cap = 0;
+    p->*buf = mem_t<float>(want, p->ctx());
+    p->*cap = want;
+  }
+  return (p->*buf).data();
+}
+int mgx_agg_upload(mgx_agg_t p, const float* host_x, int64_t rows, int feats, float** d_x) {
+  MGX_TRY
+  MGX_REQUIRE(p && d_x && rows >= 0 && feats >= 1 && (host_x || rows == 0), "mgx_agg_upload: NULL or negative argument");
+  auto [ctx, g] = enter(p);
+  const size_t count = (size_t)rows * (size_t)feats;
+  *d_x = agg_buffer(p, &mgx_agg_s::xbuf, &mgx_agg_s::xcap, count);
+  MGX_HIP(mgx::htod(*d_x, host_x, count, ctx.stream()));
+  MGX_CATCH
+}
+int mgx_agg_output(mgx_agg_t p, int64_t rows, int64_t ld, float** d_y) {
+  MGX_TRY
+  MGX_REQUIRE(p && d_y && rows >= 0 && ld >= 1, "mgx_agg_output: NULL or negative argument");
+  auto [ctx, g] = enter(p);
+  *d_y = agg_buffer(p, &mgx_agg_s::ybuf, &mgx_agg_s::ycap, (size_t)rows * (size_t)ld);
+  MGX_CATCH
+}
+int mgx_agg_result(mgx_agg_t p, float* host_y) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  require_run(p->last != 0, "mgx_agg_result");
+  auto [ctx, g] = enter(p);
+  ctx.synchronize();
+  if (host_y && p->last_rows > 0) {
+    MGX_HIP(hipMemcpy2DAsync(host_y, (size_t)p->last_feats * sizeof(float), p->last_y, (size_t)p->last_ldy * sizeof(float),
+                             (size_t)p->last_feats * sizeof(float), (size_t)p->last_rows, hipMemcpyDeviceToHost, ctx.stream()));
+    ctx.synchronize();
+  }
+  MGX_CATCH
+}
+int mgx_agg_bins(mgx_agg_t p, int64_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->last == 1, "mgx_agg_bins");
+  auto [ctx, g] = enter(p);
+  long long b[mgx::AGG_BINS];
+  p->fused->bins(b, ctx);
+  for (int i = 0; i < mgx::AGG_BINS; ++i) out[i] = b[i];
+  MGX_CATCH
+}
+int mgx_agg_set_timing(mgx_agg_t p, int on) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  p->timing = on != 0;
+  MGX_CATCH
+}
+int mgx_agg_phase_ms(mgx_agg_t p, double* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->last == 1, "mgx_agg_phase_ms");
+  auto [ctx, g] = enter(p);
+  p->fused->read_phases(out);
   MGX_CATCH
 }
 
