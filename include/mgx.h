@@ -56,6 +56,7 @@ typedef struct mgx_msbfs_s* mgx_msbfs_t;
 typedef struct mgx_rw_s* mgx_rw_t;
 typedef struct mgx_nsample_s* mgx_nsample_t;
 typedef struct mgx_agg_s* mgx_agg_t;
+typedef struct mgx_aggbwd_s* mgx_aggbwd_t;
 typedef struct mgx_louvain_s* mgx_louvain_t;
 typedef struct mgx_dbfs_s* mgx_dbfs_t;
 typedef struct mgx_dbfs2_s* mgx_dbfs2_t;
@@ -1183,6 +1184,74 @@ MGX_API int mgx_agg_bins(mgx_agg_t p, int64_t* out);
  * launches (waits for them) */
 MGX_API int mgx_agg_set_timing(mgx_agg_t p, int on);
 MGX_API int mgx_agg_phase_ms(mgx_agg_t p, double* out);
+
+/* ---- the backward of the neighbour feature aggregation (include/mgx/agg_backward.hpp, include/gunrock/aggbwd/) ----
+ * The gradient of mgx_agg_* with respect to the features: GX[c, f] = (+) over the selected rows' entries e with col_e == c of u_e,
+ * in a FIXED order of arithmetic: both paths and tests/aggbwd_model.py give the same float32 bits, on every run.  A handle of its
+ * own: the forward handle's state is never touched.  source, block, hop, op, weighted and MGX_AGG_SEG mean what they mean to
+ * mgx_agg_run (seg is read once per handle).
+ *   GY, X, GX float32 device arrays, row-major: GY is R x feats with ldgy (the gradient with respect to the forward's Y), X is the
+ *             forward's X, x_rows x feats with ldx, read by MAX and MIN only (d_x may be NULL for SUM and MEAN, and is then ignored),
+ *             GX is x_rows x feats with ldgx.  x_rows is at least n (the graph's rows) or the run's vertices (a block).  No two of
+ *             the three may overlap.  Every element of GX[:x_rows, :feats] is written on every run, the padding columns never.
+ *   upstream  g[r, f] = GY[r, f]; for MEAN GY[r, f] / float(d_r), one correctly rounded division BEFORE the weight
+ *   a term    u_e = g[row_e, f], or with weighted != 0 w_e * g[row_e, f] rounded once to float32, never fused with the add.  For MAX
+ *             and MIN u_e is that when e is the entry whose term the forward's fold kept for (row_e, f), and +0.0 otherwise
+ *             (selected, not multiplied).  The winner is recomputed from X in the forward's order: the first of equal values wins, a
+ *             leading NaN keeps the win, a later NaN never wins, a row without entries has none.
+ *   the order L_c, the entries with col_e == c, in ASCENDING e (the forward's stored order), cut into segments of seg entries: within
+ *             a segment acc = u_0, then acc = acc + u_j; the segments' values are added in segment order.  An empty L_c gives +0.0.
+ * The gradient with respect to the edge weights is not built.
+ * The transposed CSR (offsets, the forward row and the forward entry of every slot) is built on the device -- count by column, scan,
+ * cursor fill, a segmented sort of every transposed row by entry, so that no result depends on the order in which atomics land --
+ * by the first run on the out-rows and on the in-rows (kept for the handle's life, keyed by x_rows) and by every run on a block.
+ * MGX_E_INVALID before any device work, the message names the parameter: everything mgx_agg_run refuses, for its counterparts (feats,
+ * ldgy, ldgx, ldx with MAX / MIN, op, source, weighted without weights, in-rows without a CSC, the block, hop, x_rows below what the
+ * columns name, NULL d_gy or d_gx), d_x NULL with MAX or MIN, any two of GY, X and GX overlapping.
+ * stats (may be NULL), int64[10]: [0] transposed rows (x_rows), [1] entries, [2] feats, [3] team width G, [4] column tiles, [5] 1 on
+ * the vector path (feats, ldgy, ldgx multiples of 4 and both bases 16-byte aligned), [6] seg, [7] launches (mgx_aggbwd_enact:
+ * operator calls), [8] host waits, [9] 1 when this call built a transpose.  Launches and host waits of mgx_aggbwd_run, by case (L: 2
+ * more launches where transposed rows are longer than seg; W: the winners' 1 launch, 3 where forward rows are longer than seg):
+ *   repeat run on a kept transpose, SUM                                                 1 + L launches, 0 waits
+ *   repeat run on a kept transpose, MEAN                                                2 + L launches, 0 waits (the division is a pass
+ *       of its own that writes g = GY / d into a buffer of the handle's, R x feats)
+ *   repeat run on a kept transpose, MAX or MIN                                          1 + L + W launches, 0 waits
+ *   ... its first MAX or MIN on a source whose forward rows may be long                 + 2 launches, + 1 wait (the forward rows' plan)
+ *   the run that builds (first on out-rows / in-rows; every run on a block)             + 10 + P launches, + 2 waits: count, scan, fill,
+ *       the sort's classification and its three bands (each counted as run) and P = passes + (passes & 1) merge launches, with
+ *       passes = ceil(log2(longest transposed row / 2048)) where one is longer than 2048, the slots' rows, the plan's two; the waits
+ *       are the sort's and the plan's.  With fewer than 2 entries there is no sort (4 launches and 1 wait less), with none nothing.
+ *   a block                                                                              as the run that builds: at most 3 waits
+ *       (2, and the forward rows' plan for MAX / MIN where the sampling run had a fan-out of -1)
+ * A repeat run on a kept transpose does no host wait and allocates nothing; every array lives on the handle and only grows.  A call
+ * that is refused leaves no result: the getters return MGX_E_INVALID until a call succeeds. */
+MGX_API int mgx_aggbwd_create(mgx_graph_t g, mgx_aggbwd_t* out);
+MGX_API int mgx_aggbwd_free(mgx_aggbwd_t p);
+/* the fused path: a team of lanes per transposed row, the loads of 8 slots in flight, no atomics on GX */
+MGX_API int mgx_aggbwd_run(mgx_aggbwd_t p, int source, mgx_nsample_t block, int hop, const float* d_gy, int64_t ldgy, int feats, int op,
+                           int weighted, const float* d_x, int64_t ldx, int64_t x_rows, float* d_gx, int64_t ldgx, int64_t* stats);
+/* the operator path: one filter over GX's rows, a lane per transposed row (for MAX / MIN a filter over the forward rows first); the
+ * same transposed arrays, the same bits */
+MGX_API int mgx_aggbwd_enact(mgx_aggbwd_t p, int source, mgx_nsample_t block, int hop, const float* d_gy, int64_t ldgy, int feats, int op,
+                             int weighted, const float* d_x, int64_t ldx, int64_t x_rows, float* d_gx, int64_t ldgx, int64_t* stats);
+/* for callers with host arrays: mgx_aggbwd_upload copies host (rows x feats, contiguous) into the handle's array `which` (0: GY, 1:
+ * X) and gives its device address; mgx_aggbwd_output gives a handle-owned device array of rows x ld floats to pass as d_gx.  They
+ * grow only and stay valid until a larger request or free. */
+MGX_API int mgx_aggbwd_upload(mgx_aggbwd_t p, int which, const float* host, int64_t rows, int feats, float** d_out);
+MGX_API int mgx_aggbwd_output(mgx_aggbwd_t p, int64_t rows, int64_t ld, float** d_gx);
+/* the last call's GX[:x_rows, :feats] to the host, contiguous, from wherever the call wrote it; waits */
+MGX_API int mgx_aggbwd_result(mgx_aggbwd_t p, float* host_gx);
+/* the transposed arrays the last call ran on, to the host (each may be NULL): offsets int32[x_rows + 1], rows int32[entries] (the
+ * forward row of every slot, counted from the first selected row), pos int32[entries] (its forward entry, a place in the CSR's
+ * columns); waits */
+MGX_API int mgx_aggbwd_transpose(mgx_aggbwd_t p, int* offsets, int* rows, int* pos);
+/* int64[5] of the last fused run, counted by its own launches (waits): [0] transposed rows without entries, [1] of at most seg
+ * entries (a team's), [2] longer ones, [3] the segments of the latter, [4] seg */
+MGX_API int mgx_aggbwd_bins(mgx_aggbwd_t p, int64_t* out);
+/* timing (measurement tools; off by default): mgx_aggbwd_phase_ms gives out[5] = ms of the last fused run's transpose, winners,
+ * rows, items and fold (waits for them) */
+MGX_API int mgx_aggbwd_set_timing(mgx_aggbwd_t p, int on);
+MGX_API int mgx_aggbwd_phase_ms(mgx_aggbwd_t p, double* out);
 
 /* ---- vertex similarity for link prediction (include/mgx/sim_fused.hpp, include/gunrock/sim/) ----
  * How alike are two vertices' neighbourhoods, exactly, for arbitrary pairs.  The graph is the underlying simple undirected graph of

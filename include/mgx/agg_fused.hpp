@@ -28,8 +28,10 @@
 //                     only when the sampling run had a fan-out of -1 (else every row has <= 64 <= seg entries: ONE launch, no wait),
 //                     and is then rebuilt every run.
 // Grids are sized by bounds and capped at 8 workgroups a compute unit.
-// Not built: fp16 / bf16 features, the transposed (backward) aggregation over blocks, several blocks per launch,
-// features fused with the sampler's gather X[vertices], more than one device, MFMA (there is no dense weight matrix here).
+// The backward (the gradient with respect to X, over the transposed rows) is agg_backward.hpp; it shares the arithmetic,
+// the shape and the plan kernels below as they are.
+// Not built: fp16 / bf16 features, several blocks per launch, features fused with the sampler's gather
+// X[vertices], more than one device, MFMA (there is no dense weight matrix here).
 #pragma once
 #include <algorithm>
 #include <vector>

@@ -69,9 +69,11 @@ class Context:
         check(lib.mgx_ctx_create(int(device), C.c_void_p(stream or 0), C.byref(h)))
         self._h = h
         self.device = device
+        self.stream = int(stream or 0)         # the stream's address as given (0: the default stream), for callers that order work against it
 
     def set_stream(self, stream):
         check(lib.mgx_ctx_set_stream(self._h, C.c_void_p(stream or 0)))
+        self.stream = int(stream or 0)
 
     def synchronize(self):
         check(lib.mgx_ctx_synchronize(self._h))
@@ -1751,6 +1753,120 @@ class AggregateProblem(_Timed):
     def close(self):
         if self._h:
             lib.mgx_agg_free(self._h)
+            self._h = None
+
+
+class AggregateGradProblem(_Timed):
+    """The backward of AggregateProblem: GX[c, :] = the sum over the selected rows' entries e with col_e == c of the
+    upstream gradient's rows gy[row_e, :], optionally times the entry's weight -- the gradient with respect to the features x.
+    run() is the fused path (a team of lanes per TRANSPOSED row, no atomics on GX), enact() the operator path; both give the same
+    float32 bits as tests/aggbwd_model.py, on every run.  The fine print:
+      * rows=, block=, hop=, weighted= and op= say which forward is differentiated, as AggregateProblem takes them; gy has that
+        forward's rows, the result has x_rows rows (default: the graph's n, or the block's vertices);
+      * mean divides gy[r, f] by float32(d_r) first, one correctly rounded division, then the weight is applied, rounded once;
+        the multiply and the add are never fused;
+      * max and min need x= (the forward's x): the gradient goes to the entry whose term the forward's fold kept (the first of
+        equal values), every other entry contributes +0.0;
+      * a column's terms are added in ASCENDING entry order, the forward's stored order, in segments of seg (MGX_AGG_SEG) whose
+        values are added in segment order; a vertex that is nobody's neighbour gets +0.0;
+      * every element of the result is written on every run, padding columns (ldgx > feats) never;
+      * the gradient with respect to the edge weights is not built.
+    The transposed CSR is built on the device by the first run on the out-rows / in-rows and kept; for a block by every run.
+    gy, x and out may be numpy arrays (uploaded into the handle's buffers, the result stays in the handle's: result()), torch
+    tensors, or device addresses (then with rows_gy= / x_rows= and feats=)."""
+
+    _C = "mgx_aggbwd"
+    KEYS = ("rows", "entries", "feats", "team_width", "col_tiles", "vector", "seg", "launches", "host_waits", "built")
+    PHASES = ("transpose", "winners", "rows", "items", "fold")
+    BINS = ("none", "team", "long", "segments", "seg")
+    OPS = AggregateProblem.OPS
+    ROWS = AggregateProblem.ROWS
+
+    def __init__(self, graph):
+        h = C.c_void_p()
+        check(lib.mgx_aggbwd_create(graph._h, C.byref(h)))
+        self.graph, self._h = graph, h
+        self._last = None
+
+    def _device(self, a, which, ld, feats):
+        """-> (device address, leading dimension, rows, feats) of gy (which 0) or x (which 1)"""
+        if isinstance(a, np.ndarray):
+            ha = np.ascontiguousarray(a, dtype=np.float32)
+            if ha.ndim != 2:
+                raise ValueError("gy and x must be two-dimensional (rows, feats)")
+            d = C.c_void_p()
+            check(lib.mgx_aggbwd_upload(self._h, which, _ptr(ha), ha.shape[0], max(ha.shape[1], 1), C.byref(d)))
+            return d, ha.shape[1], ha.shape[0], ha.shape[1]
+        rows = None
+        if hasattr(a, "shape") and len(a.shape) == 2:
+            rows, feats = (int(s) for s in a.shape)
+            if ld is None and rows > 1:
+                ld = int(a.stride(0))
+        return _dev_ptr(a), ld, rows, feats
+
+    def _go(self, fn, gy, op, weighted, rows, block, hop, x, out, ldgy, ldx, ldgx, x_rows, feats):
+        if op not in self.OPS or rows not in self.ROWS:
+            raise ValueError("op must be one of %s and rows one of %s" % (self.OPS, self.ROWS))
+        self._last = None
+        d_gy, ldgy, _, feats = self._device(gy, 0, ldgy, feats)
+        if feats is None:
+            raise ValueError("a device address needs feats=")
+        ldgy = feats if ldgy is None else ldgy
+        d_x, have = None, None
+        if x is not None and op in ("max", "min"):
+            d_x, ldx, have, _ = self._device(x, 1, ldx, feats)
+            ldx = feats if ldx is None else ldx
+        if x_rows is None:
+            x_rows = have if have is not None else (self.graph.num_nodes if block is None else (block._last or {}).get("vertices", 0))
+        if out is None:
+            ldgx = feats if ldgx is None else ldgx
+            d = C.c_void_p()
+            check(lib.mgx_aggbwd_output(self._h, x_rows, max(ldgx, 1), C.byref(d)))
+            d_gx = d
+        else:
+            if ldgx is None:
+                ldgx = int(out.stride(0)) if hasattr(out, "stride") and len(out.shape) == 2 and out.shape[0] > 1 else feats
+            d_gx = _dev_ptr(out)
+        st = (C.c_int64 * 10)()
+        source = 2 if block is not None else self.ROWS.index(rows)
+        check(fn(self._h, source, None if block is None else block._h, -1 if hop is None else int(hop), d_gy, int(ldgy), int(feats),
+                 self.OPS.index(op), int(bool(weighted)), d_x, int(ldx or feats), int(x_rows), d_gx, int(ldgx), st))
+        self._last = dict(zip(self.KEYS, (int(v) for v in st)))
+        return dict(self._last)
+
+    def run(self, gy, op="sum", weighted=False, rows="out", block=None, hop=None, x=None, out=None, ldgy=None, ldx=None, ldgx=None, x_rows=None,
+            feats=None):
+        """fused path -> the stats dict of KEYS; a repeat run on a kept transpose only enqueues on the context's stream"""
+        return self._go(lib.mgx_aggbwd_run, gy, op, weighted, rows, block, hop, x, out, ldgy, ldx, ldgx, x_rows, feats)
+
+    def enact(self, gy, op="sum", weighted=False, rows="out", block=None, hop=None, x=None, out=None, ldgy=None, ldx=None, ldgx=None, x_rows=None,
+              feats=None):
+        """operator path (one filter over the result's rows, a lane per transposed row); the same bits"""
+        return self._go(lib.mgx_aggbwd_enact, gy, op, weighted, rows, block, hop, x, out, ldgy, ldx, ldgx, x_rows, feats)
+
+    def result(self):
+        """float32[x_rows, feats]: the last call's result, from wherever it was written (waits)"""
+        R, F = (self._last["rows"], self._last["feats"]) if self._last else (0, 1)
+        gx = np.zeros((max(R, 1), F), dtype=np.float32)
+        check(lib.mgx_aggbwd_result(self._h, _ptr(gx)))
+        return gx[:R]
+
+    def transpose(self):
+        """(offsets int32[x_rows + 1], rows int32[E], pos int32[E]): the transposed CSR the last call ran on (waits)"""
+        R, E = (self._last["rows"], self._last["entries"]) if self._last else (0, 0)
+        off, row, pos = np.zeros(R + 1, dtype=np.int32), np.zeros(max(E, 1), dtype=np.int32), np.zeros(max(E, 1), dtype=np.int32)
+        check(lib.mgx_aggbwd_transpose(self._h, _ptr(off), _ptr(row), _ptr(pos)))
+        return off, row[:E], pos[:E]
+
+    def bins(self):
+        """the last fused run's transposed rows without entries, of at most seg entries, longer ones, their segments, and seg (waits)"""
+        out = (C.c_int64 * 5)()
+        check(lib.mgx_aggbwd_bins(self._h, out))
+        return dict(zip(self.BINS, (int(v) for v in out)))
+
+    def close(self):
+        if self._h:
+            lib.mgx_aggbwd_free(self._h)
             self._h = None
 
 

@@ -26,6 +26,7 @@
 #include "gunrock/pr/pr_enactor.hxx"
 #include "gunrock/nsample/nsample_enactor.hxx"
 #include "gunrock/agg/agg_enactor.hxx"
+#include "gunrock/aggbwd/aggbwd_enactor.hxx"
 #include "gunrock/sim/sim_enactor.hxx"
 #include "gunrock/rw/rw_enactor.hxx"
 #include "gunrock/kcore/kcore_enactor.hxx"
@@ -49,6 +50,7 @@
 #include "mgx/sssp_dist.hpp"
 #include "mgx/rmat.hpp"
 #include "mgx/nsample_fused.hpp"
+#include "mgx/agg_backward.hpp"
 #include "mgx/agg_fused.hpp"
 #include "mgx/sim_fused.hpp"
 #include "mgx/rw_fused.hpp"
@@ -258,6 +260,19 @@ struct mgx_agg_s : mgx_problem_s {
   int last_rows = 0, last_feats = 0;
   bool timing = false;
   int seg = 0;                                                    // MGX_AGG_SEG as read at the handle's first call, for both paths (0: not yet)
+};
+
+struct mgx_aggbwd_s : mgx_problem_s {
+  std::unique_ptr<mgx::aggb_state_t> st;                          // lazily: the transposes, their plans, the winners, partials and control words
+  std::shared_ptr<aggbwd::aggbwd_problem_t> p;                    // lazily: the operator path's slice
+  std::unique_ptr<aggbwd::aggbwd_enactor_t> e;
+  mem_t<float> inbuf[2], outbuf;                                  // mgx_aggbwd_upload's (GY, X) and mgx_aggbwd_output's arrays, growing only
+  size_t incap[2] = {0, 0}, outcap = 0;
+  int last = 0;                                                   // 0: no run yet; 1: the fused path's result; 2: the operator path's
+  const float* last_gx = nullptr;                                 // where the last run wrote: rows x feats, leading dimension ldgx
+  long long last_ldgx = 0;
+  int last_rows = 0, last_feats = 0;
+  bool timing = false;
 };
 
 struct mgx_louvain_s : mgx_problem_s {
@@ -4074,6 +4089,203 @@ int mgx_agg_phase_ms(mgx_agg_t p, double* out) {
   require_run(p->last == 1, "mgx_agg_phase_ms");
   auto [ctx, g] = enter(p);
   p->fused->read_phases(out);
+  MGX_CATCH
+}
+
+// ---- the backward of the neighbour feature aggregation -----------------------------
+// a call's arguments, checked before any device work (the parameters first: their messages do not need a handle)
+static mgx::aggb_request_t aggbwd_check(mgx_aggbwd_t p, int source, mgx_nsample_t block, int hop, const float* d_gy, int64_t ldgy, int feats, int op,
+                                        int weighted, const float* d_x, int64_t ldx, int64_t x_rows, float* d_gx, int64_t ldgx, const char* who) {
+  const std::string w(who);
+  const bool minmax = op == mgx::AGG_MAX || op == mgx::AGG_MIN;
+  MGX_REQUIRE(feats >= 1 && feats <= mgx::AGG_MAX_FEATS, w + ": feats must be in [1, 65536]");
+  MGX_REQUIRE(ldgy >= feats && ldgx >= feats, w + ": ldgy and ldgx must be at least feats");
+  MGX_REQUIRE(op >= 0 && op < mgx::AGG_OPS, w + ": op must be 0 (sum), 1 (mean), 2 (max) or 3 (min)");
+  MGX_REQUIRE(!minmax || ldx >= feats, w + ": ldx must be at least feats (max and min read X)");
+  MGX_REQUIRE(source >= 0 && source < mgx::AGG_SOURCES, w + ": source must be 0 (out-rows), 1 (in-rows) or 2 (block)");
+  MGX_REQUIRE(x_rows >= 0 && x_rows <= INT_MAX, w + ": x_rows must be in [0, 2^31)");
+  MGX_REQUIRE(p, "NULL argument");
+  const graph_device_t& g = p->graph();
+  const size_t m = (size_t)g.num_edges;
+  mgx::aggb_request_t r;
+  r.gy = d_gy; r.x = minmax ? d_x : nullptr; r.gx = d_gx; r.ldgy = ldgy; r.ldx = ldx; r.ldgx = ldgx; r.feats = feats; r.op = op; r.source = source;
+  r.T = (int)x_rows;
+  long long need_rows = g.num_nodes;
+  if (source == mgx::AGG_SRC_OUT) {
+    r.ro = g.d_row_offsets.data(); r.ci = g.d_col_indices.data();
+    MGX_REQUIRE(!weighted || g.d_col_values.size() >= m, w + ": weighted, and the graph has no weights");
+    if (weighted) r.w = g.d_col_values.data();
+    r.R = g.num_nodes; r.entries = g.num_edges;
+  } else if (source == mgx::AGG_SRC_IN) {
+    MGX_REQUIRE(!g.csc_is_csr, w + ": the in-rows need the graph's genuine CSC (mgx_graph_build_csc)");
+    r.ro = g.d_col_offsets.data(); r.ci = g.d_row_indices.data();
+    MGX_REQUIRE(!weighted || g.d_row_values.size() >= m, w + ": weighted, and the CSC has no weights");
+    if (weighted) r.w = g.d_row_values.data();
+    r.R = g.num_nodes; r.entries = g.num_edges;
+  } else {
+    MGX_REQUIRE(block, w + ": source 2 needs a block (an mgx_nsample_t)");
+    MGX_REQUIRE(block->g == p->g, w + ": the block was sampled from another graph");
+    MGX_REQUIRE(block->last != 0, w + ": the block has no successful sampling run");
+    const mgx::ns_results_t& res = block->last == 1 ? block->fused->res : block->op_state->res;
+    const int hops = (int)res.hop_offsets.size() - 2;
+    MGX_REQUIRE(hop >= -1 && hop < hops, w + ": hop must be -1 (all sampled rows) or in [0, the run's hops)");
+    MGX_REQUIRE(!weighted || g.d_col_values.size() >= m, w + ": weighted, and the graph has no weights");
+    need_rows = res.count_vertices();
+    if (res.device) {
+      const int h0 = hop < 0 ? 0 : hop, h1 = hop < 0 ? hops : hop + 1;
+      r.ro = res.row_offsets.data() + res.hop_offsets[h0]; r.ci = res.cols.data();
+      r.R = res.hop_offsets[h1] - res.hop_offsets[h0];
+      r.e0 = res.edge_offsets[h0];
+      r.entries = res.edge_offsets[h1] - res.edge_offsets[h0];
+      if (weighted) { r.w = g.d_col_values.data(); r.entry_pos = res.entry_pos.data(); }
+      r.needs_plan = res.any_whole;
+    }
+  }
+  MGX_REQUIRE(x_rows >= need_rows, w + ": x_rows is below the number of vertices the columns name");
+  MGX_REQUIRE(x_rows == 0 || d_gx, w + ": d_gx is NULL");
+  MGX_REQUIRE(r.R == 0 || d_gy, w + ": d_gy is NULL");
+  MGX_REQUIRE(!minmax || r.R == 0 || d_x, w + ": d_x is NULL, and max and min need the forward's X");
+  // the three ranges, pairwise
+  struct range_t { const char* b; const char* e; const char* name; };
+  auto range = [](const float* p0, long long rows, long long ld, int f, const char* name) {
+    const char* const b = (const char*)p0;
+    return range_t{b, (p0 && rows > 0) ? b + ((size_t)(rows - 1) * (size_t)ld + (size_t)f) * sizeof(float) : b, name};
+  };
+  const range_t rg[3] = {range(d_gy, r.R, ldgy, feats, "GY"), range(r.x, r.R > 0 ? x_rows : 0, ldx, feats, "X"), range(d_gx, x_rows, ldgx, feats, "GX")};
+  for (int i = 0; i < 3; ++i)
+    for (int j = i + 1; j < 3; ++j)
+      MGX_REQUIRE(rg[i].b == rg[i].e || rg[j].b == rg[j].e || rg[i].e <= rg[j].b || rg[j].e <= rg[i].b,
+                  w + ": the ranges of " + rg[i].name + " and " + rg[j].name + " overlap");
+  return r;
+}
+static mgx::aggb_state_t& aggbwd_state(mgx_aggbwd_t p) {
+  if (!p->st) p->st.reset(new mgx::aggb_state_t(mgx::agg_seg_from_env()));      // (MGX_AGG_SEG is read once per handle, as the forward reads it)
+  return *p->st;
+}
+static void aggbwd_ran(mgx_aggbwd_t p, const mgx::aggb_request_t& r, int which) {
+  p->last_gx = r.gx; p->last_ldgx = r.ldgx; p->last_rows = r.T; p->last_feats = r.feats;
+  p->last = which;
+}
+int mgx_aggbwd_create(mgx_graph_t g, mgx_aggbwd_t* out) { return create_handle(g, out); }
+int mgx_aggbwd_free(mgx_aggbwd_t p) { return free_handle(p); }
+int mgx_aggbwd_run(mgx_aggbwd_t p, int source, mgx_nsample_t block, int hop, const float* d_gy, int64_t ldgy, int feats, int op, int weighted,
+                   const float* d_x, int64_t ldx, int64_t x_rows, float* d_gx, int64_t ldgx, int64_t* stats) {
+  MGX_TRY
+  if (p) p->last = 0;                                        // (a run that is refused leaves nothing to the getters)
+  const mgx::aggb_request_t r = aggbwd_check(p, source, block, hop, d_gy, ldgy, feats, op, weighted, d_x, ldx, x_rows, d_gx, ldgx, "mgx_aggbwd_run");
+  auto [ctx, g] = enter(p);
+  mgx::aggb_state_t& st = aggbwd_state(p);
+  st.timing = p->timing;
+  const std::vector<long long> s = st.run(r, ctx);
+  aggbwd_ran(p, r, 1);
+  put_stats(stats, mgx::AGGB_STATS, s);
+  MGX_CATCH
+}
+int mgx_aggbwd_enact(mgx_aggbwd_t p, int source, mgx_nsample_t block, int hop, const float* d_gy, int64_t ldgy, int feats, int op, int weighted,
+                     const float* d_x, int64_t ldx, int64_t x_rows, float* d_gx, int64_t ldgx, int64_t* stats) {
+  MGX_TRY
+  if (p) p->last = 0;
+  const mgx::aggb_request_t r = aggbwd_check(p, source, block, hop, d_gy, ldgy, feats, op, weighted, d_x, ldx, x_rows, d_gx, ldgx, "mgx_aggbwd_enact");
+  auto [ctx, g] = enter(p);
+  mgx::aggb_state_t& st = aggbwd_state(p);
+  const mgx::agg_shape_t sh = mgx::agg_shape(feats, mgx::agg_vector_ok(d_gy, ldgy, d_gx, ldgx, feats));
+  long long calls = 0, waits = 0, launches = 0;
+  bool built = false;
+  st.last_tr = nullptr;
+  if (r.T > 0) {
+    built = st.prepare(r, ctx, launches, waits);              // (the transpose's own launches are not operator calls: its waits are counted)
+    const mgx::aggb_transpose_t& t = st.tr[r.source];
+    const bool minmax = r.x != nullptr && r.R > 0;
+    const long long ldw = ((long long)feats + 3) / 4 * 4;
+    const aggbwd::aggbwd_problem_t::data_slice_t slice = {t.t_off.data(), t.t_row.data(), t.t_pos.data(), r.ro, r.ci, r.w ? r.entry_pos : nullptr, r.w,
+                                                          r.gy, r.x, r.gx, minmax ? st.ensure_win(r.R, feats, ctx) : nullptr,
+                                                          r.ldgy, r.ldx, r.ldgx, ldw, r.feats, r.op, st.seg};
+    if (!p->p) p->p = std::make_shared<aggbwd::aggbwd_problem_t>(p->g->g, slice, ctx);
+    else MGX_HIP(mgx::htod(p->p->d_data_slice.data(), &slice, 1, ctx.stream()));
+    ++waits;
+    if (!p->e) p->e.reset(new aggbwd::aggbwd_enactor_t());
+    p->e->enact(p->p, r.R, r.T, minmax, ctx);
+    calls = p->e->calls; waits += p->e->waits;
+  }
+  aggbwd_ran(p, r, 2);
+  put_stats(stats, mgx::AGGB_STATS, {r.T, r.entries, r.feats, sh.G, sh.tiles, sh.vector, st.seg, calls, waits, built ? 1 : 0});
+  MGX_CATCH
+}
+// a handle-owned array grown to `want` floats (growing only)
+static float* aggbwd_buffer(mgx_aggbwd_t p, mem_t<float>& buf, size_t& cap, size_t want) {
+  if (want > cap) {
+    p->ctx().synchronize();                                  // (a queued run may still read the old one)
+    buf = mem_t<float>();
+    cap = 0;
+    buf = mem_t<float>(want, p->ctx());
+    cap = want;
+  }
+  return buf.data();
+}
+int mgx_aggbwd_upload(mgx_aggbwd_t p, int which, const float* host, int64_t rows, int feats, float** d_out) {
+  MGX_TRY
+  MGX_REQUIRE(p && d_out && rows >= 0 && feats >= 1 && (host || rows == 0), "mgx_aggbwd_upload: NULL or negative argument");
+  MGX_REQUIRE(which == 0 || which == 1, "mgx_aggbwd_upload: which must be 0 (GY) or 1 (X)");
+  auto [ctx, g] = enter(p);
+  const size_t count = (size_t)rows * (size_t)feats;
+  *d_out = aggbwd_buffer(p, p->inbuf[which], p->incap[which], count);
+  MGX_HIP(mgx::htod(*d_out, host, count, ctx.stream()));
+  MGX_CATCH
+}
+int mgx_aggbwd_output(mgx_aggbwd_t p, int64_t rows, int64_t ld, float** d_gx) {
+  MGX_TRY
+  MGX_REQUIRE(p && d_gx && rows >= 0 && ld >= 1, "mgx_aggbwd_output: NULL or negative argument");
+  auto [ctx, g] = enter(p);
+  *d_gx = aggbwd_buffer(p, p->outbuf, p->outcap, (size_t)rows * (size_t)ld);
+  MGX_CATCH
+}
+int mgx_aggbwd_result(mgx_aggbwd_t p, float* host_gx) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  require_run(p->last != 0, "mgx_aggbwd_result");
+  auto [ctx, g] = enter(p);
+  ctx.synchronize();
+  if (host_gx && p->last_rows > 0) {
+    MGX_HIP(hipMemcpy2DAsync(host_gx, (size_t)p->last_feats * sizeof(float), p->last_gx, (size_t)p->last_ldgx * sizeof(float),
+                             (size_t)p->last_feats * sizeof(float), (size_t)p->last_rows, hipMemcpyDeviceToHost, ctx.stream()));
+    ctx.synchronize();
+  }
+  MGX_CATCH
+}
+int mgx_aggbwd_transpose(mgx_aggbwd_t p, int* offsets, int* rows, int* pos) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  require_run(p->last != 0, "mgx_aggbwd_transpose");
+  const mgx::aggb_transpose_t* t = p->st->last_tr;
+  if (t) {
+    if (offsets) read_back(p, offsets, (const int*)t->t_off.data(), (size_t)t->T + 1);
+    if (rows) read_back(p, rows, (const int*)t->t_row.data(), (size_t)t->E);
+    if (pos) read_back(p, pos, (const int*)t->t_pos.data(), (size_t)t->E);
+  }
+  MGX_CATCH
+}
+int mgx_aggbwd_bins(mgx_aggbwd_t p, int64_t* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->last == 1, "mgx_aggbwd_bins");
+  auto [ctx, g] = enter(p);
+  long long b[mgx::AGGB_BINS];
+  p->st->bins(b, ctx);
+  for (int i = 0; i < mgx::AGGB_BINS; ++i) out[i] = b[i];
+  MGX_CATCH
+}
+int mgx_aggbwd_set_timing(mgx_aggbwd_t p, int on) {
+  MGX_TRY
+  MGX_REQUIRE(p, "NULL argument");
+  p->timing = on != 0;
+  MGX_CATCH
+}
+int mgx_aggbwd_phase_ms(mgx_aggbwd_t p, double* out) {
+  MGX_TRY
+  MGX_REQUIRE(p && out, "NULL argument");
+  require_run(p->last == 1, "mgx_aggbwd_phase_ms");
+  auto [ctx, g] = enter(p);
+  p->st->read_phases(out);
   MGX_CATCH
 }
 
